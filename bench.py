@@ -10,23 +10,29 @@ with the SAM text in pinned host memory.
   N = 1 (default)   BASELINE.json configs[2]: 1 M x 150 bp reads, one resident batch                          ("weak")
   N > 1 (default)   BASELINE.json configs[3]: ONE read set of 10 M reads, sharded by contiguous ranges over the ranks; a rank
                     goes through its shard in resident chunks of <= --reads reads (moni_reads_swap)           ("strong")
-                    and, after the timed steps, the per-rank SAM blocks go to rank 0 over RCCL (sizes by all-gather, blocks by
-                    send/recv): the `gather` block of the line; --no-gather-sam skips it
+                    and, with --full, after the timed steps, the per-rank SAM blocks go to rank 0 over RCCL (sizes by all-gather,
+                    blocks by send/recv): the `gather` block of the line; --no-gather-sam skips it
   --total-reads T   the sharded mode with T reads at any N (N = 1: the same set on one GPU, the base of the scaling curve)
 
 `python bench.py --gpus N` starts the N rank processes itself when it is not already running under a launcher (no RANK in the
 environment): fresh children, one GPU each, RCCL; the parent never touches the GPU.  Under `python -m torch.distributed.run` the
 ranks come from the launcher.  --dry-run rehearses the launch, the sharding and the gather on CPU (gloo) without any GPU.
 
+A plain run sets up (the index comes from --cache when an earlier run left it there; otherwise it is built on the GPU and written
+there), warms up, times --steps steps, writes the outputs of a step with --dump-outputs DIR and prints the line.  --full adds the
+legs beside the headline, each after the timed steps (the paired path's `from_host` before them).
+
 Prints ONE JSON line (rank 0).  Everything in it is measured in this run: `roofline` prices ms_lf_kernel (the path's HBM-bound
 kernel) with HIP events recorded inside the library on the kernel's own stream; `whole_path` prices the step against SURVEY.md
 §8(d)'s bytes(read) = 128 S + 64 J + 128 P + C + R with all five counted by the kernels; `align` carries the HIP-event times of
-the align kernels by group and the DP rate; `from_host` is the same batch from host memory to SAM text in host memory
-(moni_align_stream: upload included); `cpu_baseline` is the CPU oracle's whole path on a bounded sample (rank 0, N == 1).
+the align kernels by group and the DP rate.  With --full: `from_host` is the same batch from host memory to SAM text in host memory
+(moni_align_stream: upload included); `cpu_baseline` is the CPU oracle's whole path on a bounded sample (rank 0, N == 1);
+`seeding` the seeding stage alone; `single_context` one context by itself; `scaling_base` configs[3]'s read set on one GPU.
 HBM traffic from rocprofv3 PMC passes cannot be collected from inside this process; the last committed pass is named under
 `roofline.traffic_static_from` and never mixed into the measured fields.
 """
 import argparse
+import hashlib
 import json
 import os
 import socket
@@ -34,6 +40,7 @@ import subprocess
 import sys
 import threading
 import time
+import zlib
 
 # HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default); the align stage runs its launches on
 # two streams next to a copy stream and two hand-over streams (the paired path on ~11), and with RCCL's own streams in the process
@@ -82,7 +89,7 @@ def parse_args(argv=None):
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--repeats", type=float, default=0.0, help="fraction of the base genome made of interspersed repeat copies (SURVEY.md 8(d): 0.05)")
     ap.add_argument("--fasta-index", action="store_true", help="the same text as a FASTA-built index (null lifts)")
-    ap.add_argument("--gather-sam", dest="gather_sam", action="store_true", default=None, help="gather the per-rank SAM blocks on rank 0 over RCCL after the timed steps (default at N > 1)")
+    ap.add_argument("--gather-sam", dest="gather_sam", action="store_true", default=None, help="gather the per-rank SAM blocks on rank 0 over RCCL after the timed steps (default with --full at N > 1)")
     ap.add_argument("--no-gather-sam", dest="gather_sam", action="store_false")
     ap.add_argument("--verify-gather", action="store_true", help="rank 0 also aligns the whole read set by itself and compares the gathered text with it byte for byte (rehearsals: use a small --total-reads)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -98,8 +105,58 @@ def parse_args(argv=None):
     ap.add_argument("-Z", "--secondary-chains", dest="secondary_chains", action="store_true", help="--paired: find_chains_secondary (the reference's -Z) in the learning batches and the alignment")
     ap.add_argument("--pairs", type=int, default=1000000, help="--paired: read pairs (per GPU; sharded by contiguous ranges like the reads when --total-reads is given)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: launch, rendezvous (gloo), sharding and the SAM gather with placeholder records")
-    ap.add_argument("--cache", default="/tmp/moni_bench_cache")
+    ap.add_argument("--cache", default="/tmp/moni_bench_cache", help="directory of the flat index files a run builds once and later runs reuse")
+    ap.add_argument("--full", action="store_true", help="also run the legs beside the headline: one context alone, the seeding stage alone, the batch from host memory, the CPU baselines, "
+                                                       "configs[3]'s read set on one GPU and (N > 1) the SAM gather; without it a run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the timed path computes (rank 0's SAM records: a CRC-32 per record, "
+                                                                        "numeric fields of a seeded sample, counts) as DIR/<name>.npy in float64")
     return ap.parse_args(argv)
+
+
+def builder_digest() -> str:
+    """digest of the code that makes the text and builds the index, written beside a cache file (<file>.src): a file whose digest
+    differs was written by another version of the builder and is built again"""
+    h = hashlib.sha1()
+    for f in ("index_build.py", "synth.py"):
+        with open(os.path.join(ROOT, "moni_align_amd", f), "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def cached_index_usable(path: str) -> bool:
+    try:
+        return os.path.exists(path) and open(path + ".src").read().strip() == builder_digest()
+    except OSError:
+        return False
+
+
+DUMP_SAMPLE = 500000          # records whose fields --dump-outputs writes (a seeded sample of a larger step): 32 MB, with the CRCs of 2 M records < 64 MB in all
+
+
+def dump_outputs(d: str, sam: bytes) -> None:
+    """--dump-outputs: the SAM records of a step as float64 arrays, so that the outputs of two builds can be compared record for record.
+      sam_record_crc32.npy  [n]     CRC-32 of every record line (newline excluded), in output order
+      sam_fields.npy        [m, 8]  a seeded sample of m = min(n, DUMP_SAMPLE) records: record number, FLAG, POS, MAPQ, PNEXT, TLEN, AS, 1 with an AS:i tag
+                              (AS 0 and 0 without one: every value finite)
+      sam_counts.npy        [3]     records, records with FLAG 4 clear, bytes of text"""
+    os.makedirs(d, exist_ok=True)
+    lines = sam[:-1].split(b"\n") if sam.endswith(b"\n") else (sam.split(b"\n") if sam else [])
+    n = len(lines)
+    crc = np.fromiter((zlib.crc32(x) for x in lines), dtype=np.float64, count=n)
+    pick = np.sort(np.random.default_rng(2026).choice(n, size=DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    f = np.zeros((len(pick), 8))
+    for j, i in enumerate(pick):
+        c = lines[i].split(b"\t", 11)
+        f[j, :6] = (i, int(c[1]), int(c[3]), int(c[4]), int(c[7]), int(c[8]))
+        a = lines[i].find(b"\tAS:i:")
+        if a >= 0:
+            e = lines[i].find(b"\t", a + 6)
+            f[j, 6:] = (int(lines[i][a + 6:e if e >= 0 else len(lines[i])]), 1)
+    mapped = sum(not (int(x.split(b"\t", 2)[1]) & 4) for x in lines)
+    np.save(os.path.join(d, "sam_record_crc32.npy"), crc)
+    np.save(os.path.join(d, "sam_fields.npy"), f)
+    np.save(os.path.join(d, "sam_counts.npy"), np.array([n, mapped, len(sam)], dtype=np.float64))
+    log("outputs written to %s: %d records (%d mapped), fields of %d" % (d, n, mapped, len(pick)))
 
 
 # ---- launcher: `python bench.py --gpus N` outside torch.distributed.run -------------------------------------------------
@@ -205,7 +262,7 @@ def run_rank(args) -> int:
 
     total = args.total_reads if args.total_reads >= 0 else (CONFIGS3_READS if world > 1 else 0)
     sharded = total > 0
-    gather_on = (world > 1) if args.gather_sam is None else (args.gather_sam and world > 1)
+    gather_on = (world > 1 and args.full) if args.gather_sam is None else (args.gather_sam and world > 1)
 
     # ---- inputs (seeded, synthetic: SURVEY.md §8(d)) -------------------------------------------------
     # Wall time of every phase in front of the timed region goes to stderr (rank 0) and into the line (`setup_s`): at N ranks the order is
@@ -242,7 +299,7 @@ def run_rank(args) -> int:
     fi = None
     mine = None
     if rank == 0:
-        if os.path.exists(path):
+        if cached_index_usable(path):
             t0 = time.time()
             fi = index_build.FlatIndex.load(path, mmap=True)
             phase("cached flat index mapped (%s)" % path, t0)
@@ -251,18 +308,19 @@ def run_rank(args) -> int:
             fi = index_build.build_from_pangenome(pg, device="cuda:%d" % local_rank, log=log, lifted=not args.fasta_index)
             torch.cuda.empty_cache()
             phase("flat index built on the GPU (n=%d r=%d n/r=%.2f)" % (fi.n, fi.r, fi.n / fi.r), t0)
-            if world > 1 or os.environ.get("MONI_BENCH_SAVE_INDEX"):
-                t0 = time.time()
+            t0 = time.time()          # for the next run, and for the other ranks (N > 1)
+            try:
+                fi.save(path + ".tmp")
+                os.replace(path + ".tmp", path)
+                with open(path + ".src", "w") as fh:
+                    fh.write(builder_digest() + "\n")
+                phase("index cache written", t0)
+            except OSError as e:          # (no room for the cache file: the next run builds the index again, the other ranks on their own GPUs)
+                log("could not write the index cache %s: %s" % (path, e))
                 try:
-                    fi.save(path + ".tmp")
-                    os.replace(path + ".tmp", path)
-                    phase("index cache written", t0)
-                except OSError as e:          # (no room for the 10 GB cache file: the other ranks then build the index on their own GPUs)
-                    log("could not write the index cache %s: %s" % (path, e))
-                    try:
-                        os.remove(path + ".tmp")
-                    except OSError:
-                        pass
+                    os.remove(path + ".tmp")
+                except OSError:
+                    pass
     elif not args.paired:
         t0 = time.time()
         mine = my_reads()          # while rank 0 builds the index
@@ -326,7 +384,7 @@ def run_rank(args) -> int:
             ctxs[owner[k]].swap(slot[k])                  # parked in HBM; swapped in for its turn
         chunk.append((names[int(noff[a]):int(noff[b])], (noff[a:b + 1] - noff[a]).astype(np.uint64), quals[a * L:b * L], b - a))
     offs = np.arange(0, (n_mine + 1) * L, L, dtype=np.uint64)
-    pg_keep = pg if (rank == 0 and world == 1 and not sharded and not args.no_scaling_base) else None      # (the scaling-base leg generates its read set from it)
+    pg_keep = pg if (args.full and rank == 0 and world == 1 and not sharded and not args.no_scaling_base) else None      # (the scaling-base leg generates its read set from it)
     del pg
     phases.append(("reads [%d, %d) resident in %d chunk(s)" % (lo, hi, n_chunks), 0.0))
     log("rank %d: reads [%d, %d) resident in %d chunk(s); setup took %.1fs" % (rank, lo, hi, n_chunks, time.time() - t_start))
@@ -443,9 +501,14 @@ def run_rank(args) -> int:
     cnt = cnt // np.uint64(steps)
     sizes = mdist.gather_counts([tot["aligned"], sam_len, n_mine], dist, coll_dev)     # per-rank record counts
     mem_free, mem_total = torch.cuda.mem_get_info()          # with every context's working memory allocated (grow-only buffers, kept across batches)
+    if args.dump_outputs and rank == 0:          # the text of a step: one more pass over the same resident chunks (the path is deterministic)
+        sam_bytes, _ = one_pass(want_text=True)
+        dump_outputs(args.dump_outputs, sam_bytes)
+        del sam_bytes
+    # ---- --full: the legs beside the headline ------------------------------------------------------------------------------------
     # one context alone (no second step beside it): the latency of a step, and the kernels' durations without a neighbour
     single = None
-    if inflight > 1 and shared_batch and not args.no_single_context:
+    if args.full and inflight > 1 and shared_batch and not args.no_single_context:
         sub_was = os.environ.pop("MONI_ALIGN_SUB", None)
         one_pass(ci=0)
         sync_all()
@@ -498,21 +561,22 @@ def run_rank(args) -> int:
         cx.close()
 
     # ---- seeding stage alone (BASELINE.json configs[1]) on the first resident chunk ------------------------------------------
-    if n_own[0] > 1:
-        ctx.swap(0)
-    ts = time.perf_counter()
-    n_seed_rep = 3
-    for _ in range(n_seed_rep):
-        ctx.seed_run(25, True, 1000)
-    torch.cuda.synchronize()
-    seed_s = (time.perf_counter() - ts) / n_seed_rep
-    res = ctx.seed_fetch()
-    n_mems, n_occs = len(res["mems"]), len(res["occs"])
     n_first = chunk[0][3]
+    if args.full:
+        if n_own[0] > 1:
+            ctx.swap(0)
+        ts = time.perf_counter()
+        n_seed_rep = 3
+        for _ in range(n_seed_rep):
+            ctx.seed_run(25, True, 1000)
+        torch.cuda.synchronize()
+        seed_s = (time.perf_counter() - ts) / n_seed_rep
+        res = ctx.seed_fetch()
+        n_mems, n_occs = len(res["mems"]), len(res["occs"])
 
     # ---- the same batch from host memory: upload + whole path + text in host memory (moni_align_stream) ----------------------
     from_host = None
-    if rank == 0 and world == 1 and not args.no_from_host:
+    if args.full and rank == 0 and world == 1 and not args.no_from_host:
         nm, no, ql, nb = chunk[0]
         rd = reads[:nb].reshape(-1)
         ob = offs[:nb + 1]
@@ -677,10 +741,11 @@ def run_rank(args) -> int:
             "setup_s": {"total": setup_s, "phases": [[n_, round(d_, 2)] for n_, d_ in phases], "note": "rank 0's wall time in front of the timed region"},
             "kernels_ms": {"ms_lf": kern_launch[0], "mem_count": kern_launch[1], "mem_emit": kern_launch[2], "occ_count": kern_launch[3], "occ_fill": kern_launch[4],
                            "seeding_whole": kern_launch[6], "note": "per launch (one launch per resident chunk)"},
-            "seeding": {"workload": "BASELINE.json configs[1]: MEM seeding stage alone on rank 0's first resident chunk (%d reads)" % n_first,
-                        "value": n_first / seed_s, "unit": "reads/s", "ms_per_pass": seed_s * 1e3,
-                        "work_per_pass": {"lf_steps": int(S1), "threshold_jumps": int(J1), "phi_steps": P // n_chunks, "text_bytes": C // n_chunks, "mems": n_mems, "occs": n_occs}},
         }
+        if args.full:
+            out["seeding"] = {"workload": "BASELINE.json configs[1]: MEM seeding stage alone on rank 0's first resident chunk (%d reads)" % n_first,
+                              "value": n_first / seed_s, "unit": "reads/s", "ms_per_pass": seed_s * 1e3,
+                              "work_per_pass": {"lf_steps": int(S1), "threshold_jumps": int(J1), "phi_steps": P // n_chunks, "text_bytes": C // n_chunks, "mems": n_mems, "occs": n_occs}}
         if gather:
             out["gather"] = gather
             out["value_with_gather"] = n_all / (step_s + gather["seconds"])
@@ -697,7 +762,7 @@ def run_rank(args) -> int:
         out["host"] = {"cpus_usable": host_cpus(), "cpu_count": os.cpu_count(), "host_threads_per_gpu": threads}
         out["device_memory_GB"] = {"used_after_timed_region": (mem_total - mem_free) / 1e9, "total": mem_total / 1e9,
                                    "note": "rank 0's GPU: index image + the working memory of its %d context(s)" % inflight}
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             from oracle import orc as _orc          # the CPU baseline / at-scale checker: the only use of oracle/ in this file
             oidx = _orc.OracleIndex(fi=fi)          # (rank 0 holds the flat index: built here or mapped from the cache file)
             cpu_threads = host_cpus()
@@ -789,7 +854,7 @@ def run_paired(args, rank, world, dist, coll_dev, backend, pg, fi, idx, ctx, pha
     st = None
     # reads handed over in host memory (moni_pe_align_stream: the upload inside the call): reported beside the headline, never as `value`
     from_host = None
-    if not args.no_from_host:
+    if args.full and not args.no_from_host:
         ctx.pe_align(seq, offs, nm, no, ql, model, host_threads=threads, want_text=False, stream=True, secondary_chains=zsec)
         t1 = time.perf_counter()
         for _ in range(max(1, args.steps)):
@@ -846,7 +911,7 @@ def run_paired(args, rank, world, dist, coll_dev, backend, pg, fi, idx, ctx, pha
     elapsed = mdist.max_over_ranks(time.perf_counter() - t0, dist, coll_dev)
     sam_len, st = last["r"]
     single = None
-    if inflight > 1 and not args.no_single_context:
+    if args.full and inflight > 1 and not args.no_single_context:
         n1s = max(1, min(3, args.steps))
         t1 = time.perf_counter()
         for _ in range(n1s):
@@ -858,6 +923,8 @@ def run_paired(args, rank, world, dist, coll_dev, backend, pg, fi, idx, ctx, pha
         cx.close()
     lf_ms = ctx.kernel_ms(0)                      # ms_lf_kernel of the last step (one launch over the 2 N mates), HIP events on its own stream
     S_lf, J_lf = (int(x) for x in ctx.counters()[:2])
+    if args.dump_outputs and rank == 0:          # the text of a step: one more pass over the same resident mates (the path is deterministic)
+        dump_outputs(args.dump_outputs, ctx.pe_align_run(nm, no, ql, model, host_threads=threads, want_text=True, secondary_chains=zsec)[0])
     sizes = mdist.gather_counts([st["aligned"], hi - lo], dist, coll_dev)
     if rank == 0:
         steps = max(1, args.steps)
@@ -883,7 +950,7 @@ def run_paired(args, rank, world, dist, coll_dev, backend, pg, fi, idx, ctx, pha
             out["from_host"] = from_host
         if single is not None:
             out["single_context"] = single
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             from oracle import orc as _orc          # the CPU baseline / at-scale checker
             oidx = _orc.OracleIndex(fi=fi)
             cpu_threads = host_cpus()

@@ -120,9 +120,7 @@ def test_cli_report_mems_legacy_outputs_and_mouse_fixture_reads(exe, medium_case
 
 def test_reference_fixture_reads_parse(exe):
     """data/mouse/reads/mouse.chr19.R1.fastq of the reference (5000 x 100 bp, names with /1): both readers give the same batch."""
-    src = "/root/reference/data/mouse/reads/mouse.chr19.R1.fastq"
-    if not os.path.exists(src):
-        pytest.skip("the reference checkout is not on this machine")
+    src = os.path.join(ROOT, "tests", "golden", "ref_data", "mouse", "mouse.chr19.R1.fastq")
     out = subprocess.check_output([exe, "x", "-p", src, "--dry-run"]).decode()
     assert "reads=5000 bases=500000" in out
     first = open(src).readline().split()[0][1:]
