@@ -294,7 +294,36 @@ int moni_pe_align_csv_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, con
  * the direction and frequency filters leave, under its mate's name.  *sam is malloc'ed. */
 int moni_pe_report_mems_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const uint8_t *names, const uint64_t *name_off,
                               const uint8_t *quals, const moni_align_params_t *prm, const moni_pe_params_t *pe, char **sam, uint64_t *sam_len);
-/* aligner::to_sam (aligner_ksw2.hpp:3213-3219): "@HD", one "@SQ" per sequence, "@PG". */
+/* ---- extend mode: the legacy `moni extend` (include/extender/extender_ksw2.hpp, include/extender/extend_reads_dispatcher.hpp:435-486) ---- */
+/* extender::config_t (extender_ksw2.hpp:82-102) with its defaults.  w and zdrop must stay negative (the full matrix, no z-drop: what the reference
+ * passes); ext_len <= 512 and reads of at most 2048 bases (MONI_ERANGE beyond, as for a line or a CIGAR that exceeds the kernels' staging). */
+typedef struct {
+    uint32_t min_len, ext_len;                            /* 25, 100 */
+    int8_t smatch, smismatch, gapo, gape;                 /* 2, 4, 4, 2 */
+    int32_t end_bonus, w, zdrop;                          /* 400, -1, -1 */
+    uint32_t reserved;
+} moni_extend_params_t;
+typedef struct {
+    uint64_t reads, extended, records;                    /* extended: reads with a record on either strand (extend_reads_dispatcher.hpp:468-469) */
+    uint64_t dp_tasks, dp_cells;                          /* ksw_extz2_sse calls and their qlen x tlen */
+    double t_kernel;                                      /* seconds inside the kernels (HIP events; the chunks' transfers are not in it) */
+} moni_extend_stats_t;
+void moni_extend_params_default(moni_extend_params_t *p);
+/* Replaces the per-read loop of st_extend (extend_reads_dispatcher.hpp:452-476): for every read, strand 0 then strand 1 (complement() of
+ * common.hpp:556-571, reversed), extender::extend (extender_ksw2.hpp:192-244): find_longest_mem (261-296), one extension per side (306-399), the
+ * stitched CIGAR, MD / NM and the record (401-511, 526-576, 595-675).  At most one record per strand, none for a strand that does not pass
+ * score > min_score; no header, input order.  names / name_off / quals as in moni_align_batch.  *sam is malloc'ed (moni_free); an empty batch gives
+ * MONI_OK and zero bytes.  Where this differs from the reference on purpose: a MEM at mem_pos <= ext_len takes text [0, mem_pos) reversed as its left
+ * target (the reference reads ext_len - mem_pos bytes from position 0, extender_ksw2.hpp:343-346). */
+int moni_extend_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const uint8_t *names, const uint64_t *name_off, const uint8_t *quals,
+                      const moni_extend_params_t *prm, char **sam, uint64_t *sam_len, moni_extend_stats_t *stats);
+/* The same over the batch that moni_reads_upload made resident; *sam points into the context's text buffer (moni_align_run's: valid until the next
+ * *_run / *_stream / moni_extend_batch / moni_ctx_destroy on this context, NOT to be freed; NULL when there is no text). */
+int moni_extend_run(moni_ctx_t *ctx, const uint8_t *names, const uint64_t *name_off, const uint8_t *quals, const moni_extend_params_t *prm,
+                    char **sam, uint64_t *sam_len, moni_extend_stats_t *stats);
+/* aligner::to_sam (aligner_ksw2.hpp:3213-3219): "@HD", one "@SQ" per sequence, "@PG".  Also extend mode's header (extender::to_sam,
+ * extender_ksw2.hpp:739-745, whose "@HD" line is written with blanks - not valid SAM; this one has the tabs): every sequence of the concatenation
+ * is listed, with or without lifts. */
 int moni_sam_header(const moni_index_t *idx, char **sam, uint64_t *sam_len);
 
 /* ---- the reference's on-disk liftidx (<prefix>.ldx: include/aligner/liftidx.hpp:117-143 over include/common/seqidx.hpp:197-238) ---- */

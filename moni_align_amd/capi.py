@@ -28,6 +28,7 @@ EXPORTS = [
     "moni_ldx_info", "moni_ldx_rewrite", "moni_ldx_lift_batch", "moni_ldx_write",
     "moni_ms_file_info", "moni_ms_file_read", "moni_ms_file_write", "moni_index_load_reference", "moni_ms_lengths_batch", "moni_report_mems_batch",
     "moni_pe_params_default", "moni_pe_learn_batch", "moni_pe_align_batch", "moni_pe_align_stream", "moni_pe_align_run", "moni_pe_align_csv_batch", "moni_pe_report_mems_batch",
+    "moni_extend_params_default", "moni_extend_batch", "moni_extend_run",
 ]
 
 
@@ -77,6 +78,17 @@ class PeParamsC(C.Structure):
 class PeModelC(C.Structure):
     _fields_ = [("mean", C.c_double), ("std_dev", C.c_double), ("variance", C.c_double), ("sample_variance", C.c_double), ("m2", C.c_double),
                 ("count", C.c_uint64), ("complete", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ExtendParamsC(C.Structure):
+    _fields_ = [("min_len", C.c_uint32), ("ext_len", C.c_uint32),
+                ("smatch", C.c_int8), ("smismatch", C.c_int8), ("gapo", C.c_int8), ("gape", C.c_int8),
+                ("end_bonus", C.c_int32), ("w", C.c_int32), ("zdrop", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class ExtendStatsC(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("extended", C.c_uint64), ("records", C.c_uint64), ("dp_tasks", C.c_uint64), ("dp_cells", C.c_uint64),
+                ("t_kernel", C.c_double)]
 
 
 class DpParamsC(C.Structure):
@@ -159,6 +171,12 @@ def lib():
                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_align_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AlignParamsC),
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(AlignStatsC)]
+        L.moni_extend_params_default.argtypes = [C.POINTER(ExtendParamsC)]
+        L.moni_extend_params_default.restype = None
+        L.moni_extend_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ExtendParamsC),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(ExtendStatsC)]
+        L.moni_extend_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ExtendParamsC),
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(ExtendStatsC)]
         L.moni_sam_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_last_kernel_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
         L.moni_last_counters.argtypes = [C.c_void_p, C.c_void_p]
@@ -488,6 +506,44 @@ class Ctx:
                                     C.byref(prm), C.byref(out), C.byref(ln), C.byref(st)), "moni_align_run")
         sam = C.string_at(out, ln.value) if want_text else int(ln.value)      # the buffer belongs to the context
         return sam, _stats_dict(st)
+
+    def _extend_params(self, overrides):
+        prm = ExtendParamsC()
+        self._L.moni_extend_params_default(C.byref(prm))
+        for k, v in overrides.items():
+            setattr(prm, k, v)
+        return prm
+
+    def extend_batch(self, seq: np.ndarray, offsets: np.ndarray, names: np.ndarray, name_off: np.ndarray, quals=None, **overrides):
+        """moni_extend_batch (the legacy `moni extend`): (SAM records of the batch, no header; stats dict).  overrides: fields of
+        moni_extend_params_t (min_len, ext_len, smatch, smismatch, gapo, gape, end_bonus)."""
+        b, keep = self._batch(seq, offsets)
+        names = np.ascontiguousarray(names, dtype=np.uint8)
+        name_off = np.ascontiguousarray(name_off, dtype=np.uint64)
+        if quals is not None:
+            quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        prm = self._extend_params(overrides)
+        out, ln, st = C.c_void_p(), C.c_uint64(), ExtendStatsC()
+        _chk(self._L.moni_extend_batch(self._h, C.byref(b), names.ctypes.data, name_off.ctypes.data, quals.ctypes.data if quals is not None else None,
+                                       C.byref(prm), C.byref(out), C.byref(ln), C.byref(st)), "moni_extend_batch")
+        self.n_reads = len(offsets) - 1
+        try:
+            return C.string_at(out, ln.value), {f: getattr(st, f) for f, _ in ExtendStatsC._fields_}
+        finally:
+            self._L.moni_free(out)
+
+    def extend_run(self, names: np.ndarray, name_off: np.ndarray, quals=None, want_text: bool = True, **overrides):
+        """moni_extend_run over the batch made resident by upload(); want_text=False returns the length of the text instead of a copy."""
+        names = np.ascontiguousarray(names, dtype=np.uint8)
+        name_off = np.ascontiguousarray(name_off, dtype=np.uint64)
+        if quals is not None:
+            quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        prm = self._extend_params(overrides)
+        out, ln, st = C.c_void_p(), C.c_uint64(), ExtendStatsC()
+        _chk(self._L.moni_extend_run(self._h, names.ctypes.data, name_off.ctypes.data, quals.ctypes.data if quals is not None else None,
+                                     C.byref(prm), C.byref(out), C.byref(ln), C.byref(st)), "moni_extend_run")
+        sam = (C.string_at(out, ln.value) if ln.value else b"") if want_text else int(ln.value)      # the buffer belongs to the context
+        return sam, {f: getattr(st, f) for f, _ in ExtendStatsC._fields_}
 
     def ms_lengths_batch(self, seq: np.ndarray, offsets: np.ndarray):
         """legacy `moni ms`: (pointers, lengths) of the forward strand of every read"""

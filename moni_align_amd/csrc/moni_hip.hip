@@ -37,6 +37,7 @@
 #include "align_fast.hip"
 #include "pe_fast.hip"
 #include "pe_lines.hip"
+#include "extend_kernels.hip"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "moni_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return MONI_ENODEV; } } while (0)
 
@@ -186,6 +187,13 @@ struct moni_ctx {
     HBuf<unsigned long long> h_sum;                   // per sub-batch: bytes of the block, records that need the host, aligned reads
     DBuf<uint8_t> gather_tmp[AK_NSET];                      // rocPRIM scan workspace of the gather, one per stream it runs on (the two streams' scans overlap)
     float ak_kernel_ms = 0;
+    struct ExBufs {         // extend mode (extend_api.inc): per chunk of reads, the plans, the device-resident DP task list and its results, the lines' staging
+        DBuf<uint8_t> seq2, rnames, quals, lines, block, dirs; DBuf<uint64_t> rname_off, dir_off, cig_off, len, off, pos; DBuf<ext_plan_t> plans; DBuf<moni_dp_task_t> tasks;
+        DBuf<moni_dp_result_t> res; DBuf<uint32_t> cig; DBuf<int32_t> minscore; DBuf<unsigned long long> cur; HBuf<unsigned long long> hcur;
+        moni_tables_t* tables = nullptr;          // the index tables with extend's strand-1 complement (ext_complement)
+        void release() { seq2.release(); rnames.release(); quals.release(); lines.release(); block.release(); dirs.release(); rname_off.release(); dir_off.release(); cig_off.release(); len.release(); off.release();
+                         pos.release(); plans.release(); tasks.release(); res.release(); cig.release(); minscore.release(); cur.release(); hcur.release(); if (tables) (void)hipFree(tables); tables = nullptr; }
+    } ex;
     int n_cu_cached = 0, pe_occ_cached = 0;          // hipGetDeviceProperties / the occupancy query take a millisecond each: asked once per context
 };
 
@@ -291,7 +299,7 @@ __attribute__((constructor)) static void moni_hip_default_queues() { setenv("GPU
 
 extern "C" {
 
-const char* moni_version(void) { return "moni_hip 0.1 (gfx950)"; }
+const char* moni_version(void) { return "moni_hip 0.2 (gfx950)"; }
 
 int moni_index_create(const moni_flat_index_t* f, int device, moni_index_t** out) {
     if (!f || !out || !f->F || !f->heads || !f->starts || !f->ssa || !f->esa || !f->thr || !f->seq_starts)
@@ -503,6 +511,7 @@ void moni_ctx_destroy(moni_ctx_t* c) {
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (auto e : c->ak_begin) (void)hipEventDestroy(e);
     for (auto e : c->ak_done) (void)hipEventDestroy(e);
+    c->ex.release();
     c->ak_recs.release(); c->ak_cig.release(); c->ak_alt.release(); c->ak_minscore.release(); c->pe.release();
     if (c->d_ak_cursors) (void)hipFree(c->d_ak_cursors);
     if (c->out_buf) (void)hipHostFree(c->out_buf);
@@ -572,20 +581,22 @@ int moni_reads_swap(moni_ctx_t* c, uint32_t slot) {
     return MONI_OK;
 }
 
-static int ms_launch(moni_ctx* c) {
+// tabs: the byte tables pack_kernel derives strand 1 with (default: the index's own, kpbseq.h:120-137; extend mode brings its complement)
+static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr) {
     moni_index* I = c->idx;
+    if (!tabs) tabs = I->d_tables;
     const uint64_t n_tasks = 2 * c->n_reads;
     int rc;
     if (c->h_blk.empty()) return MONI_EINVAL;
     if ((rc = c->ptr.ensure(c->h_blk.back().x + 1)) || (rc = c->pat.ensure(c->h_blk.back().y + 1)) || (rc = c->pflag.ensure(n_tasks + 8))) return rc;
     const unsigned grid = (unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK);
     if (n_tasks)
-        hipLaunchKernelGGL(pack_kernel, dim3(grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, c->seq.p, c->offs.p, c->blk.p, n_tasks, c->pat.p, c->pflag.p);
+        hipLaunchKernelGGL(pack_kernel, dim3(grid), dim3(MS_BLOCK), 0, c->stream, I->K, tabs, c->seq.p, c->offs.p, c->blk.p, n_tasks, c->pat.p, c->pflag.p);
     rec(c, EV_MS0);
     if (n_tasks) {
 #define MS_LAUNCH(NCH, MINW) do { const uint64_t nl = (n_tasks + (NCH) - 1) / (NCH); \
         hipLaunchKernelGGL((ms_lf_kernel<NCH, MINW>), dim3((unsigned)((nl + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, \
-                           I->K, I->d_tables, I->d_rows, I->d_frows, I->d_cr, I->d_recs, c->pat.p, c->offs.p, c->blk.p, n_tasks, c->ptr.p, c->d_counters); } while (0)
+                           I->K, tabs, I->d_rows, I->d_frows, I->d_cr, I->d_recs, c->pat.p, c->offs.p, c->blk.p, n_tasks, c->ptr.p, c->d_counters); } while (0)
         switch (c->ms_variant) {
             case 1: MS_LAUNCH(1, 8); break;
             case 2: MS_LAUNCH(2, 8); break;
@@ -1859,5 +1870,6 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 }
 
 #include "pe_api.inc"
+#include "extend_api.inc"
 
 }  // extern "C"

@@ -18,6 +18,8 @@
 // modes take the older path: a reader thread parses ahead into a bounded queue, two workers per GPU, a writer thread with a bounded
 // in-order window.  -m writes the report-MEMs records (aligner_ksw2.hpp:346-373);
 // --ms / --mems write the legacy `moni ms` / `moni mems` text outputs (src/matching_statistics.cpp:520-610, src/mems.cpp:520-600).
+// --extend writes the SAM file of the legacy `moni extend` (extender_ksw2.hpp, extend_reads_dispatcher.hpp:435-486; moni_extend_batch) - single-end
+// reads, the same path as -m; its @HD line has the tabs of moni_sam_header where the reference's extender writes blanks.
 // -n loads <prefix>.thrbv.full.ms (no LCP samples); -q is accepted (the text comes from the BWT, not from either grammar).
 // -c writes <sam>.csv (per-read MEM statistics, csv.hpp:55-67; through the host pipeline - for pairs one line per pair, moni_pe_align_csv_batch).  -Z (secondary chains,
 // chain.hpp:442-727) acts on paired input and is ignored for single-end input, as in the reference (aligner_ksw2.hpp:1190-1191 is the only call site).
@@ -179,6 +181,7 @@ struct Args {
     moni_align_params_t P;
     bool report_mems = false, csv = false, no_lcp = false, shaped_slp = false, secondary = false;
     bool legacy_ms = false, legacy_mems = false;      // --ms / --mems
+    bool extend = false;                              // --extend: the legacy `moni extend` (longest MEM of each strand, extended to both sides)
     int gpus = 1;
     size_t gpu_batch = 1048576;
     int ctx_per_gpu = 3;               // streaming path: contexts (ranges in flight) per GPU
@@ -201,11 +204,12 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--ctx-per-gpu") && i + 1 < argc) { a.ctx_per_gpu = std::max(1, atoi(argv[++i])); continue; }
         if (!strcmp(argv[i], "--ms")) { a.legacy_ms = true; continue; }
         if (!strcmp(argv[i], "--mems")) { a.legacy_mems = true; continue; }
+        if (!strcmp(argv[i], "--extend")) { a.extend = true; continue; }
         av.push_back(argv[i]);
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads]\n";
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems | --extend]\n";
     int c;
     char* s;
     optind = 1;
@@ -717,6 +721,13 @@ int main(int argc, char** argv) {
     const bool paired = !a.mate1.empty() || !a.mate2.empty();
     if (paired && (a.mate1.empty() || a.mate2.empty())) die("paired-end alignment needs both -1 and -2");
     if (paired && (a.legacy_ms || a.legacy_mems)) die("--ms / --mems take single-end input (-p)");
+    if (a.extend) {          // extend mode: single-end reads, one mode at a time
+        if (paired) die("--extend takes single-end input (-p), not -1 / -2");
+        if (a.report_mems) die("--extend cannot be combined with -m");
+        if (a.csv) die("--extend cannot be combined with -c");
+        if (a.legacy_ms) die("--extend cannot be combined with --ms");
+        if (a.legacy_mems) die("--extend cannot be combined with --mems");
+    }
     if (!paired && a.patterns.empty()) die("no reads given (-p)");
     std::string fn = a.filename;
     std::vector<char> tmp(fn.begin(), fn.end()); tmp.push_back(0);
@@ -735,13 +746,13 @@ int main(int argc, char** argv) {
         Batch b; size_t n = 0, bases = 0;
         while (next_record(b)) { ++n; }
         bases = b.seq.size();
-        printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s\n", n, bases, a.P.min_len,
+        printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "");
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : "");
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
-    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
+    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
     const int per_gpu = legacy ? 1 : (fast ? a.ctx_per_gpu : 2);                      // contexts (batches in flight) per GPU
     std::vector<moni_index_t*> idx(a.gpus, nullptr);
     std::vector<moni_ctx_t*> ctx((size_t)a.gpus * per_gpu, nullptr);
@@ -953,6 +964,13 @@ int main(int argc, char** argv) {
                     sa.push_back('\n');
                 }
                 d.a = (char*)malloc(sa.size() + 1); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size(); d.b = std::move(sb);
+            } else if (a.extend) {          // extender::config_t from the flags it shares with the aligner (-l -L -A -B -O -E)
+                moni_extend_params_t xp; moni_extend_params_default(&xp);
+                xp.min_len = a.P.min_len; xp.ext_len = a.P.ext_len; xp.smatch = a.P.smatch; xp.smismatch = a.P.smismatch; xp.gapo = a.P.gapo; xp.gape = a.P.gape;
+                moni_extend_stats_t st;
+                const int xr = moni_extend_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &xp, &d.a, &d.la, &st);
+                if (xr) die("moni_extend_batch failed (" + std::to_string(xr) + ")");
+                n_al = st.extended;
             } else if (a.report_mems) {
                 if (moni_report_mems_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &d.a, &d.la)) die("moni_report_mems_batch failed");
                 n_al = b.n();
@@ -987,7 +1005,7 @@ int main(int argc, char** argv) {
     close_out(out2);
     delete zrd;
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    info("Number of aligned reads: " + std::to_string(aligned) + "/" + std::to_string(processed));
+    info(std::string(a.extend ? "Number of extended reads: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
     info("Elapsed time (s): " + std::to_string(el));
     info("Reads per second: " + std::to_string(processed / (el > 0 ? el : 1)));
     info("Stage busy seconds: reader (parse) " + std::to_string(t_reader) + ", library calls summed over " + std::to_string(ctx.size()) + " workers " + std::to_string(t_align) +
