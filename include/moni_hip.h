@@ -326,6 +326,26 @@ int moni_extend_run(moni_ctx_t *ctx, const uint8_t *names, const uint64_t *name_
  * is listed, with or without lifts. */
 int moni_sam_header(const moni_index_t *idx, char **sam, uint64_t *sam_len);
 
+/* ---- pseudo-matching lengths: the legacy `moni pseudo-ms` (include/ms/spumoni.hpp:356-410; src/spumoni/run_spumoni.cpp:186-193) ---- */
+/* SPUMONI's pseudo-matching lengths (PML) of every read, forward strand, bytes as they are: the walk of ms_t::query over the run-length BWT
+ * and the thresholds, with one counter per read in place of the suffix-array sample - length + 1 on a BWT match, 0 on a threshold jump or on
+ * a byte whose letter the BWT does not hold.  lengths[offsets[i] - offsets[0] + k] is the PML of read i at read offset k; read_max[i] the
+ * read's largest PML (0 for an empty read); read_hits[i] the number of its offsets with PML >= thr.  Any of the three may be NULL, not all.
+ * An empty batch gives MONI_OK and writes nothing. */
+int moni_pml_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, uint32_t thr,
+                   uint32_t *lengths, uint32_t *read_max, uint32_t *read_hits);
+/* The same over the batch that moni_reads_upload made resident, device only: the results stay in HBM.  moni_last_kernel_ms(ctx, 0, ..) then
+ * gives pml_kernel's time, (ctx, 6, ..) the whole run's (pack_kernel included); moni_last_counters the steps and the threshold jumps. */
+int moni_pml_run(moni_ctx_t *ctx, uint32_t thr);
+/* The results of the last moni_pml_run on this context (any pointer may be NULL); MONI_EINVAL before any run, and after another batch was
+ * made resident (moni_reads_upload, moni_reads_swap, any *_batch call).  The call takes no capacities: it writes as many values as the batch
+ * that was resident at moni_pml_run has - moni_pml_sizes gives the two figures - so `lengths` must hold *total_len and the other two
+ * *n_reads values. */
+int moni_pml_fetch(moni_ctx_t *ctx, uint32_t *lengths, uint32_t *read_max, uint32_t *read_hits);
+/* What moni_pml_fetch would write: the reads and the bases of the batch of the last moni_pml_run (either pointer may be NULL);
+ * MONI_EINVAL where moni_pml_fetch gives it. */
+int moni_pml_sizes(moni_ctx_t *ctx, uint64_t *n_reads, uint64_t *total_len);
+
 /* ---- the reference's on-disk liftidx (<prefix>.ldx: include/aligner/liftidx.hpp:117-143 over include/common/seqidx.hpp:197-238) ---- */
 /* Both layouts load: the current one (u64 w after u) and the older one the reference's fixture data/Chr21.10.ldx has. */
 int moni_ldx_info(const char *path, uint64_t *n_seq, uint64_t *u, uint64_t *w, int *has_w);

@@ -29,6 +29,7 @@ EXPORTS = [
     "moni_ms_file_info", "moni_ms_file_read", "moni_ms_file_write", "moni_index_load_reference", "moni_ms_lengths_batch", "moni_report_mems_batch",
     "moni_pe_params_default", "moni_pe_learn_batch", "moni_pe_align_batch", "moni_pe_align_stream", "moni_pe_align_run", "moni_pe_align_csv_batch", "moni_pe_report_mems_batch",
     "moni_extend_params_default", "moni_extend_batch", "moni_extend_run",
+    "moni_pml_batch", "moni_pml_run", "moni_pml_fetch", "moni_pml_sizes",
 ]
 
 
@@ -177,6 +178,10 @@ def lib():
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(ExtendStatsC)]
         L.moni_extend_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ExtendParamsC),
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(ExtendStatsC)]
+        L.moni_pml_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.moni_pml_run.argtypes = [C.c_void_p, C.c_uint32]
+        L.moni_pml_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.moni_pml_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.moni_sam_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_last_kernel_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
         L.moni_last_counters.argtypes = [C.c_void_p, C.c_void_p]
@@ -544,6 +549,33 @@ class Ctx:
                                      C.byref(prm), C.byref(out), C.byref(ln), C.byref(st)), "moni_extend_run")
         sam = (C.string_at(out, ln.value) if ln.value else b"") if want_text else int(ln.value)      # the buffer belongs to the context
         return sam, {f: getattr(st, f) for f, _ in ExtendStatsC._fields_}
+
+    def pml_batch(self, seq: np.ndarray, offsets: np.ndarray, thr: int = 25):
+        """legacy `moni pseudo-ms` (moni_pml_batch): (lengths, read_max, read_hits) - the pseudo-matching length at every read offset (forward
+        strand), the largest of each read, and the number of offsets of each read with a length >= thr"""
+        b, keep = self._batch(seq, offsets)
+        n = len(offsets) - 1
+        ln = np.zeros(int(keep[1][-1] - keep[1][0]), dtype=np.uint32)
+        mx = np.zeros(n, dtype=np.uint32)
+        hits = np.zeros(n, dtype=np.uint32)
+        _chk(self._L.moni_pml_batch(self._h, C.byref(b), thr, ln.ctypes.data, mx.ctypes.data, hits.ctypes.data), "moni_pml_batch")
+        self.n_reads = n
+        return ln, mx, hits
+
+    def pml_run(self, thr: int = 25):
+        """moni_pml_run over the batch made resident by upload(): device only, the results wait for pml_fetch()"""
+        _chk(self._L.moni_pml_run(self._h, thr), "moni_pml_run")
+
+    def pml_fetch(self, want_lengths: bool = True):
+        """(lengths or None, read_max, read_hits) of the last pml_run(); the arrays are sized by what the library says that run covered
+        (moni_pml_sizes), whichever calls made its batch resident"""
+        nr, total = C.c_uint64(), C.c_uint64()
+        _chk(self._L.moni_pml_sizes(self._h, C.byref(nr), C.byref(total)), "moni_pml_sizes")
+        ln = np.zeros(total.value, dtype=np.uint32) if want_lengths else None
+        mx = np.zeros(nr.value, dtype=np.uint32)
+        hits = np.zeros(nr.value, dtype=np.uint32)
+        _chk(self._L.moni_pml_fetch(self._h, ln.ctypes.data if want_lengths else None, mx.ctypes.data, hits.ctypes.data), "moni_pml_fetch")
+        return ln, mx, hits
 
     def ms_lengths_batch(self, seq: np.ndarray, offsets: np.ndarray):
         """legacy `moni ms`: (pointers, lengths) of the forward strand of every read"""

@@ -20,6 +20,8 @@
 // --ms / --mems write the legacy `moni ms` / `moni mems` text outputs (src/matching_statistics.cpp:520-610, src/mems.cpp:520-600).
 // --extend writes the SAM file of the legacy `moni extend` (extender_ksw2.hpp, extend_reads_dispatcher.hpp:435-486; moni_extend_batch) - single-end
 // reads, the same path as -m; its @HD line has the tabs of moni_sam_header where the reference's extender writes blanks.
+// --pseudo-ms writes <out>.pseudo_lengths, the text of the legacy `moni pseudo-ms` (src/spumoni/run_spumoni.cpp:466-501; moni_pml_batch): per read a
+// line ">" + the read's running number in the input, then its pseudo-matching lengths, each followed by a blank.  Single-end reads, the same path as -m.
 // -n loads <prefix>.thrbv.full.ms (no LCP samples); -q is accepted (the text comes from the BWT, not from either grammar).
 // -c writes <sam>.csv (per-read MEM statistics, csv.hpp:55-67; through the host pipeline - for pairs one line per pair, moni_pe_align_csv_batch).  -Z (secondary chains,
 // chain.hpp:442-727) acts on paired input and is ignored for single-end input, as in the reference (aligner_ksw2.hpp:1190-1191 is the only call site).
@@ -182,6 +184,7 @@ struct Args {
     bool report_mems = false, csv = false, no_lcp = false, shaped_slp = false, secondary = false;
     bool legacy_ms = false, legacy_mems = false;      // --ms / --mems
     bool extend = false;                              // --extend: the legacy `moni extend` (longest MEM of each strand, extended to both sides)
+    bool pseudo_ms = false;                           // --pseudo-ms: the legacy `moni pseudo-ms` (pseudo-matching lengths of every read)
     int gpus = 1;
     size_t gpu_batch = 1048576;
     int ctx_per_gpu = 3;               // streaming path: contexts (ranges in flight) per GPU
@@ -205,11 +208,12 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--ms")) { a.legacy_ms = true; continue; }
         if (!strcmp(argv[i], "--mems")) { a.legacy_mems = true; continue; }
         if (!strcmp(argv[i], "--extend")) { a.extend = true; continue; }
+        if (!strcmp(argv[i], "--pseudo-ms")) { a.pseudo_ms = true; continue; }
         av.push_back(argv[i]);
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems | --extend]\n";
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems | --extend | --pseudo-ms]\n";
     int c;
     char* s;
     optind = 1;
@@ -721,6 +725,14 @@ int main(int argc, char** argv) {
     const bool paired = !a.mate1.empty() || !a.mate2.empty();
     if (paired && (a.mate1.empty() || a.mate2.empty())) die("paired-end alignment needs both -1 and -2");
     if (paired && (a.legacy_ms || a.legacy_mems)) die("--ms / --mems take single-end input (-p)");
+    if (a.pseudo_ms) {       // pseudo-matching lengths: single-end reads, one mode at a time
+        if (paired) die("--pseudo-ms takes single-end input (-p), not -1 / -2");
+        if (a.report_mems) die("--pseudo-ms cannot be combined with -m");
+        if (a.csv) die("--pseudo-ms cannot be combined with -c");
+        if (a.legacy_ms) die("--pseudo-ms cannot be combined with --ms");
+        if (a.legacy_mems) die("--pseudo-ms cannot be combined with --mems");
+        if (a.extend) die("--pseudo-ms cannot be combined with --extend");
+    }
     if (a.extend) {          // extend mode: single-end reads, one mode at a time
         if (paired) die("--extend takes single-end input (-p), not -1 / -2");
         if (a.report_mems) die("--extend cannot be combined with -m");
@@ -736,7 +748,7 @@ int main(int argc, char** argv) {
     if (!a.output.empty()) sam_filename = a.output;
     if (paired) return run_paired(a, sam_filename);
     const bool legacy = a.legacy_ms || a.legacy_mems;
-    if (legacy && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp: <patterns>_<index> + .mems / .pointers / .lengths
+    if ((legacy || a.pseudo_ms) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths
     info("Output file: " + sam_filename);
     MappedReader mrd;
     const bool mapped = mrd.open(a.patterns);
@@ -748,11 +760,11 @@ int main(int argc, char** argv) {
         bases = b.seq.size();
         printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : "");
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : ""));
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
-    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
+    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && !a.pseudo_ms && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
     const int per_gpu = legacy ? 1 : (fast ? a.ctx_per_gpu : 2);                      // contexts (batches in flight) per GPU
     std::vector<moni_index_t*> idx(a.gpus, nullptr);
     std::vector<moni_ctx_t*> ctx((size_t)a.gpus * per_gpu, nullptr);
@@ -861,6 +873,7 @@ int main(int argc, char** argv) {
     FILE* out = nullptr; FILE* out2 = nullptr;
     if (a.legacy_ms) { out = fopen((sam_filename + ".pointers").c_str(), "w"); out2 = fopen((sam_filename + ".lengths").c_str(), "w"); if (!out || !out2) die("open() file " + sam_filename + ".pointers/.lengths failed"); }
     else if (a.legacy_mems) { out = fopen((sam_filename + ".mems").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".mems failed"); }
+    else if (a.pseudo_ms) { out = fopen((sam_filename + ".pseudo_lengths").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".pseudo_lengths failed"); }
     else {
         out = fopen(sam_filename.c_str(), "w");
         if (!out) die("open() file " + sam_filename + " failed");
@@ -874,7 +887,7 @@ int main(int argc, char** argv) {
     }
     auto t0 = std::chrono::steady_clock::now();
     // ---- reader thread -> bounded queue of parsed batches -> workers -> bounded in-order window -> writer thread ----
-    struct Item { size_t id; Batch* b; };
+    struct Item { size_t id; Batch* b; size_t first; };      // first: the running number of the batch's first read in the input
     struct Done { char* a = nullptr; uint64_t la = 0; std::string b; };      // a: malloc'ed block of the library; b: a second stream (.lengths)
     std::mutex mu_q, mu_out;
     std::condition_variable cv_q_put, cv_q_get, cv_out, cv_window;
@@ -887,7 +900,7 @@ int main(int argc, char** argv) {
     bool workers_done = false;
     std::map<size_t, Done> done;
     std::thread reader([&]() {
-        size_t id = 0;
+        size_t id = 0, n_read = 0;
         while (true) {
             const double r0 = now();
             Batch* b = new Batch();
@@ -904,7 +917,9 @@ int main(int argc, char** argv) {
             if (b->n() == 0) { delete b; break; }
             std::unique_lock<std::mutex> lk(mu_q);
             cv_q_put.wait(lk, [&] { return queue.size() < q_cap; });
-            queue.push_back(Item{id++, b});
+            const size_t first = n_read;
+            n_read += b->n();
+            queue.push_back(Item{id++, b, first});
             cv_q_get.notify_one();
         }
         std::lock_guard<std::mutex> lk(mu_q);
@@ -964,6 +979,21 @@ int main(int argc, char** argv) {
                     sa.push_back('\n');
                 }
                 d.a = (char*)malloc(sa.size() + 1); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size(); d.b = std::move(sb);
+            } else if (a.pseudo_ms) {       // run_spumoni.cpp:495-498: ">" + the read's running number, then the lengths, each followed by a blank
+                std::vector<uint32_t> len(b.seq.size() + 1), hits(b.n() + 1);
+                const int pr = moni_pml_batch(C, &rb, a.P.min_len, len.data(), nullptr, hits.data());
+                if (pr) die("moni_pml_batch failed (" + std::to_string(pr) + ")");
+                std::string sa;
+                sa.reserve(b.seq.size() * 3 + b.n() * 12);
+                char num[24];
+                for (size_t r = 0; r < b.n(); ++r) {
+                    sa.push_back('>'); sa += std::to_string(it.first + r); sa.push_back('\n');
+                    const size_t o = b.off[r], m = b.off[r + 1] - o;
+                    for (size_t k = 0; k < m; ++k) { const int nc = snprintf(num, sizeof num, "%u ", len[o + k]); sa.append(num, (size_t)nc); }
+                    sa.push_back('\n');
+                    if (hits[r]) ++n_al;          // reads with a length >= -l somewhere
+                }
+                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
             } else if (a.extend) {          // extender::config_t from the flags it shares with the aligner (-l -L -A -B -O -E)
                 moni_extend_params_t xp; moni_extend_params_default(&xp);
                 xp.min_len = a.P.min_len; xp.ext_len = a.P.ext_len; xp.smatch = a.P.smatch; xp.smismatch = a.P.smismatch; xp.gapo = a.P.gapo; xp.gape = a.P.gape;
@@ -1005,7 +1035,7 @@ int main(int argc, char** argv) {
     close_out(out2);
     delete zrd;
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    info(std::string(a.extend ? "Number of extended reads: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
+    info(std::string(a.extend ? "Number of extended reads: " : a.pseudo_ms ? "Number of reads with a pseudo-matching length >= -l: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
     info("Elapsed time (s): " + std::to_string(el));
     info("Reads per second: " + std::to_string(processed / (el > 0 ? el : 1)));
     info("Stage busy seconds: reader (parse) " + std::to_string(t_reader) + ", library calls summed over " + std::to_string(ctx.size()) + " workers " + std::to_string(t_align) +
