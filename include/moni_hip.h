@@ -378,6 +378,11 @@ int moni_last_kernel_ms(moni_ctx_t *ctx, int which, float *ms);
 /* Work counters of the last moni_seed_run: out[0] LF steps, [1] threshold jumps, [2] phi steps,
  * [3] text bytes compared (the S, J, P, C of SURVEY.md §8(d)). */
 int moni_last_counters(moni_ctx_t *ctx, uint64_t out[4]);
+/* The occurrence stage of the last moni_seed_run: out[0] seeds whose list is longer than the in-place cap (16) and lies in the overflow
+ * region, [1] overflow entries they take, [2] entries the region holds, [3] count passes run (more than one: the counter pool or the
+ * overflow region was grown and the pass repeated), [4] launches of the long-seed kernel (0: skipped, there was no long seed),
+ * [5] compactions done for moni_seed_fetch since that run (the align paths do none). */
+int moni_seed_occ_stats(moni_ctx_t *ctx, uint64_t out[6]);
 const char *moni_version(void);
 
 #ifdef __cplusplus

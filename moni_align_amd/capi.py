@@ -23,7 +23,7 @@ EXPORTS = [
     "moni_version", "moni_index_create", "moni_index_load", "moni_index_destroy", "moni_index_n", "moni_index_r",
     "moni_index_device_bytes", "moni_index_text", "moni_ctx_create", "moni_ctx_destroy", "moni_reads_upload", "moni_reads_swap", "moni_ms_run",
     "moni_ms_query_batch", "moni_seed_run", "moni_seed_counts", "moni_seed_fetch", "moni_seed_batch", "moni_free",
-    "moni_phi_lcp_batch", "moni_extz_batch", "moni_last_kernel_ms", "moni_last_counters",
+    "moni_phi_lcp_batch", "moni_extz_batch", "moni_last_kernel_ms", "moni_last_counters", "moni_seed_occ_stats",
     "moni_align_params_default", "moni_align_batch", "moni_align_csv_batch", "moni_align_run", "moni_align_stream", "moni_sam_header",
     "moni_ldx_info", "moni_ldx_rewrite", "moni_ldx_lift_batch", "moni_ldx_write",
     "moni_ms_file_info", "moni_ms_file_read", "moni_ms_file_write", "moni_index_load_reference", "moni_ms_lengths_batch", "moni_report_mems_batch",
@@ -185,6 +185,7 @@ def lib():
         L.moni_sam_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_last_kernel_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
         L.moni_last_counters.argtypes = [C.c_void_p, C.c_void_p]
+        L.moni_seed_occ_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.moni_ms_lengths_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.c_void_p, C.c_void_p]
         L.moni_report_mems_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AlignParamsC),
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -624,6 +625,12 @@ class Ctx:
         out = np.zeros(4, dtype=np.uint64)
         _chk(self._L.moni_last_counters(self._h, out.ctypes.data), "moni_last_counters")
         return out
+
+    def seed_occ_stats(self) -> Dict[str, int]:
+        """the occurrence stage of the last seed_run (moni_seed_occ_stats)"""
+        out = np.zeros(6, dtype=np.uint64)
+        _chk(self._L.moni_seed_occ_stats(self._h, out.ctypes.data), "moni_seed_occ_stats")
+        return dict(zip(("long_seeds", "overflow_used", "overflow_cap", "count_passes", "long_launches", "compactions"), (int(v) for v in out)))
 
 
 def ldx_info(path: str):

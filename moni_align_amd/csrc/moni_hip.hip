@@ -124,10 +124,16 @@ struct moni_ctx {
     DBuf<uint64_t> tot, read_mem_off;
     DBuf<moni_mem_t> mems;
     DBuf<uint32_t> aux;
-    DBuf<uint64_t> lowers, tmp, occ_cnt, occ_off, occs;
+    DBuf<uint64_t> lowers, tmp;              // tmp: the occurrence array the align paths read - tmp_cap entries per MEM slot, then ovf_cap overflow entries for the longer lists
+    DBuf<uint64_t> long_list;                // slots of the seeds with a list in the overflow region
+    DBuf<uint64_t> occ_cnt, occ_off, occs;   // compaction on demand (seed_compact): the lists as one array in slot order, for the callers that fetch them
+    DBuf<moni_mem_t> mems_compact;           // ... and the MEM records with occ_off into it
+    bool occs_valid = false;
+    uint64_t ovf_cap = 4096;                 // grown to a pass's demand, like pool_rows
+    uint64_t occ_stats[6] = {0, 0, 0, 0, 0, 0};      // moni_seed_occ_stats
     DBuf<uint32_t> pool;
     DBuf<uint8_t> scan_tmp;
-    uint32_t* d_small = nullptr;            // [0] pool_next, [1] error_flag
+    occ_small_t* d_small = nullptr;         // seed_core.h
     unsigned long long* d_counters = nullptr;   // 4
     uint64_t n_mems = 0, n_occs = 0;
     uint32_t dirs_scale = 1;                                   // direction-bit budget multiplier (doubles after a batch that overflowed it)
@@ -487,8 +493,8 @@ int moni_ctx_create(moni_index_t* I, moni_ctx_t** out) {
     for (int i = 0; i < EV_N; ++i) { c->ev[i] = nullptr; c->ev_valid[i] = false; }
     bool ok = hipStreamCreate(&c->stream) == hipSuccess;
     for (int i = 0; ok && i < EV_N; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
-    ok = ok && hipMalloc((void**)&c->d_small, 16) == hipSuccess && hipMalloc((void**)&c->d_counters, 4 * sizeof(unsigned long long)) == hipSuccess &&
-         hipMemset(c->d_small, 0, 16) == hipSuccess && hipMemset(c->d_counters, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
+    ok = ok && hipMalloc((void**)&c->d_small, sizeof(occ_small_t)) == hipSuccess && hipMalloc((void**)&c->d_counters, 4 * sizeof(unsigned long long)) == hipSuccess &&
+         hipMemset(c->d_small, 0, sizeof(occ_small_t)) == hipSuccess && hipMemset(c->d_counters, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) { fprintf(stderr, "moni_hip: context creation failed on device %d\n", I->device); moni_ctx_destroy(c); return MONI_ENODEV; }
     *out = c;
     return MONI_OK;
@@ -501,7 +507,7 @@ void moni_ctx_destroy(moni_ctx_t* c) {
     for (auto& x : c->stash) { x.seq.release(); x.offs.release(); x.blk.release(); }
     c->blk.release(); c->seq.release(); c->offs.release(); c->ptr.release(); c->pat.release(); c->pflag.release(); c->cnt_m.release(); c->cnt_s.release(); c->mem_slots.release(); c->tot.release();
     c->read_mem_off.release(); c->mems.release(); c->aux.release(); c->lowers.release(); c->tmp.release();
-    c->occ_cnt.release(); c->occ_off.release(); c->occs.release(); c->pool.release(); c->scan_tmp.release();
+    c->occ_cnt.release(); c->occ_off.release(); c->occs.release(); c->mems_compact.release(); c->long_list.release(); c->pool.release(); c->scan_tmp.release();
     for (int x = 0; x < AK_NSET; ++x) c->af[x].release();
     for (int x = 0; x < PE_NSET; ++x) c->af_pe[x].release();
     for (int x = 0; x < PE_NSTREAM; ++x) if (c->pe_stream[x]) (void)hipStreamDestroy(c->pe_stream[x]);
@@ -570,7 +576,7 @@ static int reads_upload(moni_ctx* c, const moni_read_batch_t* b, bool keep_host_
     c->h_blk.swap(blk);
     if (keep_host_copy) { c->h_seq.assign(b->seq + b->offsets[0], b->seq + b->offsets[0] + total); c->h_offs = rel; }
     else { c->h_seq.clear(); c->h_offs.clear(); }
-    c->n_mems = c->n_occs = 0; c->pml.valid = false;
+    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false;
     return MONI_OK;
 }
 
@@ -582,7 +588,7 @@ int moni_reads_swap(moni_ctx_t* c, uint32_t slot) {
     moni_ctx::Stash& x = c->stash[slot];
     std::swap(c->seq, x.seq); std::swap(c->offs, x.offs); std::swap(c->blk, x.blk); c->h_blk.swap(x.h_blk); std::swap(c->n_reads, x.n_reads); std::swap(c->total_len, x.total_len); std::swap(c->max_len, x.max_len);
     c->h_seq.swap(x.h_seq); c->h_offs.swap(x.h_offs);
-    c->n_mems = c->n_occs = 0; c->pml.valid = false;
+    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false;
     return MONI_OK;
 }
 
@@ -680,7 +686,8 @@ int moni_ms_lengths_batch(moni_ctx_t* c, const moni_read_batch_t* b, uint64_t* p
     return MONI_OK;
 }
 
-// The seeding stage over the resident batch: MS pointers, MEMs (count, scan, emit), occurrences (count, scan, fill).
+// The seeding stage over the resident batch: MS pointers, MEMs (count, scan, emit), occurrences (one pass that counts them and leaves the lists where it
+// wrote them; a second, small launch only for the seeds whose list is longer than tmp_cap).
 static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
     moni_index* I = c->idx;
     const uint64_t nr = c->n_reads, n_tasks = 2 * nr;
@@ -693,7 +700,7 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
     moni_u64x2* slots = c->mem_slots.p;
     const uint64_t* offs = c->offs.p;
     HIPCHK(hipMemsetAsync(c->d_counters, 0, 4 * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_small, 0, 16, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_small, 0, sizeof(occ_small_t), c->stream));
     rec(c, EV_ALL0);
     if ((rc = ms_launch(c))) return rc;                              // (allocates pat / ptr)
     const uint64_t* pat = c->pat.p; const uint64_t* ptr = c->ptr.p;
@@ -717,14 +724,11 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
     HIPCHK(hipMemcpyAsync(&n_mems, rmo + nr, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->tmp_cap = 16;
-    {
-        const uint64_t need = n_mems + 2;
-        if ((rc = c->mems.ensure(need)) || (rc = c->aux.ensure(need)) || (rc = c->lowers.ensure(need)) || (rc = c->tmp.ensure(need * c->tmp_cap + 1)) ||
-            (rc = c->occ_cnt.ensure(need + 1)) || (rc = c->occ_off.ensure(need + 1))) return rc;
-        if ((rc = c->pool.ensure((size_t)c->pool_rows * I->K.n_seq + 1))) return rc;
-    }
+    c->occs_valid = false; c->n_mems = c->n_occs = 0;
+    const uint64_t need = n_mems + 2;
+    if ((rc = c->mems.ensure(need)) || (rc = c->aux.ensure(need)) || (rc = c->lowers.ensure(need)) || (rc = c->long_list.ensure(need))) return rc;
+    if ((rc = c->pool.ensure((size_t)c->pool_rows * I->K.n_seq + 1))) return rc;
     moni_mem_t* mems = c->mems.p; uint32_t* aux = c->aux.p;
-    uint64_t* occ_cnt = c->occ_cnt.p; uint64_t* occ_off = c->occ_off.p;
     rec(c, EV_ME0);
     if (n_tasks)
         MEM_LAUNCH(true, (const uint64_t*)rmo, mems, aux);
@@ -733,52 +737,75 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
     A.phi.recs = I->d_phi; A.phi.dir = I->d_phi_dir; A.phi_inv.recs = I->d_phi_inv; A.phi_inv.dir = I->d_phi_inv_dir;
     A.text = I->d_text;
     A.seq_starts = I->d_seq_starts; A.name_id = I->d_name_id; A.mems = mems; A.aux = aux; A.read_mem_off = rmo;
-    A.n_mems = n_mems; A.occs = nullptr; A.tmp = c->tmp.p; A.lowers = c->lowers.p; A.tmp_cap = c->tmp_cap;
+    A.n_mems = n_mems; A.occs = nullptr; A.tmp = nullptr; A.lowers = c->lowers.p; A.tmp_cap = c->tmp_cap;
     A.filter_seeds = prm->filter_seeds; A.n_seeds_thr = prm->n_seeds_thr; A.pool_rows = c->pool_rows; A.pool = c->pool.p;
-    A.pool_next = c->d_small; A.error_flag = c->d_small + 1; A.counters = c->d_counters;
+    A.pool_next = &c->d_small->pool_next; A.error_flag = &c->d_small->error_flag; A.counters = c->d_counters;
+    A.long_list = c->long_list.p; A.small = c->d_small;
     const unsigned grid_m = (unsigned)((n_mems + MS_BLOCK - 1) / MS_BLOCK);
     // The per-genome filter needs a row of per-name counters only for seeds with more than n_seeds_thr occurrences;
     // rows come from a bump-allocated pool.  If a pass asks for more rows than the pool holds, the pool is grown to the
-    // demand the pass reported and the pass is repeated (results of an exhausted pass are discarded).
-    uint64_t n_occs = 0;
-    uint32_t small[2] = {0, 0};
-    for (int attempt = 0;; ++attempt) {
-        A.pool = c->pool.p; A.pool_rows = c->pool_rows;
-        HIPCHK(hipMemsetAsync(c->d_small, 0, 16, c->stream));
+    // demand the pass reported and the pass is repeated (results of an exhausted pass are discarded).  The overflow region
+    // of the occurrence array is sized the same way: a pass that asked for more entries than it has is repeated on a larger array.
+    occ_small_t small;
+    uint64_t attempts = 0;
+    for (int pool_tries = 0, ovf_tries = 0;;) {
+        if ((rc = c->tmp.ensure(need * c->tmp_cap + c->ovf_cap + 1))) return rc;
+        A.tmp = c->tmp.p; A.pool = c->pool.p; A.pool_rows = c->pool_rows;
+        HIPCHK(hipMemsetAsync(c->d_small, 0, sizeof small, c->stream));
         HIPCHK(hipMemsetAsync(c->d_counters + 2, 0, sizeof(unsigned long long), c->stream));
         rec(c, EV_PC0);
-        if (n_mems) hipLaunchKernelGGL(occ_kernel<false>, dim3(grid_m), dim3(MS_BLOCK), 0, c->stream, I->K, A);
+        if (n_mems) hipLaunchKernelGGL(occ_kernel, dim3(grid_m), dim3(MS_BLOCK), 0, c->stream, I->K, A);
         rec(c, EV_PC1);
-        HIPCHK(hipMemcpyAsync(small, c->d_small, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&small, c->d_small, sizeof small, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (!small[1]) break;
-        if (attempt >= 2) { fprintf(stderr, "moni_hip: per-genome counter pool exhausted (%u rows)\n", c->pool_rows); return MONI_ENOMEM; }
-        c->pool_rows = small[0] + small[0] / 4 + 64;
-        if ((rc = c->pool.ensure((size_t)c->pool_rows * I->K.n_seq + 1))) return rc;
+        ++attempts;
+        if (small.error_flag) {
+            if (++pool_tries > 2) { fprintf(stderr, "moni_hip: per-genome counter pool exhausted (%u rows)\n", c->pool_rows); return MONI_ENOMEM; }
+            c->pool_rows = small.pool_next + small.pool_next / 4 + 64;
+            if ((rc = c->pool.ensure((size_t)c->pool_rows * I->K.n_seq + 1))) return rc;
+            continue;
+        }
+        if (small.ovf <= c->ovf_cap) break;
+        if (++ovf_tries > 1) { fprintf(stderr, "moni_hip: occurrence overflow region too small twice (%llu of %llu entries)\n", (unsigned long long)c->ovf_cap, small.ovf); return MONI_ENOMEM; }
+        c->ovf_cap = small.ovf + small.ovf / 4 + 64;
     }
-    hipLaunchKernelGGL(occ_cnt_gather_kernel, dim3((unsigned)((n_mems + 1 + 255) / 256)), dim3(256), 0, c->stream, mems, n_mems, occ_cnt);
-    if ((rc = exclusive_scan_u64(c, occ_cnt, occ_off, n_mems + 1))) return rc;
-    if (n_mems) hipLaunchKernelGGL(occ_off_scatter_kernel, dim3(grid_m), dim3(256), 0, c->stream, mems, n_mems, occ_off);
-    HIPCHK(hipMemcpyAsync(&n_occs, occ_off + n_mems, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if ((rc = c->occs.ensure(n_occs + 1))) return rc;
-    A.occs = c->occs.p;
-    for (int attempt = 0;; ++attempt) {
-        A.pool = c->pool.p; A.pool_rows = c->pool_rows;
-        HIPCHK(hipMemsetAsync(c->d_small, 0, 16, c->stream));
-        rec(c, EV_PE0);
-        if (n_mems) hipLaunchKernelGGL(occ_kernel<true>, dim3(grid_m), dim3(MS_BLOCK), 0, c->stream, I->K, A);
-        rec(c, EV_PE1);
-        rec(c, EV_ALL1);
-        HIPCHK(hipMemcpyAsync(small, c->d_small, 8, hipMemcpyDeviceToHost, c->stream));
+    // the long lists: the listed seeds are walked again into their overflow space (they need no more pool rows than the count pass took)
+    rec(c, EV_PE0);
+    if (small.n_long) {
+        HIPCHK(hipMemsetAsync(c->d_small, 0, 8, c->stream));
+        hipLaunchKernelGGL(occ_long_kernel, dim3((small.n_long + MS_BLOCK - 1) / MS_BLOCK), dim3(MS_BLOCK), 0, c->stream, I->K, A, small.n_long);
+    }
+    rec(c, EV_PE1);
+    rec(c, EV_ALL1);
+    if (small.n_long) {
+        uint32_t flag[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(flag, c->d_small, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (!small[1]) break;
-        if (attempt >= 2) { fprintf(stderr, "moni_hip: per-genome counter pool exhausted (%u rows)\n", c->pool_rows); return MONI_ENOMEM; }
-        c->pool_rows = small[0] + small[0] / 4 + 64;
-        if ((rc = c->pool.ensure((size_t)c->pool_rows * I->K.n_seq + 1))) return rc;
+        if (flag[1]) { fprintf(stderr, "moni_hip: per-genome counter pool exhausted (%u rows)\n", c->pool_rows); return MONI_ENOMEM; }
     }
     HIPCHK(hipGetLastError());
-    c->n_mems = n_mems; c->n_occs = n_occs;
+    c->n_mems = n_mems; c->n_occs = small.n_occs;
+    c->occ_stats[0] = small.n_long; c->occ_stats[1] = small.ovf; c->occ_stats[2] = c->ovf_cap; c->occ_stats[3] = attempts; c->occ_stats[4] = small.n_long ? 1 : 0; c->occ_stats[5] = 0;
+    return MONI_OK;
+}
+
+// The lists as one array in slot order (c->occs) and every slot's offset into it (c->occ_off): what moni_seed_fetch hands out.  Once per seeding
+// run, and only when a caller asks; the device's mems keep pointing into the array the align kernels read.
+static int seed_compact(moni_ctx* c) {
+    if (c->occs_valid) return MONI_OK;
+    const uint64_t n_mems = c->n_mems;
+    int rc;
+    if ((rc = c->occ_cnt.ensure(n_mems + 2)) || (rc = c->occ_off.ensure(n_mems + 2)) || (rc = c->occs.ensure(c->n_occs + 1)) || (rc = c->mems_compact.ensure(n_mems + 1))) return rc;
+    hipLaunchKernelGGL(occ_cnt_gather_kernel, dim3((unsigned)((n_mems + 1 + 255) / 256)), dim3(256), 0, c->stream, c->mems.p, n_mems, c->occ_cnt.p);
+    if ((rc = exclusive_scan_u64(c, c->occ_cnt.p, c->occ_off.p, n_mems + 1))) return rc;
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, c->occ_off.p + n_mems, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (total != c->n_occs) { fprintf(stderr, "moni_hip: the seeds' occurrence counts sum to %llu, the count pass reported %llu\n", (unsigned long long)total, (unsigned long long)c->n_occs); return MONI_ENODEV; }
+    if (n_mems) hipLaunchKernelGGL(occ_compact_kernel, dim3((unsigned)((n_mems + 255) / 256)), dim3(256), 0, c->stream, c->mems.p, n_mems, c->occ_off.p, c->tmp.p, c->occs.p, c->mems_compact.p);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipGetLastError());
+    c->occs_valid = true; c->occ_stats[5] += 1;
     return MONI_OK;
 }
 
@@ -798,7 +825,11 @@ int moni_seed_counts(moni_ctx_t* c, uint64_t* n_mems, uint64_t* n_occs) {
 int moni_seed_fetch(moni_ctx_t* c, moni_mem_t* mems, uint64_t* occs, uint64_t* read_mem_off) {
     if (!c) return MONI_EINVAL;
     HIPCHK(hipSetDevice(c->idx->device));
-    if (mems && c->n_mems) HIPCHK(hipMemcpy(mems, c->mems.p, c->n_mems * sizeof(moni_mem_t), hipMemcpyDeviceToHost));
+    if ((mems || occs) && c->n_mems) {
+        int rc = seed_compact(c);
+        if (rc) return rc;
+    }
+    if (mems && c->n_mems) HIPCHK(hipMemcpy(mems, c->mems_compact.p, c->n_mems * sizeof(moni_mem_t), hipMemcpyDeviceToHost));          // occ_off into the compacted array
     if (occs && c->n_occs) HIPCHK(hipMemcpy(occs, c->occs.p, c->n_occs * 8, hipMemcpyDeviceToHost));
     if (read_mem_off) HIPCHK(hipMemcpy(read_mem_off, c->read_mem_off.p, (c->n_reads + 1) * 8, hipMemcpyDeviceToHost));
     return MONI_OK;
@@ -844,6 +875,12 @@ int moni_last_kernel_ms(moni_ctx_t* c, int which, float* ms) {
     if (!c->ev_valid[a] || !c->ev_valid[b]) return MONI_EINVAL;
     HIPCHK(hipEventSynchronize(c->ev[b]));
     HIPCHK(hipEventElapsedTime(ms, c->ev[a], c->ev[b]));
+    return MONI_OK;
+}
+
+int moni_seed_occ_stats(moni_ctx_t* c, uint64_t out[6]) {
+    if (!c || !out) return MONI_EINVAL;
+    for (int i = 0; i < 6; ++i) out[i] = c->occ_stats[i];
     return MONI_OK;
 }
 
@@ -1415,7 +1452,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
             A.D.sc_mch = prm->smatch; A.D.sc_mis = -prm->smismatch; A.D.sc_N = -prm->gape; A.D.wild = 4; A.D.qo = prm->gapo; A.D.e = prm->gape;
             A.D.end_bonus = prm->end_bonus; A.D.reads = c->seq.p; A.D.text = I->d_text; A.D.n_text = I->K.n_text;
             A.D.reads_limit = (c->total_len + 8) & ~7ull; A.D.text_limit = (I->K.n_text + 8) & ~7ull;       // both buffers carry 16 bytes of padding
-            A.mems = c->mems.p; A.occs = c->occs.p; A.read_mem_off = c->read_mem_off.p; A.offs = c->offs.p;
+            A.mems = c->mems.p; A.occs = c->tmp.p; A.read_mem_off = c->read_mem_off.p; A.offs = c->offs.p;
             A.min_score_of_len = c->ak_minscore.p; A.max_len = (uint32_t)c->max_len + 1; A.read_lo = r0; A.n_reads = nr;
             A.slots = c->ak_slots.p + (k % AK_NSET) * ak_waves * AK_NL; A.waves = c->ak_waves.p + (k % AK_NSET) * ak_waves;
             // records: pinned host memory when host threads read them behind every launch; with the lines ordered on the GPU they are read only

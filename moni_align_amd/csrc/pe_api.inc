@@ -200,7 +200,7 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
     A.D.sc_mch = prm->smatch; A.D.sc_mis = -prm->smismatch; A.D.sc_N = -prm->gape; A.D.wild = 4; A.D.qo = prm->gapo; A.D.e = prm->gape;
     A.D.end_bonus = prm->end_bonus; A.D.reads = c->seq.p; A.D.text = I->d_text; A.D.n_text = I->K.n_text;
     A.D.reads_limit = (c->total_len + 8) & ~7ull; A.D.text_limit = (I->K.n_text + 8) & ~7ull;
-    A.mems = c->mems.p; A.occs = c->occs.p; A.read_mem_off = c->read_mem_off.p; A.aux = c->aux.p; A.offs = c->offs.p;
+    A.mems = c->mems.p; A.occs = c->tmp.p; A.read_mem_off = c->read_mem_off.p; A.aux = c->aux.p; A.offs = c->offs.p;
     A.min_score_of_len = c->pe.minscore.p; A.max_len = (uint32_t)c->max_len + 1;
     A.sw_wave = 1;                     // MONI_PE_SW_WAVE=0: the orphan search by the pair's own lane (the first, slower form; same results)
     if (const char* v = getenv("MONI_PE_SW_WAVE")) A.sw_wave = atoi(v) ? 1u : 0u;
@@ -367,10 +367,8 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
         if (!big.empty()) {
             if (h_mems.empty()) {          // the batch's seeds, once
                 h_mems.resize(c->n_mems + 1); h_occs.resize(c->n_occs + 1); h_rmo.resize(c->n_reads + 1); h_aux.resize(c->n_mems + 1); h_offs.resize(c->n_reads + 1);
-                if (c->n_mems) { HIPCHK(hipMemcpyAsync(h_mems.data(), c->mems.p, c->n_mems * sizeof(moni_mem_t), hipMemcpyDeviceToHost, c->copy_stream));
-                                 HIPCHK(hipMemcpyAsync(h_aux.data(), c->aux.p, c->n_mems * 4, hipMemcpyDeviceToHost, c->copy_stream)); }
-                if (c->n_occs) HIPCHK(hipMemcpyAsync(h_occs.data(), c->occs.p, c->n_occs * 8, hipMemcpyDeviceToHost, c->copy_stream));
-                HIPCHK(hipMemcpyAsync(h_rmo.data(), c->read_mem_off.p, (c->n_reads + 1) * 8, hipMemcpyDeviceToHost, c->copy_stream));
+                if ((rc = moni_seed_fetch(c, h_mems.data(), h_occs.data(), h_rmo.data()))) return rc;          // the host reads the lists as one array: compacted here, on demand
+                if (c->n_mems) HIPCHK(hipMemcpyAsync(h_aux.data(), c->aux.p, c->n_mems * 4, hipMemcpyDeviceToHost, c->copy_stream));
                 HIPCHK(hipMemcpyAsync(h_offs.data(), c->offs.p, (c->n_reads + 1) * 8, hipMemcpyDeviceToHost, c->copy_stream));
                 HIPCHK(hipStreamSynchronize(c->copy_stream));
             }

@@ -582,6 +582,14 @@ MONI_HD uint64_t lce_bounded(const uint8_t* __restrict__ text, uint64_t a, uint6
     return l < len ? l : len;
 }
 
+// the words the occurrence stage's kernels and the host share (moni_ctx::d_small): zeroed before a pass, read back behind it
+struct occ_small_t {
+    uint32_t pool_next, error_flag;             // counter rows asked for (bump allocator); a pass asked for more than the pool holds
+    uint32_t n_long, pad;                       // slots in long_list
+    unsigned long long ovf;                     // overflow entries asked for (the host compares it with the region's size)
+    unsigned long long n_occs;                  // kept occurrences of all seeds
+};
+
 struct occ_args_t {
     phi_tab_t phi, phi_inv;
     const uint8_t* text;            // K.no_lcp: the LCP of a phi step is measured here
@@ -602,7 +610,15 @@ struct occ_args_t {
     uint32_t* pool_next;            // bump allocator
     uint32_t* error_flag;
     unsigned long long* counters;
+    // occurrence lists used in place (occ_kernel; the host replay calls occ_task alone and leaves these unset): tmp is the occurrence array.  A seed
+    // that keeps at most tmp_cap occurrences has its list at slot * tmp_cap; a longer one gets occ_cnt entries of the overflow region that lies
+    // behind the n_mems * tmp_cap short-list entries, bump-allocated, and its slot number is appended to long_list for occ_long_task.
+    uint64_t* long_list = nullptr;              // n_mems entries
+    occ_small_t* small = nullptr;
 };
+
+// what the count pass kept for the (at most two) seeds a lane walked: its own slot and, for a full MEM, the left half's
+struct occ_kept_t { uint64_t slot[2]; uint32_t kept[2]; uint32_t n; };
 
 struct walk_t {
     uint64_t total, filtered, kept;
@@ -693,9 +709,11 @@ MONI_HD void run_seed(const occ_args_t& A, const moni_consts_t& K, uint64_t firs
 // from the MEM's upper/lower suffix); right halves have their own lane.
 //   FILL = false: fills total_occ / num_filtered / occ_cnt (+ left-half pos, lower suffix) and keeps the
 //                 first tmp_cap occurrences of every seed in tmp.
-//   FILL = true : writes occurrences at occ_off (from tmp when the list fits, otherwise by walking again).
+//   FILL = true : writes occurrences at occ_off (from tmp when the list fits, otherwise by walking again): the host replay's
+//                 second pass over a compact array.  The product leaves the lists in place (seed_kernels.hip: occ_kernel takes
+//                 `kept` from the count pass and places them) and walks only the long ones again (occ_long_task).
 template <bool FILL>
-MONI_HD void occ_task(const moni_consts_t& K, const occ_args_t& A, uint64_t g, unsigned long long& phi_steps) {
+MONI_HD void occ_task(const moni_consts_t& K, const occ_args_t& A, uint64_t g, unsigned long long& phi_steps, occ_kept_t* kept = nullptr) {
     const uint32_t ax = A.aux[g];
     if (ax == 0xFFFFFFFEu) return;                         // left halves ride with their parent
     const moni_mem_t M = A.mems[g];
@@ -704,6 +722,7 @@ MONI_HD void occ_task(const moni_consts_t& K, const occ_args_t& A, uint64_t g, u
     if (!FILL) {
         run_seed(A, K, M.pos, M.pos, M.pos, M.len, A.tmp + g * A.tmp_cap, A.tmp_cap, W, upper, lower);
         A.mems[g].total_occ = (uint32_t)W.total; A.mems[g].num_filtered = (uint32_t)W.filtered; A.mems[g].occ_cnt = (uint32_t)W.kept;
+        if (kept) { kept->slot[0] = g; kept->kept[0] = (uint32_t)W.kept; kept->n = 1; }
     } else if (M.occ_cnt <= A.tmp_cap) {
         for (uint32_t i = 0; i < M.occ_cnt; ++i) A.occs[M.occ_off + i] = A.tmp[g * A.tmp_cap + i];
     } else {
@@ -720,6 +739,7 @@ MONI_HD void occ_task(const moni_consts_t& K, const occ_args_t& A, uint64_t g, u
             A.mems[hb].total_occ = (uint32_t)WB.total; A.mems[hb].num_filtered = (uint32_t)WB.filtered; A.mems[hb].occ_cnt = (uint32_t)WB.kept;
             A.lowers[hb] = lower;
             W.phi_steps += WB.phi_steps;
+            if (kept) { kept->slot[1] = hb; kept->kept[1] = (uint32_t)WB.kept; kept->n = 2; }
         } else if (Bm.occ_cnt <= A.tmp_cap) {
             for (uint32_t i = 0; i < Bm.occ_cnt; ++i) A.occs[Bm.occ_off + i] = A.tmp[hb * A.tmp_cap + i];
         } else {
@@ -727,6 +747,15 @@ MONI_HD void occ_task(const moni_consts_t& K, const occ_args_t& A, uint64_t g, u
         }
     }
     phi_steps += W.phi_steps;
+}
+
+// occ_long_task: the seed of slot g keeps more than tmp_cap occurrences; it is walked again into the overflow space the count pass gave it
+// (occ_off, occ_cnt entries).  A left half walks down from its parent's lower suffix, as in the count pass.
+MONI_HD void occ_long_task(const moni_consts_t& K, const occ_args_t& A, uint64_t g) {
+    const moni_mem_t M = A.mems[g];
+    walk_t W; W.phi_steps = 0;
+    uint64_t upper, lower;
+    run_seed(A, K, M.pos, M.pos, A.aux[g] == 0xFFFFFFFEu ? A.lowers[g] : M.pos, M.len, A.tmp + M.occ_off, M.occ_cnt, W, upper, lower);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -108,24 +108,67 @@ extern "C" __global__ void phi_batch_kernel(const moni_consts_t K, phi_tab_t P, 
     if (t < n) { uint64_t a, b; phi_step(P, K, pos[t], a, b); out_pos[t] = a; out_lcp[t] = b; }
 }
 
-template <bool FILL>
+// The count pass.  The lists stay where the pass writes them: a seed that keeps at most tmp_cap occurrences points at its own
+// tmp_cap entries of tmp, a longer one at overflow space behind the short lists.  The overflow cursor and the list of long seeds are bumped once
+// per wavefront (a prefix sum over the lanes' demands), so a repeat-rich index does not put one atomic per seed on one address; the order in
+// which wavefronts arrive decides where a long list lies, and nothing reads occ_off as anything but a pointer.
 __global__ void __launch_bounds__(MS_BLOCK)
 occ_kernel(const moni_consts_t K, occ_args_t A) {
     const uint64_t g = (uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
     unsigned long long phi_steps = 0;
-    if (g < A.n_mems) occ_task<FILL>(K, A, g, phi_steps);
-    if (!FILL) wave_add(phi_steps, &A.counters[2]);
+    occ_kept_t kp; kp.n = 0;
+    if (g < A.n_mems) occ_task<false>(K, A, g, phi_steps, &kp);
+    wave_add(phi_steps, &A.counters[2]);
+    unsigned long long want = 0, kept = 0;          // overflow entries this lane's long lists need; occurrences its seeds keep
+    uint32_t n_long = 0;
+    for (uint32_t i = 0; i < kp.n; ++i) {
+        kept += kp.kept[i];
+        if (kp.kept[i] > A.tmp_cap) { want += kp.kept[i]; ++n_long; }
+        else A.mems[kp.slot[i]].occ_off = kp.slot[i] * A.tmp_cap;
+    }
+    wave_add(kept, &A.small->n_occs);
+    if (!__any(n_long != 0)) return;
+    const int lane = threadIdx.x & 63;
+    unsigned long long w_incl = want; uint32_t n_incl = n_long;
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long w = __shfl_up(w_incl, o); const uint32_t n = __shfl_up(n_incl, o);
+        if (lane >= o) { w_incl += w; n_incl += n; }
+    }
+    unsigned long long base_w = 0; uint32_t base_n = 0;
+    if (lane == 63) { base_w = atomicAdd(&A.small->ovf, w_incl); base_n = atomicAdd(&A.small->n_long, n_incl); }
+    base_w = __shfl(base_w, 63); base_n = __shfl(base_n, 63);
+    unsigned long long at = base_w + (w_incl - want); uint32_t li = base_n + (n_incl - n_long);
+    for (uint32_t i = 0; i < kp.n; ++i)
+        if (kp.kept[i] > A.tmp_cap) {
+            A.mems[kp.slot[i]].occ_off = A.n_mems * A.tmp_cap + at;
+            A.long_list[li++] = kp.slot[i];               // every slot is appended at most once: the list holds n_mems entries
+            at += kp.kept[i];
+        }
 }
 
-// gather occ_cnt into a u64 array for the scan, and scatter the scanned offsets back
+// the seeds the count pass listed as long, walked again into their overflow space; not launched when there is none
+__global__ void __launch_bounds__(MS_BLOCK)
+occ_long_kernel(const moni_consts_t K, occ_args_t A, uint32_t n_long) {
+    const uint32_t t = blockIdx.x * MS_BLOCK + threadIdx.x;
+    if (t < n_long) occ_long_task(K, A, A.long_list[t]);
+}
+
+// Compaction on demand (moni_seed_fetch and the host paths that read the lists as one array): occ_cnt gathered into a u64 array for the scan,
+// then every list copied from where it lies to its place in slot order.  The align kernels never run these.
 extern "C" __global__ void occ_cnt_gather_kernel(const moni_mem_t* __restrict__ mems, uint64_t n, uint64_t* __restrict__ cnt) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < n) cnt[g] = mems[g].occ_cnt;
     if (g == n) cnt[g] = 0;
 }
-extern "C" __global__ void occ_off_scatter_kernel(moni_mem_t* __restrict__ mems, uint64_t n, const uint64_t* __restrict__ off) {
+extern "C" __global__ void occ_compact_kernel(const moni_mem_t* __restrict__ mems, uint64_t n, const uint64_t* __restrict__ off, const uint64_t* __restrict__ src,
+                                              uint64_t* __restrict__ occs, moni_mem_t* __restrict__ mems_out) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < n) mems[g].occ_off = off[g];
+    if (g >= n) return;
+    moni_mem_t M = mems[g];
+    const uint64_t from = M.occ_off, to = off[g];
+    const uint32_t cnt = M.occ_cnt;
+    M.occ_off = to; mems_out[g] = M;          // the record as a caller sees it: occ_off into the compacted array
+    for (uint32_t i = 0; i < cnt; ++i) occs[to + i] = src[from + i];
 }
 
 
