@@ -346,6 +346,37 @@ int moni_pml_fetch(moni_ctx_t *ctx, uint32_t *lengths, uint32_t *read_max, uint3
  * MONI_EINVAL where moni_pml_fetch gives it. */
 int moni_pml_sizes(moni_ctx_t *ctx, uint64_t *n_reads, uint64_t *total_len);
 
+/* ---- exact-match count and locate: what ri::r_index::count / locate_all give the users of ms_pointers (include/ms/moni.hpp: ms_pointers derives
+ * from ri::r_index) ---- */
+/* A backward search of every pattern of the batch over the BWT the matching-statistics walk reads.  Strand 0 takes the pattern's bytes as they are
+ * (no case folding; N matches only an N of the text), strand 1 its reverse complement by the aligner's table (kpbseq.h:120-137).  A byte the BWT does
+ * not hold never matches, nor does a byte <= 1 (terminator, separator).  Task t of pattern i on strand s is i * strands + s. */
+typedef struct { uint32_t strands;   /* 1: forward only, 2: forward and reverse complement */
+                 uint32_t max_occ;   /* positions kept per (pattern, strand); 0 = count only */
+                 uint32_t reserved[2]; } moni_locate_params_t;
+/* count: occurrences in the concatenation, exact and uncapped (0: none; an empty pattern has none).  sa_lo: the first BWT position of the
+ * pattern's interval, defined where count > 0.  matched: pattern bytes consumed while the interval held a position = the length of the longest
+ * suffix of the (strand's) pattern that occurs; the pattern's length where it occurs.  n_occ = min(count, max_occ) positions lie at occ_off (defined
+ * where n_occ > 0) of pos / seq / seq_off: the text position of the occurrence's first byte (0-based, in the concatenation; no lift-over), the
+ * sequence it lies in and the 0-based offset inside it (seqidx::index, seqidx.hpp:149-154) - the suffixes of the n_occ highest ranks of the interval,
+ * in decreasing rank order (the order in which phi yields them from the toehold at the interval's upper end). */
+typedef struct { uint64_t count, sa_lo, occ_off; uint32_t n_occ, matched; } moni_locate_res_t;
+void moni_locate_params_default(moni_locate_params_t *p);            /* strands 1, max_occ 0 */
+/* Device-only run over the batch that moni_reads_upload made resident; the results stay in HBM.  MONI_EINVAL: strands outside {1, 2}, a non-zero
+ * reserved word, no resident batch.  moni_last_kernel_ms(ctx, 0, ..) then gives count_kernel's time, (ctx, 3, ..) locate_walk_kernel's (with the
+ * buffer growth in front of it), (ctx, 6, ..) the whole run's; moni_last_counters: [0] search steps, [1] fast rows fetched, [2] phi steps, [3] steps
+ * that took the general path.  Works on an index without LCP samples. */
+int  moni_locate_run(moni_ctx_t *ctx, const moni_locate_params_t *prm);
+/* What moni_locate_fetch would write: the tasks (patterns x strands) and the positions of the last moni_locate_run (either pointer may be NULL);
+ * MONI_EINVAL before any run, and after another batch was made resident (moni_reads_upload, moni_reads_swap, any *_batch call). */
+int  moni_locate_sizes(moni_ctx_t *ctx, uint64_t *n_tasks, uint64_t *n_occ);
+/* The results of the last moni_locate_run on this context: res holds *n_tasks records, pos / seq / seq_off *n_occ values each (any pointer may be NULL). */
+int  moni_locate_fetch(moni_ctx_t *ctx, moni_locate_res_t *res, uint64_t *pos, uint32_t *seq, uint64_t *seq_off);
+/* Host-buffer form: upload, run, fetch.  res: batch->n_reads * strands records (the caller's); *pos / *seq / *seq_off are malloc'ed (moni_free; NULL
+ * when there is no position), any of the three pointers may be NULL; *n_occ (may be NULL) their length.  An empty batch gives MONI_OK. */
+int  moni_locate_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const moni_locate_params_t *prm,
+                       moni_locate_res_t *res, uint64_t **pos, uint32_t **seq, uint64_t **seq_off, uint64_t *n_occ);
+
 /* ---- the reference's on-disk liftidx (<prefix>.ldx: include/aligner/liftidx.hpp:117-143 over include/common/seqidx.hpp:197-238) ---- */
 /* Both layouts load: the current one (u64 w after u) and the older one the reference's fixture data/Chr21.10.ldx has. */
 int moni_ldx_info(const char *path, uint64_t *n_seq, uint64_t *u, uint64_t *w, int *has_w);

@@ -30,6 +30,7 @@ EXPORTS = [
     "moni_pe_params_default", "moni_pe_learn_batch", "moni_pe_align_batch", "moni_pe_align_stream", "moni_pe_align_run", "moni_pe_align_csv_batch", "moni_pe_report_mems_batch",
     "moni_extend_params_default", "moni_extend_batch", "moni_extend_run",
     "moni_pml_batch", "moni_pml_run", "moni_pml_fetch", "moni_pml_sizes",
+    "moni_locate_params_default", "moni_locate_run", "moni_locate_sizes", "moni_locate_fetch", "moni_locate_batch",
 ]
 
 
@@ -92,6 +93,10 @@ class ExtendStatsC(C.Structure):
                 ("t_kernel", C.c_double)]
 
 
+class LocateParamsC(C.Structure):
+    _fields_ = [("strands", C.c_uint32), ("max_occ", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class DpParamsC(C.Structure):
     _fields_ = [("m", C.c_int8), ("mat", C.c_int8 * 25), ("q", C.c_int8), ("e", C.c_int8),
                 ("w", C.c_int32), ("zdrop", C.c_int32), ("end_bonus", C.c_int32)]
@@ -105,6 +110,8 @@ DP_TASK_DTYPE = np.dtype([("q_off", "<u8"), ("t_off", "<u8"), ("qlen", "<i4"), (
 DP_RESULT_DTYPE = np.dtype([("max", "<i4"), ("max_q", "<i4"), ("max_t", "<i4"), ("mqe", "<i4"), ("mqe_t", "<i4"),
                             ("mte", "<i4"), ("mte_q", "<i4"), ("score", "<i4"), ("reach_end", "<i4"),
                             ("zdropped", "<i4"), ("n_cigar", "<u4"), ("cigar_off", "<u4")])
+LOCATE_RES_DTYPE = np.dtype([("count", "<u8"), ("sa_lo", "<u8"), ("occ_off", "<u8"), ("n_occ", "<u4"), ("matched", "<u4")])
+assert LOCATE_RES_DTYPE.itemsize == 32
 assert MEM_DTYPE.itemsize == 48 and DP_TASK_DTYPE.itemsize == 32 and DP_RESULT_DTYPE.itemsize == 48
 
 DEFAULT_MAT = [2, -4, -4, -4, 0, -4, 2, -4, -4, 0, -4, -4, 2, -4, 0, -4, -4, -4, 2, 0, 0, 0, 0, 0, 0]
@@ -182,6 +189,13 @@ def lib():
         L.moni_pml_run.argtypes = [C.c_void_p, C.c_uint32]
         L.moni_pml_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.moni_pml_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.moni_locate_params_default.argtypes = [C.POINTER(LocateParamsC)]
+        L.moni_locate_params_default.restype = None
+        L.moni_locate_run.argtypes = [C.c_void_p, C.POINTER(LocateParamsC)]
+        L.moni_locate_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.moni_locate_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.moni_locate_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.POINTER(LocateParamsC), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_sam_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_last_kernel_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
         L.moni_last_counters.argtypes = [C.c_void_p, C.c_void_p]
@@ -577,6 +591,48 @@ class Ctx:
         hits = np.zeros(nr.value, dtype=np.uint32)
         _chk(self._L.moni_pml_fetch(self._h, ln.ctypes.data if want_lengths else None, mx.ctypes.data, hits.ctypes.data), "moni_pml_fetch")
         return ln, mx, hits
+
+    def _locate_params(self, strands: int, max_occ: int) -> "LocateParamsC":
+        p = LocateParamsC()
+        self._L.moni_locate_params_default(C.byref(p))
+        p.strands, p.max_occ = strands, max_occ
+        return p
+
+    def locate_batch(self, seq: np.ndarray, offsets: np.ndarray, strands: int = 1, max_occ: int = 0):
+        """exact-match count and locate (moni_locate_batch): (res, pos, seq, seq_off) - res[i * strands + s] (LOCATE_RES_DTYPE: count, sa_lo,
+        occ_off, n_occ, matched) of pattern i on strand s, and the text position, sequence index and offset inside the sequence of the
+        n_occ = min(count, max_occ) occurrences kept of each, at res["occ_off"]"""
+        b, keep = self._batch(seq, offsets)
+        n = len(offsets) - 1
+        p = self._locate_params(strands, max_occ)
+        res = np.zeros(n * strands, dtype=LOCATE_RES_DTYPE)
+        hp, hs, ho, no = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _chk(self._L.moni_locate_batch(self._h, C.byref(b), C.byref(p), res.ctypes.data, C.byref(hp), C.byref(hs), C.byref(ho), C.byref(no)), "moni_locate_batch")
+        self.n_reads = n
+        try:
+            k = no.value
+            take = lambda h, dt: np.frombuffer(C.string_at(h, k * np.dtype(dt).itemsize), dtype=dt).copy() if k else np.zeros(0, dtype=dt)
+            return res, take(hp, np.uint64), take(hs, np.uint32), take(ho, np.uint64)
+        finally:
+            for h in (hp, hs, ho):
+                self._L.moni_free(h)
+
+    def locate_run(self, strands: int = 1, max_occ: int = 0):
+        """moni_locate_run over the batch made resident by upload(): device only, the results wait for locate_fetch()"""
+        p = self._locate_params(strands, max_occ)
+        _chk(self._L.moni_locate_run(self._h, C.byref(p)), "moni_locate_run")
+
+    def locate_fetch(self, want_occ: bool = True):
+        """(res, pos, seq, seq_off) of the last locate_run(), sized by moni_locate_sizes; want_occ=False fetches the records alone (the three
+        arrays come back empty)"""
+        nt, no = C.c_uint64(), C.c_uint64()
+        _chk(self._L.moni_locate_sizes(self._h, C.byref(nt), C.byref(no)), "moni_locate_sizes")
+        k = no.value if want_occ else 0
+        res = np.zeros(nt.value, dtype=LOCATE_RES_DTYPE)
+        pos, sq, so = np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.uint32), np.zeros(k, dtype=np.uint64)
+        _chk(self._L.moni_locate_fetch(self._h, res.ctypes.data, pos.ctypes.data if k else None, sq.ctypes.data if k else None, so.ctypes.data if k else None),
+             "moni_locate_fetch")
+        return res, pos, sq, so
 
     def ms_lengths_batch(self, seq: np.ndarray, offsets: np.ndarray):
         """legacy `moni ms`: (pointers, lengths) of the forward strand of every read"""

@@ -22,6 +22,9 @@
 // reads, the same path as -m; its @HD line has the tabs of moni_sam_header where the reference's extender writes blanks.
 // --pseudo-ms writes <out>.pseudo_lengths, the text of the legacy `moni pseudo-ms` (src/spumoni/run_spumoni.cpp:466-501; moni_pml_batch): per read a
 // line ">" + the read's running number in the input, then its pseudo-matching lengths, each followed by a blank.  Single-end reads, the same path as -m.
+// --locate [--max-occ N] [--both-strands] writes <out>.locate (moni_locate_batch: exact-match count and locate, what r_index::count / locate_all give):
+// per pattern and strand one line `name <+|-> count matched occurrences`, tab-separated, the occurrences as seqname:pos (1-based), comma-separated, in
+// the library's order, `*` when there are none.  Single-end input (FASTA or FASTQ), the same path as -m.
 // -n loads <prefix>.thrbv.full.ms (no LCP samples); -q is accepted (the text comes from the BWT, not from either grammar).
 // -c writes <sam>.csv (per-read MEM statistics, csv.hpp:55-67; through the host pipeline - for pairs one line per pair, moni_pe_align_csv_batch).  -Z (secondary chains,
 // chain.hpp:442-727) acts on paired input and is ignored for single-end input, as in the reference (aligner_ksw2.hpp:1190-1191 is the only call site).
@@ -185,6 +188,8 @@ struct Args {
     bool legacy_ms = false, legacy_mems = false;      // --ms / --mems
     bool extend = false;                              // --extend: the legacy `moni extend` (longest MEM of each strand, extended to both sides)
     bool pseudo_ms = false;                           // --pseudo-ms: the legacy `moni pseudo-ms` (pseudo-matching lengths of every read)
+    bool locate = false, both_strands = false;        // --locate [--both-strands]: exact-match count and locate of every pattern
+    uint32_t max_occ = 0;                             // --max-occ: positions listed per pattern and strand (0: counts alone)
     int gpus = 1;
     size_t gpu_batch = 1048576;
     int ctx_per_gpu = 3;               // streaming path: contexts (ranges in flight) per GPU
@@ -209,11 +214,14 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--mems")) { a.legacy_mems = true; continue; }
         if (!strcmp(argv[i], "--extend")) { a.extend = true; continue; }
         if (!strcmp(argv[i], "--pseudo-ms")) { a.pseudo_ms = true; continue; }
+        if (!strcmp(argv[i], "--locate")) { a.locate = true; continue; }
+        if (!strcmp(argv[i], "--both-strands")) { a.both_strands = true; continue; }
+        if (!strcmp(argv[i], "--max-occ") && i + 1 < argc) { a.max_occ = (uint32_t)strtoul(argv[++i], nullptr, 10); continue; }
         av.push_back(argv[i]);
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems | --extend | --pseudo-ms]\n";
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems | --extend | --pseudo-ms | --locate [--max-occ N] [--both-strands]]\n";
     int c;
     char* s;
     optind = 1;
@@ -733,6 +741,15 @@ int main(int argc, char** argv) {
         if (a.legacy_mems) die("--pseudo-ms cannot be combined with --mems");
         if (a.extend) die("--pseudo-ms cannot be combined with --extend");
     }
+    if (a.locate) {          // exact-match count and locate: single-end patterns, one mode at a time
+        if (paired) die("--locate takes single-end input (-p), not -1 / -2");
+        if (a.report_mems) die("--locate cannot be combined with -m");
+        if (a.csv) die("--locate cannot be combined with -c");
+        if (a.legacy_ms) die("--locate cannot be combined with --ms");
+        if (a.legacy_mems) die("--locate cannot be combined with --mems");
+        if (a.extend) die("--locate cannot be combined with --extend");
+        if (a.pseudo_ms) die("--locate cannot be combined with --pseudo-ms");
+    } else if (a.both_strands || a.max_occ) die("--max-occ / --both-strands belong to --locate");
     if (a.extend) {          // extend mode: single-end reads, one mode at a time
         if (paired) die("--extend takes single-end input (-p), not -1 / -2");
         if (a.report_mems) die("--extend cannot be combined with -m");
@@ -748,7 +765,7 @@ int main(int argc, char** argv) {
     if (!a.output.empty()) sam_filename = a.output;
     if (paired) return run_paired(a, sam_filename);
     const bool legacy = a.legacy_ms || a.legacy_mems;
-    if ((legacy || a.pseudo_ms) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths
+    if ((legacy || a.pseudo_ms || a.locate) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate)
     info("Output file: " + sam_filename);
     MappedReader mrd;
     const bool mapped = mrd.open(a.patterns);
@@ -760,11 +777,11 @@ int main(int argc, char** argv) {
         bases = b.seq.size();
         printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : ""));
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : (a.locate ? (a.both_strands ? " mode=locate strands=2" : " mode=locate strands=1") : "")));
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
-    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && !a.pseudo_ms && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
+    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && !a.pseudo_ms && !a.locate && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
     const int per_gpu = legacy ? 1 : (fast ? a.ctx_per_gpu : 2);                      // contexts (batches in flight) per GPU
     std::vector<moni_index_t*> idx(a.gpus, nullptr);
     std::vector<moni_ctx_t*> ctx((size_t)a.gpus * per_gpu, nullptr);
@@ -874,6 +891,7 @@ int main(int argc, char** argv) {
     if (a.legacy_ms) { out = fopen((sam_filename + ".pointers").c_str(), "w"); out2 = fopen((sam_filename + ".lengths").c_str(), "w"); if (!out || !out2) die("open() file " + sam_filename + ".pointers/.lengths failed"); }
     else if (a.legacy_mems) { out = fopen((sam_filename + ".mems").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".mems failed"); }
     else if (a.pseudo_ms) { out = fopen((sam_filename + ".pseudo_lengths").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".pseudo_lengths failed"); }
+    else if (a.locate) { out = fopen((sam_filename + ".locate").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".locate failed"); }
     else {
         out = fopen(sam_filename.c_str(), "w");
         if (!out) die("open() file " + sam_filename + " failed");
@@ -884,6 +902,12 @@ int main(int argc, char** argv) {
             static const char hdr[] = "Read,Unique,Total,Max_Freq,Min_Freq,Highest_Occ,Lowest_Occ,Filtered,Chains_Skipped\n";
             put(hdr, sizeof hdr - 1, out2);
         }
+    }
+    std::vector<std::string> seq_names;          // --locate: the sequences' names, from the header's @SQ lines (one per sequence of the concatenation, in order)
+    if (a.locate) {
+        char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
+        const std::string hs(h, hl); moni_free(h);
+        for (size_t at = 0; (at = hs.find("@SQ\tSN:", at)) != std::string::npos;) { at += 7; seq_names.push_back(hs.substr(at, hs.find('\t', at) - at)); }
     }
     auto t0 = std::chrono::steady_clock::now();
     // ---- reader thread -> bounded queue of parsed batches -> workers -> bounded in-order window -> writer thread ----
@@ -994,6 +1018,35 @@ int main(int argc, char** argv) {
                     if (hits[r]) ++n_al;          // reads with a length >= -l somewhere
                 }
                 d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
+            } else if (a.locate) {          // one line per pattern and strand: name, strand, count, bytes matched, the occurrences kept
+                moni_locate_params_t lp; moni_locate_params_default(&lp);
+                lp.strands = a.both_strands ? 2 : 1; lp.max_occ = a.max_occ;
+                std::vector<moni_locate_res_t> res(b.n() * lp.strands + 1);
+                uint32_t* sq = nullptr; uint64_t* so = nullptr; uint64_t n_occ = 0;
+                const int lr = moni_locate_batch(C, &rb, &lp, res.data(), nullptr, &sq, &so, &n_occ);
+                if (lr) die("moni_locate_batch failed (" + std::to_string(lr) + ")");
+                std::string sa;
+                for (size_t r = 0; r < b.n(); ++r) {
+                    bool occurs = false;
+                    for (uint32_t s = 0; s < lp.strands; ++s) {
+                        const moni_locate_res_t& R = res[r * lp.strands + s];
+                        sa.append((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r]));
+                        sa += s ? "\t-\t" : "\t+\t";
+                        sa += std::to_string(R.count); sa.push_back('\t'); sa += std::to_string(R.matched); sa.push_back('\t');
+                        if (!R.n_occ) sa.push_back('*');
+                        for (uint32_t k = 0; k < R.n_occ; ++k) {
+                            const uint64_t o = R.occ_off + k;
+                            if (o >= n_occ || sq[o] >= seq_names.size()) die("moni_locate_batch returned a position outside the index");
+                            if (k) sa.push_back(',');
+                            sa += seq_names[sq[o]]; sa.push_back(':'); sa += std::to_string(so[o] + 1);
+                        }
+                        sa.push_back('\n');
+                        occurs = occurs || R.count;
+                    }
+                    if (occurs) ++n_al;
+                }
+                moni_free(sq); moni_free(so);
+                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
             } else if (a.extend) {          // extender::config_t from the flags it shares with the aligner (-l -L -A -B -O -E)
                 moni_extend_params_t xp; moni_extend_params_default(&xp);
                 xp.min_len = a.P.min_len; xp.ext_len = a.P.ext_len; xp.smatch = a.P.smatch; xp.smismatch = a.P.smismatch; xp.gapo = a.P.gapo; xp.gape = a.P.gape;
@@ -1035,7 +1088,7 @@ int main(int argc, char** argv) {
     close_out(out2);
     delete zrd;
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    info(std::string(a.extend ? "Number of extended reads: " : a.pseudo_ms ? "Number of reads with a pseudo-matching length >= -l: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
+    info(std::string(a.extend ? "Number of extended reads: " : a.pseudo_ms ? "Number of reads with a pseudo-matching length >= -l: " : a.locate ? "Number of patterns that occur: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
     info("Elapsed time (s): " + std::to_string(el));
     info("Reads per second: " + std::to_string(processed / (el > 0 ? el : 1)));
     info("Stage busy seconds: reader (parse) " + std::to_string(t_reader) + ", library calls summed over " + std::to_string(ctx.size()) + " workers " + std::to_string(t_align) +
