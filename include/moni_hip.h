@@ -377,6 +377,37 @@ int  moni_locate_fetch(moni_ctx_t *ctx, moni_locate_res_t *res, uint64_t *pos, u
 int  moni_locate_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const moni_locate_params_t *prm,
                        moni_locate_res_t *res, uint64_t **pos, uint32_t **seq, uint64_t **seq_off, uint64_t *n_occ);
 
+/* ---- sequence counts: in which sequences of the index a pattern occurs, and how often in each ---- */
+/* The search is moni_locate's (strand 0 the bytes as they are, strand 1 the reverse complement, task t = pattern * strands + strand).  Every
+ * occurrence is attributed to the sequence its first byte lies in - the seq of moni_locate_res_t's lists, no lift-over - and counted into a dense
+ * table of n_tasks rows of n_seq 64-bit counts.  The whole interval is enumerated, in pieces that run in parallel (one per BWT run the interval
+ * touches), so the cost does not depend on a cap per pattern; max_walk bounds it instead. */
+typedef struct { uint32_t strands;    /* 1: forward only, 2: forward and reverse complement */
+                 uint32_t reserved;   /* 0 */
+                 uint64_t max_walk;   /* a task with count > max_walk is not enumerated; 0 = no limit */
+               } moni_seqcount_params_t;
+/* count, sa_lo, matched: as in moni_locate_res_t, exact whether or not the task was walked.  walked: 1 where the interval was enumerated
+ * (count <= max_walk, or no limit) - then the task's row sums to count and n_seqs is the number of its non-zero entries; 0 where it was not - then
+ * the row is all zero and n_seqs is 0.  n_segs: the pieces the interval was cut into, 0 for a task that was not walked or has no occurrence. */
+typedef struct { uint64_t count, sa_lo; uint32_t matched, n_seqs, walked, n_segs; } moni_seqcount_res_t;
+void moni_seqcount_params_default(moni_seqcount_params_t *p);        /* strands 1, max_walk 1 << 20 */
+/* Device-only run over the batch that moni_reads_upload made resident; the results stay in HBM.  MONI_EINVAL: strands outside {1, 2}, a non-zero
+ * reserved, no resident batch; MONI_ENOMEM: the table of n_tasks * n_seq * 8 bytes cannot be had.  moni_last_kernel_ms(ctx, 0, ..) then gives
+ * count_kernel's time, (ctx, 3, ..) the walk's with its planning and scan, (ctx, 6, ..) the whole run's; moni_last_counters: [0] search steps,
+ * [1] fast rows fetched, [2] phi steps = the sum of count - n_segs over the walked tasks, [3] steps that took the general path.  Works on an index
+ * without LCP samples. */
+int  moni_seqcount_run(moni_ctx_t *ctx, const moni_seqcount_params_t *prm);
+/* The shape of what moni_seqcount_fetch would write (either pointer may be NULL); MONI_EINVAL before any run, and after another batch was made
+ * resident (moni_reads_upload, moni_reads_swap, any *_batch call). */
+int  moni_seqcount_sizes(moni_ctx_t *ctx, uint64_t *n_tasks, uint32_t *n_seq);
+/* The results of the last moni_seqcount_run on this context: res holds n_tasks records, counts n_tasks * n_seq values, one row per task (either
+ * pointer may be NULL). */
+int  moni_seqcount_fetch(moni_ctx_t *ctx, moni_seqcount_res_t *res, uint64_t *counts);
+/* Host-buffer form: upload, run, fetch into the caller's buffers (batch->n_reads * strands records and rows; counts may be NULL).  An empty batch
+ * gives MONI_OK. */
+int  moni_seqcount_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const moni_seqcount_params_t *prm,
+                         moni_seqcount_res_t *res, uint64_t *counts);
+
 /* ---- the reference's on-disk liftidx (<prefix>.ldx: include/aligner/liftidx.hpp:117-143 over include/common/seqidx.hpp:197-238) ---- */
 /* Both layouts load: the current one (u64 w after u) and the older one the reference's fixture data/Chr21.10.ldx has. */
 int moni_ldx_info(const char *path, uint64_t *n_seq, uint64_t *u, uint64_t *w, int *has_w);

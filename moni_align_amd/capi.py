@@ -31,6 +31,7 @@ EXPORTS = [
     "moni_extend_params_default", "moni_extend_batch", "moni_extend_run",
     "moni_pml_batch", "moni_pml_run", "moni_pml_fetch", "moni_pml_sizes",
     "moni_locate_params_default", "moni_locate_run", "moni_locate_sizes", "moni_locate_fetch", "moni_locate_batch",
+    "moni_seqcount_params_default", "moni_seqcount_run", "moni_seqcount_sizes", "moni_seqcount_fetch", "moni_seqcount_batch",
 ]
 
 
@@ -97,6 +98,10 @@ class LocateParamsC(C.Structure):
     _fields_ = [("strands", C.c_uint32), ("max_occ", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class SeqcountParamsC(C.Structure):
+    _fields_ = [("strands", C.c_uint32), ("reserved", C.c_uint32), ("max_walk", C.c_uint64)]
+
+
 class DpParamsC(C.Structure):
     _fields_ = [("m", C.c_int8), ("mat", C.c_int8 * 25), ("q", C.c_int8), ("e", C.c_int8),
                 ("w", C.c_int32), ("zdrop", C.c_int32), ("end_bonus", C.c_int32)]
@@ -111,7 +116,8 @@ DP_RESULT_DTYPE = np.dtype([("max", "<i4"), ("max_q", "<i4"), ("max_t", "<i4"), 
                             ("mte", "<i4"), ("mte_q", "<i4"), ("score", "<i4"), ("reach_end", "<i4"),
                             ("zdropped", "<i4"), ("n_cigar", "<u4"), ("cigar_off", "<u4")])
 LOCATE_RES_DTYPE = np.dtype([("count", "<u8"), ("sa_lo", "<u8"), ("occ_off", "<u8"), ("n_occ", "<u4"), ("matched", "<u4")])
-assert LOCATE_RES_DTYPE.itemsize == 32
+SEQCOUNT_RES_DTYPE = np.dtype([("count", "<u8"), ("sa_lo", "<u8"), ("matched", "<u4"), ("n_seqs", "<u4"), ("walked", "<u4"), ("n_segs", "<u4")])
+assert LOCATE_RES_DTYPE.itemsize == 32 and SEQCOUNT_RES_DTYPE.itemsize == 32
 assert MEM_DTYPE.itemsize == 48 and DP_TASK_DTYPE.itemsize == 32 and DP_RESULT_DTYPE.itemsize == 48
 
 DEFAULT_MAT = [2, -4, -4, -4, 0, -4, 2, -4, -4, 0, -4, -4, 2, -4, 0, -4, -4, -4, 2, 0, 0, 0, 0, 0, 0]
@@ -194,6 +200,12 @@ def lib():
         L.moni_locate_run.argtypes = [C.c_void_p, C.POINTER(LocateParamsC)]
         L.moni_locate_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.moni_locate_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.moni_seqcount_params_default.argtypes = [C.POINTER(SeqcountParamsC)]
+        L.moni_seqcount_params_default.restype = None
+        L.moni_seqcount_run.argtypes = [C.c_void_p, C.POINTER(SeqcountParamsC)]
+        L.moni_seqcount_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        L.moni_seqcount_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.moni_seqcount_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.POINTER(SeqcountParamsC), C.c_void_p, C.c_void_p]
         L.moni_locate_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.POINTER(LocateParamsC), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_sam_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -633,6 +645,47 @@ class Ctx:
         _chk(self._L.moni_locate_fetch(self._h, res.ctypes.data, pos.ctypes.data if k else None, sq.ctypes.data if k else None, so.ctypes.data if k else None),
              "moni_locate_fetch")
         return res, pos, sq, so
+
+    def _seqcount_params(self, strands: int, max_walk: int) -> "SeqcountParamsC":
+        p = SeqcountParamsC()
+        self._L.moni_seqcount_params_default(C.byref(p))
+        p.strands, p.max_walk = strands, max_walk
+        return p
+
+    def seqcount_batch(self, seq: np.ndarray, offsets: np.ndarray, strands: int = 1, max_walk: int = 1 << 20):
+        """per-sequence occurrence counts (moni_seqcount_batch): (res, counts) - res[i * strands + s] (SEQCOUNT_RES_DTYPE: count, sa_lo, matched,
+        n_seqs, walked, n_segs) of pattern i on strand s and counts[i * strands + s, q], its occurrences that start in sequence q; a task with
+        count > max_walk (0: no limit) is not walked and its row is zero"""
+        b, keep = self._batch(seq, offsets)
+        n = len(offsets) - 1
+        p = self._seqcount_params(strands, max_walk)
+        res = np.zeros(n * strands, dtype=SEQCOUNT_RES_DTYPE)
+        _chk(self._L.moni_seqcount_batch(self._h, C.byref(b), C.byref(p), res.ctypes.data, None), "moni_seqcount_batch")
+        self.n_reads = n
+        if not n:                                    # nothing was run: no row, and no width to ask for
+            return res, np.zeros((0, 0), dtype=np.uint64)
+        counts = np.zeros(self.seqcount_sizes(), dtype=np.uint64)          # the table's width is the index's: asked once the run has happened
+        _chk(self._L.moni_seqcount_fetch(self._h, None, counts.ctypes.data), "moni_seqcount_fetch")
+        return res, counts
+
+    def seqcount_run(self, strands: int = 1, max_walk: int = 1 << 20):
+        """moni_seqcount_run over the batch made resident by upload(): device only, the results wait for seqcount_fetch()"""
+        p = self._seqcount_params(strands, max_walk)
+        _chk(self._L.moni_seqcount_run(self._h, C.byref(p)), "moni_seqcount_run")
+
+    def seqcount_sizes(self):
+        """(n_tasks, n_seq) of the last seqcount_run()"""
+        nt, ns = C.c_uint64(), C.c_uint32()
+        _chk(self._L.moni_seqcount_sizes(self._h, C.byref(nt), C.byref(ns)), "moni_seqcount_sizes")
+        return nt.value, ns.value
+
+    def seqcount_fetch(self, want_counts: bool = True):
+        """(res, counts) of the last seqcount_run(), sized by moni_seqcount_sizes; want_counts=False fetches the records alone (counts is None)"""
+        nt, ns = self.seqcount_sizes()
+        res = np.zeros(nt, dtype=SEQCOUNT_RES_DTYPE)
+        counts = np.zeros((nt, ns), dtype=np.uint64) if want_counts else None
+        _chk(self._L.moni_seqcount_fetch(self._h, res.ctypes.data, counts.ctypes.data if want_counts else None), "moni_seqcount_fetch")
+        return res, counts
 
     def ms_lengths_batch(self, seq: np.ndarray, offsets: np.ndarray):
         """legacy `moni ms`: (pointers, lengths) of the forward strand of every read"""

@@ -40,6 +40,7 @@
 #include "extend_kernels.hip"
 #include "pml_kernels.hip"
 #include "locate_kernels.hip"
+#include "seqcount_kernels.hip"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "moni_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return MONI_ENODEV; } } while (0)
 
@@ -210,6 +211,11 @@ struct moni_ctx {
         DBuf<moni_locate_res_t> res; DBuf<uint64_t> toe, cnt, off, pos, seq_off; DBuf<uint32_t> seq; uint64_t n_tasks = 0, n_occ = 0; bool valid = false;
         void release() { res.release(); toe.release(); cnt.release(); off.release(); pos.release(); seq_off.release(); seq.release(); valid = false; }
     } loc;
+    struct ScBufs {         // sequence counts (seqcount_api.inc): the last run's records and table, on the device until moni_seqcount_fetch; grow-only
+        DBuf<moni_locate_res_t> lres; DBuf<moni_seqcount_res_t> res; DBuf<uint64_t> toe, cnt, off, counts; DBuf<uint32_t> k_lo;
+        uint64_t n_tasks = 0, n_segs = 0; uint32_t n_seq = 0; bool valid = false;
+        void release() { lres.release(); res.release(); toe.release(); cnt.release(); off.release(); counts.release(); k_lo.release(); valid = false; }
+    } sc;
     int n_cu_cached = 0, pe_occ_cached = 0;          // hipGetDeviceProperties / the occupancy query take a millisecond each: asked once per context
 };
 
@@ -527,7 +533,7 @@ void moni_ctx_destroy(moni_ctx_t* c) {
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (auto e : c->ak_begin) (void)hipEventDestroy(e);
     for (auto e : c->ak_done) (void)hipEventDestroy(e);
-    c->ex.release(); c->pml.release(); c->loc.release();
+    c->ex.release(); c->pml.release(); c->loc.release(); c->sc.release();
     c->ak_recs.release(); c->ak_cig.release(); c->ak_alt.release(); c->ak_minscore.release(); c->pe.release();
     if (c->d_ak_cursors) (void)hipFree(c->d_ak_cursors);
     if (c->out_buf) (void)hipHostFree(c->out_buf);
@@ -581,7 +587,7 @@ static int reads_upload(moni_ctx* c, const moni_read_batch_t* b, bool keep_host_
     c->h_blk.swap(blk);
     if (keep_host_copy) { c->h_seq.assign(b->seq + b->offsets[0], b->seq + b->offsets[0] + total); c->h_offs = rel; }
     else { c->h_seq.clear(); c->h_offs.clear(); }
-    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false;
+    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false;
     return MONI_OK;
 }
 
@@ -593,7 +599,7 @@ int moni_reads_swap(moni_ctx_t* c, uint32_t slot) {
     moni_ctx::Stash& x = c->stash[slot];
     std::swap(c->seq, x.seq); std::swap(c->offs, x.offs); std::swap(c->blk, x.blk); c->h_blk.swap(x.h_blk); std::swap(c->n_reads, x.n_reads); std::swap(c->total_len, x.total_len); std::swap(c->max_len, x.max_len);
     c->h_seq.swap(x.h_seq); c->h_offs.swap(x.h_offs);
-    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false;
+    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false;
     return MONI_OK;
 }
 
@@ -1920,5 +1926,6 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "extend_api.inc"
 #include "pml_api.inc"
 #include "locate_api.inc"
+#include "seqcount_api.inc"
 
 }  // extern "C"

@@ -22,6 +22,9 @@
 // reads, the same path as -m; its @HD line has the tabs of moni_sam_header where the reference's extender writes blanks.
 // --pseudo-ms writes <out>.pseudo_lengths, the text of the legacy `moni pseudo-ms` (src/spumoni/run_spumoni.cpp:466-501; moni_pml_batch): per read a
 // line ">" + the read's running number in the input, then its pseudo-matching lengths, each followed by a blank.  Single-end reads, the same path as -m.
+// --seq-count [--both-strands] [--max-walk N] writes <out>.seqcount (moni_seqcount_batch: per pattern and strand, the occurrences that start in each
+// sequence of the index): name <+|-> count matched n_seqs seqname:count,... - the sequences with a count, in index order; * for none, ? where the
+// pattern has more than --max-walk occurrences and was not enumerated.
 // --locate [--max-occ N] [--both-strands] writes <out>.locate (moni_locate_batch: exact-match count and locate, what r_index::count / locate_all give):
 // per pattern and strand one line `name <+|-> count matched occurrences`, tab-separated, the occurrences as seqname:pos (1-based), comma-separated, in
 // the library's order, `*` when there are none.  Single-end input (FASTA or FASTQ), the same path as -m.
@@ -190,6 +193,8 @@ struct Args {
     bool pseudo_ms = false;                           // --pseudo-ms: the legacy `moni pseudo-ms` (pseudo-matching lengths of every read)
     bool locate = false, both_strands = false;        // --locate [--both-strands]: exact-match count and locate of every pattern
     uint32_t max_occ = 0;                             // --max-occ: positions listed per pattern and strand (0: counts alone)
+    bool seq_count = false;                           // --seq-count [--both-strands] [--max-walk N]: per-sequence occurrence counts of every pattern
+    uint64_t max_walk = 1ull << 20; bool max_walk_set = false;      // --max-walk: patterns with more occurrences are counted, not enumerated (0: no limit)
     int gpus = 1;
     size_t gpu_batch = 1048576;
     int ctx_per_gpu = 3;               // streaming path: contexts (ranges in flight) per GPU
@@ -215,13 +220,15 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--extend")) { a.extend = true; continue; }
         if (!strcmp(argv[i], "--pseudo-ms")) { a.pseudo_ms = true; continue; }
         if (!strcmp(argv[i], "--locate")) { a.locate = true; continue; }
+        if (!strcmp(argv[i], "--seq-count")) { a.seq_count = true; continue; }
+        if (!strcmp(argv[i], "--max-walk") && i + 1 < argc) { a.max_walk = strtoull(argv[++i], nullptr, 10); a.max_walk_set = true; continue; }
         if (!strcmp(argv[i], "--both-strands")) { a.both_strands = true; continue; }
         if (!strcmp(argv[i], "--max-occ") && i + 1 < argc) { a.max_occ = (uint32_t)strtoul(argv[++i], nullptr, 10); continue; }
         av.push_back(argv[i]);
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems | --extend | --pseudo-ms | --locate [--max-occ N] [--both-strands]]\n";
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems | --extend | --pseudo-ms | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands]]\n";
     int c;
     char* s;
     optind = 1;
@@ -749,7 +756,17 @@ int main(int argc, char** argv) {
         if (a.legacy_mems) die("--locate cannot be combined with --mems");
         if (a.extend) die("--locate cannot be combined with --extend");
         if (a.pseudo_ms) die("--locate cannot be combined with --pseudo-ms");
-    } else if (a.both_strands || a.max_occ) die("--max-occ / --both-strands belong to --locate");
+    } else if ((a.both_strands && !a.seq_count) || a.max_occ) die("--max-occ / --both-strands belong to --locate");
+    if (a.seq_count) {       // per-sequence occurrence counts: single-end patterns, one mode at a time
+        if (paired) die("--seq-count takes single-end input (-p), not -1 / -2");
+        if (a.report_mems) die("--seq-count cannot be combined with -m");
+        if (a.csv) die("--seq-count cannot be combined with -c");
+        if (a.legacy_ms) die("--seq-count cannot be combined with --ms");
+        if (a.legacy_mems) die("--seq-count cannot be combined with --mems");
+        if (a.extend) die("--seq-count cannot be combined with --extend");
+        if (a.pseudo_ms) die("--seq-count cannot be combined with --pseudo-ms");
+        if (a.locate) die("--seq-count cannot be combined with --locate");
+    } else if (a.max_walk_set) die("--max-walk belongs to --seq-count");
     if (a.extend) {          // extend mode: single-end reads, one mode at a time
         if (paired) die("--extend takes single-end input (-p), not -1 / -2");
         if (a.report_mems) die("--extend cannot be combined with -m");
@@ -765,7 +782,7 @@ int main(int argc, char** argv) {
     if (!a.output.empty()) sam_filename = a.output;
     if (paired) return run_paired(a, sam_filename);
     const bool legacy = a.legacy_ms || a.legacy_mems;
-    if ((legacy || a.pseudo_ms || a.locate) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate)
+    if ((legacy || a.pseudo_ms || a.locate || a.seq_count) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate / .seqcount)
     info("Output file: " + sam_filename);
     MappedReader mrd;
     const bool mapped = mrd.open(a.patterns);
@@ -777,11 +794,11 @@ int main(int argc, char** argv) {
         bases = b.seq.size();
         printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : (a.locate ? (a.both_strands ? " mode=locate strands=2" : " mode=locate strands=1") : "")));
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : (a.locate ? (a.both_strands ? " mode=locate strands=2" : " mode=locate strands=1") : (a.seq_count ? (a.both_strands ? " mode=seq-count strands=2" : " mode=seq-count strands=1") : ""))));
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
-    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && !a.pseudo_ms && !a.locate && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
+    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && !a.pseudo_ms && !a.locate && !a.seq_count && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
     const int per_gpu = legacy ? 1 : (fast ? a.ctx_per_gpu : 2);                      // contexts (batches in flight) per GPU
     std::vector<moni_index_t*> idx(a.gpus, nullptr);
     std::vector<moni_ctx_t*> ctx((size_t)a.gpus * per_gpu, nullptr);
@@ -892,6 +909,7 @@ int main(int argc, char** argv) {
     else if (a.legacy_mems) { out = fopen((sam_filename + ".mems").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".mems failed"); }
     else if (a.pseudo_ms) { out = fopen((sam_filename + ".pseudo_lengths").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".pseudo_lengths failed"); }
     else if (a.locate) { out = fopen((sam_filename + ".locate").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".locate failed"); }
+    else if (a.seq_count) { out = fopen((sam_filename + ".seqcount").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".seqcount failed"); }
     else {
         out = fopen(sam_filename.c_str(), "w");
         if (!out) die("open() file " + sam_filename + " failed");
@@ -903,12 +921,14 @@ int main(int argc, char** argv) {
             put(hdr, sizeof hdr - 1, out2);
         }
     }
-    std::vector<std::string> seq_names;          // --locate: the sequences' names, from the header's @SQ lines (one per sequence of the concatenation, in order)
-    if (a.locate) {
+    std::vector<std::string> seq_names;          // --locate / --seq-count: the sequences' names, from the header's @SQ lines (one per sequence of the concatenation, in order)
+    if (a.locate || a.seq_count) {
         char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
         const std::string hs(h, hl); moni_free(h);
         for (size_t at = 0; (at = hs.find("@SQ\tSN:", at)) != std::string::npos;) { at += 7; seq_names.push_back(hs.substr(at, hs.find('\t', at) - at)); }
     }
+    size_t batch_cap = a.gpu_batch;          // reads per GPU batch; --seq-count keeps the dense table (tasks x sequences x 8 bytes) below 1 GiB
+    if (a.seq_count) batch_cap = std::min(batch_cap, std::max<size_t>(1, (((size_t)1 << 27) - 1) / (std::max<size_t>(1, seq_names.size()) * (a.both_strands ? 2 : 1))));
     auto t0 = std::chrono::steady_clock::now();
     // ---- reader thread -> bounded queue of parsed batches -> workers -> bounded in-order window -> writer thread ----
     struct Item { size_t id; Batch* b; size_t first; };      // first: the running number of the batch's first read in the input
@@ -932,7 +952,7 @@ int main(int argc, char** argv) {
             // the matching-statistics workspace of a batch is strided by its longest read (2 x reads x longest x 8 bytes): the legacy modes,
             // which take long patterns, close a batch when that product passes 2^28 entries (4 GB)
             size_t longest = 0;
-            while (b->n() < a.gpu_batch && next_record(*b)) {
+            while (b->n() < batch_cap && next_record(*b)) {
                 if (!legacy) continue;
                 longest = std::max(longest, (size_t)(b->off[b->n()] - b->off[b->n() - 1]));
                 if (b->n() * longest > ((size_t)1 << 28)) break;
@@ -1047,6 +1067,41 @@ int main(int argc, char** argv) {
                 }
                 moni_free(sq); moni_free(so);
                 d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
+            } else if (a.seq_count) {       // one line per pattern and strand: name, strand, count, bytes matched, sequences that hold it, their counts
+                moni_seqcount_params_t sp; moni_seqcount_params_default(&sp);
+                sp.strands = a.both_strands ? 2 : 1; sp.max_walk = a.max_walk;
+                const size_t n_seq = seq_names.size(), n_tasks = b.n() * sp.strands;
+                std::vector<moni_seqcount_res_t> res(n_tasks + 1);
+                std::vector<uint64_t> counts(n_tasks * n_seq + 1);
+                const int sr = moni_seqcount_batch(C, &rb, &sp, res.data(), counts.data());
+                if (sr) die("moni_seqcount_batch failed (" + std::to_string(sr) + ")");
+                std::string sa;
+                for (size_t r = 0; r < b.n(); ++r) {
+                    bool occurs = false;
+                    for (uint32_t s = 0; s < sp.strands; ++s) {
+                        const size_t t = r * sp.strands + s;
+                        const moni_seqcount_res_t& R = res[t];
+                        sa.append((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r]));
+                        sa += s ? "\t-\t" : "\t+\t";
+                        sa += std::to_string(R.count); sa.push_back('\t'); sa += std::to_string(R.matched); sa.push_back('\t'); sa += std::to_string(R.n_seqs); sa.push_back('\t');
+                        if (!R.walked) sa.push_back('?');
+                        else if (!R.n_seqs) sa.push_back('*');
+                        else {
+                            bool first = true;
+                            for (size_t q = 0; q < n_seq; ++q) {
+                                const uint64_t v = counts[t * n_seq + q];
+                                if (!v) continue;
+                                if (!first) sa.push_back(',');
+                                first = false;
+                                sa += seq_names[q]; sa.push_back(':'); sa += std::to_string(v);
+                            }
+                        }
+                        sa.push_back('\n');
+                        occurs = occurs || R.count;
+                    }
+                    if (occurs) ++n_al;
+                }
+                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
             } else if (a.extend) {          // extender::config_t from the flags it shares with the aligner (-l -L -A -B -O -E)
                 moni_extend_params_t xp; moni_extend_params_default(&xp);
                 xp.min_len = a.P.min_len; xp.ext_len = a.P.ext_len; xp.smatch = a.P.smatch; xp.smismatch = a.P.smismatch; xp.gapo = a.P.gapo; xp.gape = a.P.gape;
@@ -1088,7 +1143,7 @@ int main(int argc, char** argv) {
     close_out(out2);
     delete zrd;
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    info(std::string(a.extend ? "Number of extended reads: " : a.pseudo_ms ? "Number of reads with a pseudo-matching length >= -l: " : a.locate ? "Number of patterns that occur: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
+    info(std::string(a.extend ? "Number of extended reads: " : a.pseudo_ms ? "Number of reads with a pseudo-matching length >= -l: " : (a.locate || a.seq_count) ? "Number of patterns that occur: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
     info("Elapsed time (s): " + std::to_string(el));
     info("Reads per second: " + std::to_string(processed / (el > 0 ? el : 1)));
     info("Stage busy seconds: reader (parse) " + std::to_string(t_reader) + ", library calls summed over " + std::to_string(ctx.size()) + " workers " + std::to_string(t_align) +
