@@ -149,6 +149,7 @@ struct af_args_t {
     uint64_t* bnd;                           // per resident DP wave: (H, E) of a target block's last row for every query position (global problems)
     uint32_t* ctr;                           // AF_NCTR counters, see the AFC_* indices
     unsigned long long* prof;                // AF_PROFILE builds: wave cycles per phase
+    unsigned long long* prep_prof;           // AF_PROFILE builds: finish_prep_kernel's stamps of this launch (AFPP_WAVE words per wavefront, then AFPP_READ per read)
     uint32_t l0_mm, l0_ma;                   // capacities (seeds, anchors) of the instance the launch uses for LEVEL 0 (classify_kernel)
     uint32_t wave_max;                       // a group of the WILD / GLOBAL / GWILD queues with at most this many chunks is computed by dp_wave_kernel (af_chunk_kernel decides; MONI_AF_WAVE_MAX)
     uint32_t dbg;                            // AF_PROFILE builds: 1 = no direction stores, 2 = no DP rows (timing experiments; results are wrong)
@@ -156,10 +157,17 @@ struct af_args_t {
 #ifdef AF_PROFILE
 #define AF_STAMP(var) const long long var = clock64()
 #define AF_PROF(G, slot, t0, t1) do { if (threadIdx.x == 0 && (G).prof) atomicAdd(&(G).prof[slot], (unsigned long long)((t1) - (t0))); } while (0)
+#define AF_ACC(acc, t0, t1) (acc) += (t1) - (t0)
 #else
 #define AF_STAMP(var) do {} while (0)
 #define AF_PROF(G, slot, t0, t1) do {} while (0)
+#define AF_ACC(acc, t0, t1) do {} while (0)
 #endif
+// finish_prep_kernel's stamps (AF_PROFILE builds).  Per wavefront AFPP_WAVE words: 100 MHz clock at entry and exit, then the cycles of the phases (a wavefront's
+// lanes leave a loop together, so a phase's cycles are its slowest lane's): stitch, lift, MAPQ and sequence lookups, first MD walk, second MD walk, alternatives.
+// Per read AFPP_READ words: what sizes the lane's loops.
+#define AFPP_WAVE 8u
+#define AFPP_READ 2u
 enum { AFC_TASKS = 0, AFC_FALLBACK = 1, AFC_TRACED = 2, AFC_READ_CUR = 3, AFC_DIRS_OVF = 4, AFC_CELLS = 6 /* 64 bit */, AFC_DIROFF = 8 /* 64 bit */,
        AFC_NCHUNKS = 10 /* + group (7) */, AFC_CURSOR = 18 /* + group (7) */, AFC_BIG = 26, AFC_BIG_CUR = 27, AFC_HUGE = 28, AFC_HUGE_CUR = 29, AFC_L0 = 30 /* reads of the small instance's list */,
        AFC_NT = 31 /* DP problems queued by bin_tasks_kernel */, AFC_WHY = 32 /* + reason (12) */, AFC_RBYTES = 44 /* 64 bit: text bytes of the DP targets, the R of SURVEY.md 8(d) */,
@@ -3018,6 +3026,10 @@ __device__ __forceinline__ int afl_md(const dp_launch_t& D, const afl_two_t& W, 
 __global__ void __launch_bounds__(64) finish_prep_kernel(const af_args_t G, uint32_t* __restrict__ recipes) {
     const ak_args_t& A = G.A;
     const ak_fmt_t& F = A.fmt;
+#ifdef AF_PROFILE
+    const unsigned long long pw0 = wall_clock64();
+    long long pph[6] = {0, 0, 0, 0, 0, 0};
+#endif
     for (uint64_t r_in = (uint64_t)blockIdx.x * 64 + threadIdx.x; r_in < A.n_reads; r_in += (uint64_t)gridDim.x * 64) {
         const af_plan_t& PL = G.plans[r_in];
         const uint64_t* H = reinterpret_cast<const uint64_t*>(&PL);
@@ -3039,6 +3051,7 @@ __global__ void __launch_bounds__(64) finish_prep_kernel(const af_args_t G, uint
         const moni_lift_seq_t LS0 = A.P.lift_seqs[sid0];
         const af_cand_t C = PL.cand[h_final];
         uint32_t* const cig = S + AFP_CIG; uint32_t* const lcig = S + AFP_LCIG;
+        AF_STAMP(p0);
         // ---- CIGAR stitching (aligner_ksw2.hpp:3049-3108); the last operation written is kept in a register (a match run merges into it) ----
         uint32_t n = 0, last = 0; bool ovf = false;
 #define PUSH(op) do { if (n < AFS_CIG) { last = (op); cig[n++] = last; } else ovf = true; } while (0)
@@ -3066,6 +3079,7 @@ __global__ void __launch_bounds__(64) finish_prep_kernel(const af_args_t G, uint
         }
 #undef PUSH
 #undef PUSH_MERGE_FIRST
+        AF_STAMP(p1); AF_ACC(pph[0], p0, p1);
 #if defined(AF_CUTS)
         if (G.dbg & 0x100000u) { S[AFP_H_FLAGS] = n; continue; }          // timing experiments (results are wrong): stop after the stitching ...
 #endif
@@ -3077,6 +3091,7 @@ __global__ void __launch_bounds__(64) finish_prep_kernel(const af_args_t G, uint
         if (nl < 0) ovf = true;
         const uint64_t lifted = LS0.second + (ovf ? 0ull : lp);
         const uint32_t n_cig = n, n_lcig = nl < 0 ? 0u : (uint32_t)nl;
+        AF_STAMP(p2); AF_ACC(pph[1], p1, p2);
 #if defined(AF_CUTS)
         if (G.dbg & 0x200000u) { S[AFP_H_FLAGS] = n_lcig + (uint32_t)lifted; continue; }          // ... after the lift
 #endif
@@ -3122,19 +3137,40 @@ __global__ void __launch_bounds__(64) finish_prep_kernel(const af_args_t G, uint
 #if defined(AF_CUTS)
             if (G.dbg & 0x400000u) { S[AFP_H_FLAGS] = (uint32_t)mapq + lsid; continue; }          // ... in front of the MD walks
 #endif
+            AF_STAMP(p3); AF_ACC(pph[2], p2, p3);
             if (mapped) nm = afl_md(A.D, W, off, m, strand, lcig, n_lcig, lifted, true, n_md, S + AFP_MD);
+            AF_STAMP(p4); AF_ACC(pph[3], p3, p4);
             lift_nm = same ? nm : afl_md(A.D, W, off, m, strand, cig, n_cig, aln_pos, false, dummy, nullptr);
+            AF_STAMP(p5); AF_ACC(pph[4], p4, p5);
             if (n_md > AFS_MAXMD) { flags |= AFP_F_HOST; n_md = 0; }
             for (uint32_t k = 0; k < n_alt && k < AF_MAX_CAND; ++k) {       // the alternatives' sequences and 1-based positions
                 const uint64_t ap = PL.alt_pos[k];
                 const uint32_t s2 = ac_seq_of(A.P, ap);
                 S[AFP_ALT + 3 * k] = s2; S[AFP_ALT + 3 * k + 1] = (uint32_t)(ap - A.P.lift_seqs[s2].start + 1); S[AFP_ALT + 3 * k + 2] = (uint32_t)PL.alt_score[k];
             }
+            AF_STAMP(p6); AF_ACC(pph[5], p5, p6);
         }
+#ifdef AF_PROFILE
+        if (G.prep_prof) {
+            unsigned long long* const PR = G.prep_prof + (size_t)AFPP_WAVE * gridDim.x + (size_t)AFPP_READ * r_in;
+            PR[0] = (unsigned long long)n_cig | ((unsigned long long)n_lcig << 16) | ((unsigned long long)n_md << 32) | ((unsigned long long)n_alt << 48) | ((unsigned long long)(flags & AFP_F_HOST ? 1 : 0) << 56);
+            PR[1] = (unsigned long long)rel | ((unsigned long long)LS0.n_runs << 32);
+        }
+#endif
         S[AFP_H_FLAGS] = flags | (n_alt << 8); S[AFP_H_NCIG] = n_cig | (n_lcig << 16); S[AFP_H_NMD] = n_md; S[AFP_H_NM] = (uint32_t)nm; S[AFP_H_LIFTNM] = (uint32_t)lift_nm;
         S[AFP_H_MAPQ] = (uint32_t)mapq; S[AFP_H_SCORE] = (uint32_t)C.score; S[AFP_H_SCORE2] = (uint32_t)score2; S[AFP_H_POS1] = (uint32_t)pos1; S[AFP_H_OAPOS] = (uint32_t)oa_pos;
         S[AFP_H_SIDS] = sid0 | (lsid << 16); S[AFP_H_LIFTED_LO] = (uint32_t)lifted; S[AFP_H_LIFTED_HI] = (uint32_t)(lifted >> 32); S[AFP_H_POS_LO] = (uint32_t)aln_pos; S[AFP_H_POS_HI] = (uint32_t)(aln_pos >> 32);
     }
+#ifdef AF_PROFILE
+    if (G.prep_prof) {
+        for (int x = 0; x < 6; ++x) for (int o = 1; o < 64; o <<= 1) { const long long y = __shfl_xor(pph[x], o); if (y > pph[x]) pph[x] = y; }
+        if (threadIdx.x == 0) {
+            unsigned long long* const PW = G.prep_prof + (size_t)AFPP_WAVE * blockIdx.x;
+            PW[0] = pw0; PW[1] = wall_clock64();
+            for (int x = 0; x < 6; ++x) PW[2 + x] = (unsigned long long)pph[x];
+        }
+    }
+#endif
 }
 
 #define AFR_MAXSEG 136u          // 35 fixed segments + 6 per alternative + the newline

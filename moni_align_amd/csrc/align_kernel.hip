@@ -364,7 +364,13 @@ align_kernel(const ak_args_t A) {
     ac_ws_t& W = S->ws;
     uint8_t* __restrict__ dirs = A.waves[blockIdx.x].dirs;
     if (lane < AK_NL) for (int k = 0; k < 6; ++k) W.prof[k] = 0;
-    int state = lane < AK_NL ? 0 : 2;             // 0: wants a read, 1: waits for DP results, 2: no more reads, 3: finished, record not yet written
+    // A launch for the staged kernels' hand-overs has a full grid and a read or two: only as many lanes as there are reads ask for one (lane 0 of every wavefront
+    // first, so that the reads spread over the wavefronts), and only a wavefront that took a read adds to the statistics.  With every lane of an all but empty
+    // launch asking (65 536 atomics on one address) and adding its zeros (another 285 000 on the counters' two 128-byte lines) the atomics took 3.4 ms to drain;
+    // the one read's own loads waited behind them, and so did finish_prep_kernel of the same sub-batch on the other stream: 3.5 ms instead of 0.29 (profiles/prep_tail).
+    const uint64_t n_launch = A.n_reads_dev ? (uint64_t)*A.n_reads_dev : A.n_reads;
+    int state = lane < AK_NL && (uint64_t)lane * gridDim.x + blockIdx.x < n_launch ? 0 : 2;             // 0: wants a read, 1: waits for DP results, 2: no more reads, 3: finished, record not yet written
+    bool took = false;
     uint64_t r_in = 0;                            // read index inside the launch
     uint64_t r_slot = 0, r_read = 0;              // its record slot and its index in the resident batch
     while (true) {
@@ -375,8 +381,9 @@ align_kernel(const ak_args_t A) {
         if (state == 3 && start) { ak_write_record(A, ak_view(W), S->md_tmp, S->txt_tmp, S->lcig, AC_MAX_CIGAR, r_slot, r_read); state = 0; }
         if (state == 0 && start) {
             r_in = atomicAdd(&A.cursors[4], 1ull);
-            if (r_in >= (A.n_reads_dev ? (uint64_t)*A.n_reads_dev : A.n_reads)) state = 2;
+            if (r_in >= n_launch) state = 2;
             else {
+                took = true;
                 const uint64_t r = A.read_list ? (uint64_t)A.read_list[r_in] : A.read_lo + r_in;
                 r_read = r; r_slot = r - A.read_lo;
                 W.off = A.offs[r]; W.m = (uint32_t)(A.offs[r + 1] - A.offs[r]);
@@ -503,7 +510,8 @@ align_kernel(const ak_args_t A) {
         if (lane == 0) s_cnt[C_DRIVE] += (unsigned long long)(clock64() - c2);
     }
     __syncthreads();
-    if (lane < AK_NL) for (int k = 0; k < 4; ++k) atomicAdd(&A.cursors[10 + k], W.prof[k]);
+    if (__ballot(took) == 0ull) return;
+    if (took) for (int k = 0; k < 4; ++k) atomicAdd(&A.cursors[10 + k], W.prof[k]);
     if (lane == 0) {
         atomicAdd(&A.cursors[2], s_cnt[C_DP]); atomicAdd(&A.cursors[3], s_cnt[C_CELLS]); atomicAdd(&A.cursors[5], s_cnt[C_INIT]); atomicAdd(&A.cursors[6], s_cnt[C_DRIVE]);
         atomicAdd(&A.cursors[7], s_cnt[C_CYDP]);

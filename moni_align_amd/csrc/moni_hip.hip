@@ -156,7 +156,7 @@ struct moni_ctx {
     DBuf<uint8_t> dp_dir_big;
     struct AfSet {          // device buffers of the staged align kernels (align_fast.hip), one set per launch stream
         DBuf<af_plan_t> plans; DBuf<moni_dp_task_t> tasks; DBuf<af_res_t> res; DBuf<uint32_t> bin_q, task_pos, tb_task, big_list, ctr; DBuf<uint8_t> ntasks;
-        DBuf<af_chunk_t> chunks; DBuf<uint8_t> dirs, fin; DBuf<uint32_t> recipes; DBuf<af_ctab_t> ctab; DBuf<af_tb_t> tb; DBuf<uint64_t> bnd; DBuf<unsigned long long> prof, txt_cur;
+        DBuf<af_chunk_t> chunks; DBuf<uint8_t> dirs, fin; DBuf<uint32_t> recipes; DBuf<af_ctab_t> ctab; DBuf<af_tb_t> tb; DBuf<uint64_t> bnd; DBuf<unsigned long long> prof, prep_prof, txt_cur;
         void release() { ctab.release(); ntasks.release(); bnd.release(); prof.release(); big_list.release(); txt_cur.release(); plans.release(); tasks.release(); res.release(); bin_q.release(); task_pos.release(); tb_task.release(); ctr.release();
                          chunks.release(); dirs.release(); fin.release(); recipes.release(); tb.release(); }
     } af[AK_NSET], af_pe[PE_NSET];
@@ -1500,6 +1500,12 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                 if (k < AK_NSET) HIPCHK(hipMemsetAsync(S.prof.p, 0, 32 * 8, sx));
                 G.prof = S.prof.p;
                 if (const char* v = getenv("MONI_AF_DBG")) G.dbg = (uint32_t)atoi(v);
+                {   // finish_prep_kernel's stamps: a region per sub-batch of the set (AFPP_WAVE words per wavefront of the grid, AFPP_READ per read)
+                    const size_t pp_stride = (size_t)AFPP_WAVE * ((sub_reads + 63) / 64 + 1) + (size_t)AFPP_READ * (sub_reads + 1);
+                    if ((rc = S.prep_prof.ensure(pp_stride * ((n_sub + AK_NSET - 1) / AK_NSET)))) return rc;
+                    G.prep_prof = S.prep_prof.p + pp_stride * (k / AK_NSET);
+                    HIPCHK(hipMemsetAsync(G.prep_prof, 0, pp_stride * sizeof(unsigned long long), sx));
+                }
 #endif
 #ifdef AF_CUTS
                 if (const char* v = getenv("MONI_AF_DBG")) G.dbg = (uint32_t)atoi(v);
@@ -1630,6 +1636,32 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                     (double)pf[0], (double)pf[1], (double)pf[5], (double)pf[6], (double)pf[7], (double)pf[2], (double)pf[3], (double)pf[4]);
             fprintf(stderr, "finish_wave_kernel wave cycles (set %d): stage + stitch + lift %.3g, MD / NM / MAPQ %.3g, segment list %.3g, render %.3g, out %.3g, whole read %.3g\n", x,
                     (double)pf[16], (double)pf[17], (double)pf[18], (double)pf[19], (double)pf[21], (double)pf[22]); } }
+        if (use_fast && gpu_text && !fin_v1) for (uint64_t k = 0; k < n_sub; ++k) {          // finish_prep_kernel's wavefronts of every launch: when they ran, and what the slowest one held
+            const uint64_t nr = sub_lo[k + 1] - sub_lo[k];
+            if (!nr) continue;
+            const size_t pp_stride = (size_t)AFPP_WAVE * ((sub_reads + 63) / 64 + 1) + (size_t)AFPP_READ * (sub_reads + 1);
+            const size_t nw = (size_t)std::min<uint64_t>((nr + 63) / 64, (uint64_t)n_cu * 32);
+            std::vector<unsigned long long> pp(AFPP_WAVE * nw + AFPP_READ * nr);
+            HIPCHK(hipMemcpy(pp.data(), c->af[k % AK_NSET].prep_prof.p + pp_stride * (k / AK_NSET), pp.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            unsigned long long first = ~0ull, last_start = 0, last_end = 0; size_t slow = 0; std::vector<unsigned long long> dur(nw);
+            for (size_t w = 0; w < nw; ++w) {
+                const unsigned long long* W = pp.data() + AFPP_WAVE * w;
+                first = std::min(first, W[0]); last_start = std::max(last_start, W[0]); last_end = std::max(last_end, W[1]); dur[w] = W[1] - W[0];
+                if (dur[w] > dur[slow]) slow = w;
+            }
+            std::vector<unsigned long long> sd(dur); std::sort(sd.begin(), sd.end());
+            const unsigned long long* W = pp.data() + AFPP_WAVE * slow;
+            fprintf(stderr, "finish_prep_kernel sub-batch %llu (%llu reads, %zu wavefronts): span %.3f ms, last wavefront starts at %.3f ms; wavefront time median %.3f ms, 99 %% %.3f ms, max %.3f ms\n",
+                    (unsigned long long)k, (unsigned long long)nr, nw, (last_end - first) / 1e5, (last_start - first) / 1e5, sd[nw / 2] / 1e5, sd[nw * 99 / 100] / 1e5, sd[nw - 1] / 1e5);
+            fprintf(stderr, "  slowest wavefront %zu (reads %llu..): starts at %.3f ms, ends at %.3f ms; cycles: stitch %llu, lift %llu, MAPQ + sequences %llu, MD %llu, MD of the unlifted %llu, alternatives %llu\n",
+                    slow, (unsigned long long)(sub_lo[k] + 64 * slow), (W[0] - first) / 1e5, (W[1] - first) / 1e5, W[2], W[3], W[4], W[5], W[6], W[7]);
+            if (sd[nw - 1] > 4 * sd[nw / 2]) {
+                fprintf(stderr, "  its lanes (operations of the CIGAR / of the lifted one / MD items / alternatives / to the host; run hint, runs of the lift):");
+                for (size_t l = 0; l < 64 && 64 * slow + l < nr; ++l) { const unsigned long long* R = pp.data() + AFPP_WAVE * nw + AFPP_READ * (64 * slow + l);
+                    fprintf(stderr, " [%zu: %llu/%llu/%llu/%llu/%llu; %lld, %llu]", l, R[0] & 0xFFFF, (R[0] >> 16) & 0xFFFF, (R[0] >> 32) & 0xFFFF, (R[0] >> 48) & 0xFF, (R[0] >> 56) & 1, (long long)(int32_t)(uint32_t)R[1], R[1] >> 32); }
+                fprintf(stderr, "\n");
+            }
+        }
 #endif
         double ak_sum_ms = c->dp_kernel_ms_accum;
         if (n_sub) { float ms = 0; if (hipEventElapsedTime(&ms, c->ak_begin[0], c->ak_done[n_sub - 1]) == hipSuccess) c->dp_kernel_ms_accum = ms; }      // launches overlap: report the span

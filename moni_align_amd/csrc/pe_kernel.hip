@@ -262,7 +262,9 @@ pe_align_kernel(const pe_args_t A) {
     pe_slot_t* __restrict__ S = A.slots + (size_t)blockIdx.x * NL + (lane < NL ? lane : 0);
     pe_ws_t& W = S->ws;
     uint8_t* __restrict__ dirs = A.waves[blockIdx.x].dirs;
-    int state = lane < NL ? 0 : 2;             // 0: wants a pair, 1: waits for DP results, 2: no more pairs, 3: finished, record not yet written
+    // only as many lanes as the launch has pairs ask for one, lane 0 of every wavefront first (align_kernel: a full grid asking for a hand-over or two is a burst of atomics on one address)
+    const uint64_t n_launch = A.pair_list ? (uint64_t)*A.n_list : A.n_pairs;
+    int state = lane < NL && (uint64_t)lane * gridDim.x + blockIdx.x < n_launch ? 0 : 2;             // 0: wants a pair, 1: waits for DP results, 2: no more pairs, 3: finished, record not yet written
     uint64_t pair = 0;
     while (true) {
         // ---- phase 1 (lane-private): take a pair; seeds -> chains -> first DP request ----
