@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "align_core.h"
+#include "render_core.h"
 
 #define AF_MAX_MEMS 64
 #define AF_MAX_ANCH 256
@@ -2505,11 +2506,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 #define AFW_NAMES 1024           // sequence names kept in LDS when they fit (else they are read from HBM)
 #define AFW_NSEQ 126
 #define AFW_TB_WORDS (AF_TB_CIG + 1)
-static __device__ const char afs_lit[] = "\t" "\t*\t0\t0\t" "\tAS:i:" "\tNM:i:" "\tZS:i:" "\tMD:Z:" "\tOA:Z:" ",+," ",-," "," ";" "\tAA:Z:" "\n" "\t4\t*\t0\t255\t*\t*\t0\t0\t" "*" "^" "MIDNSHP=X" "ACGTN";
+static __device__ const char afs_lit[] = AFR_LIT_TEXT;          // (the text and the LT_* / SK_* names: render_core.h)
 static_assert(sizeof(afs_lit) == 89, "literal table");
-enum { LT_TAB = 0, LT_MATE = 1, LT_AS = 8, LT_NM = 14, LT_ZS = 20, LT_MD = 26, LT_OA = 32, LT_PLUS = 38, LT_MINUS = 41, LT_COMMA = 44, LT_SEMI = 45, LT_AA = 46, LT_NL = 52,
-       LT_UNAL = 53, LT_STAR = 72, LT_CARET = 73, LT_OPS = 74, LT_BASES = 83 };
-enum { SK_LIT = 0, SK_NUM, SK_NEG, SK_NAME, SK_RNAME, SK_SEQ, SK_QUAL, SK_CIG, SK_MD };
 struct af_finw_t {
     uint8_t line[AFS_LINE];
     uint8_t seq[AF_MAX_READ];            // the read in alignment orientation (ASCII, kpbseq.h:120-137 complement)
@@ -2925,18 +2923,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6)))
 // (aligner_ksw2.hpp:3049-3108), lift it (:3133-3160), MAPQ (mapq.hpp:146-184), and the MD / NM walks (sam.hpp:249-287), which were 64 columns wide but a
 // few items long - is ONE LANE's work per read here: 64 reads per wavefront, 1 / 64 of the wavefront instructions (finish_wave_kernel issued ~3500 per
 // read, 63 of 64 lanes idle in two thirds of them: profiles/r04t).  The lane leaves a "recipe" in HBM (AFP_WORDS words per read: header numbers, the
-// alternatives, the stitched and the lifted CIGAR, the MD items).  finish_render_kernel, one wavefront per read, stages the recipe, lays the line's segments
-// out BY ALL LANES (a segment's kind and length follow from its index; offsets by a wavefront scan - finish_wave_kernel's lane 0 listed them one by one) and
-// renders and stores the bytes as before.  Same bytes, same records, same hand-overs to the host pipeline.
+// alternatives, the stitched and the lifted CIGAR, the MD items).  finish_render_kernel, one wavefront per read, lays the line's segments
+// out BY ALL LANES (a segment's kind and length follow from its index; offsets by a wavefront scan - finish_wave_kernel's lane 0 listed them one by one),
+// has every piece of the line written by the lanes that own it (render_core.h) and stores the bytes as before.  Same bytes, same records, same hand-overs
+// to the host pipeline.
 // ------------------------------------------------------------------------------------------------------------------------------
 #define AFP_WORDS 512u
-#define AFP_ALT 16u              // 3 words per alternative: sequence, 1-based position, score
 #define AFP_CIG 64u
 #define AFP_LCIG 128u
 #define AFP_MD 256u
-enum { AFP_F_ALIGNED = 1u, AFP_F_MAPPED = 2u, AFP_F_STRAND = 4u, AFP_F_HOST = 8u };
-enum { AFP_H_FLAGS = 0, AFP_H_NCIG, AFP_H_NMD, AFP_H_NM, AFP_H_LIFTNM, AFP_H_MAPQ, AFP_H_SCORE, AFP_H_SCORE2, AFP_H_POS1, AFP_H_OAPOS, AFP_H_SIDS, AFP_H_LIFTED_LO, AFP_H_LIFTED_HI,
-       AFP_H_POS_LO, AFP_H_POS_HI, AFP_H_N };
+// (the header words AFP_H_*, the flags AFP_F_* and AFP_ALT: render_core.h)
 static_assert(AFP_H_N <= AFP_ALT && AFP_ALT + 3 * AF_MAX_CAND <= AFP_CIG && AFP_CIG + AFS_CIG <= AFP_LCIG && AFP_LCIG + AFS_LCIG <= AFP_MD && AFP_MD + AFS_MAXMD <= AFP_WORDS, "recipe layout");
 
 // a sequence of bytes read front to back by one lane, eight per load (af_bytes_t; element e = byte start + e, or start - e)
@@ -3173,37 +3169,34 @@ __global__ void __launch_bounds__(64) finish_prep_kernel(const af_args_t G, uint
 #endif
 }
 
-#define AFR_MAXSEG 136u          // 35 fixed segments + 6 per alternative + the newline
 struct af_finr_t {
     uint8_t line[AFS_LINE];
-    uint8_t seq[AF_MAX_READ];
-    uint32_t hdr[AFP_CIG];               // the recipe's header and alternatives
-    uint32_t cig[AFS_CIG], lcig[AFS_LCIG];
-    uint32_t md_item[AFS_MAXMD];
-    uint16_t md_off[AFS_MAXMD + 1], cig_off[AFS_CIG + 1], lcig_off[AFS_LCIG + 1];
+    uint8_t lit[96];                     // afs_lit (kernel lifetime)
     uint8_t names[AFW_NAMES]; uint16_t name_off[AFW_NSEQ + 2];
-    uint16_t seg_off[AFR_MAXSEG + 1]; uint8_t seg_kind[AFR_MAXSEG]; uint32_t seg_val[AFR_MAXSEG];
 };
-// exclusive prefix sums of len[0 .. n) over the wavefront, 64 at a time: off[k] = sum of the lengths before k, off[n] = the total (returned).  len(k) is evaluated by lane k & 63.
-template <class LenF>
-__device__ __forceinline__ uint32_t afr_scan(uint32_t n, uint16_t* off, LenF len) {
-    const int lane = threadIdx.x;
-    uint32_t base = 0;
-    for (uint32_t k0 = 0; k0 < n; k0 += 64) {
-        const uint32_t k = k0 + lane;
-        const uint32_t mine = k < n ? len(k) : 0u;
-        uint32_t inc = mine;
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t x = (uint32_t)__shfl_up((int)inc, o); if (lane >= o) inc += x; }
-        if (k < n) off[k] = (uint16_t)(base + inc - mine < 0xFFFFu ? base + inc - mine : 0xFFFFu);
-        base += (uint32_t)__shfl((int)inc, 63);
-    }
-    if (lane == 0) off[n] = (uint16_t)(base < 0xFFFFu ? base : 0xFFFFu);
-    return base;
+static_assert(AFR_LIT_BYTES <= 96 && AFS_LINE % 8 == 0 && AFS_LINE == AFR_LINE_BYTES, "render staging");
+static __device__ const uint32_t afr_tab[AFR_NFIX] = AFR_TAB_INIT;
+// inclusive prefix sums over the wavefront in six DPP additions (rows of 16 by row_shr, a lane without a source adds 0; then row_bcast:15 and row_bcast:31 carry the rows' totals on); all 64 lanes active
+__device__ __forceinline__ uint32_t afr_wave_scan(uint32_t x) {
+    int v = (int)x;
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111 /* row_shr:1 */, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112 /* row_shr:2 */, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114 /* row_shr:4 */, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118 /* row_shr:8 */, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142 /* row_bcast:15 */, 0xA, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143 /* row_bcast:31 */, 0xC, 0xF, false);
+    return (uint32_t)v;
 }
+__device__ __forceinline__ uint32_t afr_lane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }      // lane l's value, in a scalar register
 
+// One wavefront per read.  Lane j holds word j of the recipe (header and alternatives); what the whole wavefront needs of it is read from that lane into scalar
+// registers.  The line is laid out with lane i as segment i (render_core.h): length by a table lookup and a few selects, offset by one scan.  Then every short
+// segment - a literal, a number, an alternative's sequence name - is written by its lane, and the long ones by all lanes together, one after the other: the read's
+// name, the two sequence names of the skeleton, SEQ and QUAL straight from HBM into the line, the CIGARs one operation per lane and MD one item per lane, each at the offset its own scan gave it.  No byte of the line
+// is searched for.  Lists longer than a wavefront (n_lcig <= 128, n_md <= 256, more than 4 alternatives) take the same steps 64 at a time.
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) finish_render_kernel(const af_args_t G, const uint32_t* __restrict__ recipes) {
     __shared__ af_finr_t L;
-    const int lane = threadIdx.x;
+    const uint32_t lane = threadIdx.x;
     const ak_args_t& A = G.A;
     const ak_fmt_t& F = A.fmt;
     const uint32_t n_seq = (uint32_t)A.P.n_seq;
@@ -3212,167 +3205,133 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6)))
         for (uint32_t k = lane; k <= n_seq; k += 64) L.name_off[k] = (uint16_t)F.sname_off[k];
         for (uint32_t k = lane; k < F.sname_off[n_seq]; k += 64) L.names[k] = F.snames[k];
     }
-#define NAME_LEN(sid) (names_lds ? (uint32_t)(L.name_off[(sid) + 1] - L.name_off[sid]) : F.sname_off[(sid) + 1] - F.sname_off[sid])
+    for (uint32_t k = lane; k < AFR_LIT_BYTES; k += 64) L.lit[k] = (uint8_t)afs_lit[k];
+    const char* const lit = reinterpret_cast<const char*>(L.lit);
+    const uint32_t ent = lane < AFR_NFIX ? afr_tab[lane] : 0u;          // lane i is segment i of every aligned line
+    const uint64_t ent_lit = afr_lit8(afs_lit, (ent >> 8) & 0xFFu, (ent >> 16) & 0xFu);
+    const uint32_t has_q = F.quals ? 1u : 0u;
+    auto name_len = [&](uint32_t sid) { return names_lds ? (uint32_t)(L.name_off[sid + 1] - L.name_off[sid]) : (uint32_t)(F.sname_off[sid + 1] - F.sname_off[sid]); };
+    auto put_seg = [&](uint32_t at, const afr_seg_t& s, bool names) {          // a segment that is its lane's own (names: an alternative's sequence name too)
+        uint8_t* const dst = L.line + at;
+        if (s.kind == SK_LIT) afr_put_lit(dst, s.lit, s.len);
+        else if (s.kind == SK_NUM || s.kind == SK_NEG) afr_put_num(dst, s.kind, s.val, s.len);
+        else if (names && s.kind == SK_NAME) {
+            if (names_lds) { const uint8_t* src = L.names + L.name_off[s.val];
+                _Pragma("unroll 1") for (uint32_t d = 0; d < s.len; ++d) dst[d] = src[d]; }
+            else { const uint64_t src = F.sname_off[s.val];
+                _Pragma("unroll 1") for (uint32_t d = 0; d < s.len; ++d) dst[d] = (uint8_t)F.snames[src + d]; }
+        }
+    };
+    auto put_name = [&](uint32_t at, uint32_t sid, uint32_t len) {          // a sequence name of the skeleton, by all lanes
+        if (names_lds) { const uint32_t src = L.name_off[sid]; _Pragma("unroll 1") for (uint32_t k = lane; k < len; k += 64) L.line[at + k] = L.names[src + k]; }
+        else { const uint64_t src = F.sname_off[sid]; _Pragma("unroll 1") for (uint32_t k = lane; k < len; k += 64) L.line[at + k] = (uint8_t)F.snames[src + k]; }
+    };
     // a read's status and the recipe's first words come with one round trip, the next read's while this one is rendered
     uint32_t st_n = AF_ST_FALLBACK, hw_n = 0;
     if (blockIdx.x < A.n_reads) { st_n = G.plans[blockIdx.x].status; hw_n = recipes[(size_t)blockIdx.x * AFP_WORDS + lane]; }
     for (uint64_t r_in = blockIdx.x; r_in < A.n_reads; r_in += gridDim.x) {
-        const uint32_t st = st_n, hw = hw_n;
+        const uint32_t st = (uint32_t)__builtin_amdgcn_readfirstlane((int)st_n), hw = hw_n;
         if (r_in + gridDim.x < A.n_reads) { st_n = G.plans[r_in + gridDim.x].status; hw_n = recipes[(size_t)(r_in + gridDim.x) * AFP_WORDS + lane]; }
         if (st == AF_ST_FALLBACK) continue;
         const uint32_t* __restrict__ S = recipes + (size_t)r_in * AFP_WORDS;
-        __syncthreads();
-        L.hdr[lane] = hw;
-        __syncthreads();
-        const uint32_t flags = L.hdr[AFP_H_FLAGS];
+        const uint32_t flags = afr_lane(hw, AFP_H_FLAGS);
         const bool aligned = (flags & AFP_F_ALIGNED) != 0 && st == AF_ST_FINAL;
-        const bool mapped = (flags & AFP_F_MAPPED) != 0;
         const uint32_t strand = aligned && (flags & AFP_F_STRAND) ? 1u : 0u;
-        const uint32_t n_alt = aligned ? (flags >> 8) & 0xFFu : 0u;
-        const uint32_t n_cig = aligned ? L.hdr[AFP_H_NCIG] & 0xFFFFu : 0u, n_lcig = aligned ? L.hdr[AFP_H_NCIG] >> 16 : 0u, n_md = aligned ? L.hdr[AFP_H_NMD] : 0u;
         const uint64_t r = A.read_lo + r_in;
         const uint64_t off = A.offs[r];
         const uint32_t m = (uint32_t)(A.offs[r + 1] - off);
-        const uint64_t lifted = (uint64_t)L.hdr[AFP_H_LIFTED_LO] | ((uint64_t)L.hdr[AFP_H_LIFTED_HI] << 32);
-        const uint64_t aln_pos = aligned ? (uint64_t)L.hdr[AFP_H_POS_LO] | ((uint64_t)L.hdr[AFP_H_POS_HI] << 32) : 0ull;
-        const int32_t score = aligned ? (int32_t)L.hdr[AFP_H_SCORE] : 0, score2 = aligned ? (int32_t)L.hdr[AFP_H_SCORE2] : 0;
         bool to_host = (aligned && (flags & AFP_F_HOST)) || m > AF_MAX_READ;
         if (aligned && (flags & AFP_F_HOST) && lane == 0) atomicAdd(&G.ctr[AFC_WHY + AF_WHY_CIGAR], 1u);
-        // ---- the CIGARs, the MD items and the read in alignment orientation ----
-        if (!to_host) {
-            for (uint32_t k = lane; k < n_cig; k += 64) L.cig[k] = S[AFP_CIG + k];
-            for (uint32_t k = lane; k < n_lcig; k += 64) L.lcig[k] = S[AFP_LCIG + k];
-            for (uint32_t k = lane; k < n_md; k += 64) L.md_item[k] = S[AFP_MD + k];
-            for (uint32_t k = lane; k < m; k += 64) L.seq[k] = strand ? ak_compl(A.D.reads[off + m - 1 - k]) : A.D.reads[off + k];
-        }
-        __syncthreads();
         moni_aln_rec_t rec;
-        rec.status = aligned ? 1u : 0u; rec.strand = strand; rec.ref_pos = aln_pos; rec.score = score; rec.score2 = score2;
+        rec.status = aligned ? 1u : 0u; rec.strand = strand;
+        rec.ref_pos = aligned ? (uint64_t)afr_lane(hw, AFP_H_POS_LO) | ((uint64_t)afr_lane(hw, AFP_H_POS_HI) << 32) : 0ull;
+        rec.score = aligned ? (int32_t)afr_lane(hw, AFP_H_SCORE) : 0; rec.score2 = aligned ? (int32_t)afr_lane(hw, AFP_H_SCORE2) : 0;
         rec.n_cigar = 0; rec.n_alt = 0; rec.cigar_off = 0; rec.alt_off = 0; rec.nm = 0; rec.md_len = 0; rec.md_off = 0; rec.txt_len = 0; rec.lift_nm = 0; rec.txt_off = 0;
         uint32_t p = 0;
-        const uint64_t n0 = F.rname_off[r], n1 = F.rname_off[r + 1];
-        if (!to_host) {
-            const int nm = (int)L.hdr[AFP_H_NM], lift_nm = (int)L.hdr[AFP_H_LIFTNM], mapq = (int)L.hdr[AFP_H_MAPQ], pos1 = (int)L.hdr[AFP_H_POS1], oa_pos = (int)L.hdr[AFP_H_OAPOS];
-            const uint32_t sid = L.hdr[AFP_H_SIDS] & 0xFFFFu, lsid = L.hdr[AFP_H_SIDS] >> 16;
-            // ---- where the texts of the CIGAR operations and of the MD items start ----
-            uint32_t w_lcig = 0, w_cig = 0, w_md = 0;
-            if (aligned) {
-                w_lcig = afr_scan(n_lcig, L.lcig_off, [&](uint32_t k) { return afs_ndig(L.lcig[k] >> 4) + 1u; });
-                w_cig = afr_scan(n_cig, L.cig_off, [&](uint32_t k) { return afs_ndig(L.cig[k] >> 4) + 1u; });
-                w_md = afr_scan(n_md, L.md_off, [&](uint32_t k) { const uint32_t it = L.md_item[k], ty = it & 3u; return afs_ndig((it >> 2) & 0x3FFu) + (ty == 1 ? 1u : ty == 2 ? 1u + ((it >> 12) & 0x1FFu) : 0u); });
+        const uint64_t n0 = F.rname_off[r];
+        const uint32_t rn = (uint32_t)(F.rname_off[r + 1] - n0);
+        __syncthreads();          // the line before this one has left L.line
+        if (!to_host && !aligned) {
+            // ---- an unaligned record: the name, 19 literal bytes, SEQ, a tab, QUAL or "*", the newline ----
+            const uint32_t s_at = rn + 19u, q_at = s_at + m + 1u;
+            p = q_at + (has_q ? m : 1u) + 1u;
+            if (afr_fits(p)) {
+                if (lane < 19u) L.line[rn + lane] = (uint8_t)lit[LT_UNAL + lane];
+                if (lane == 19u) L.line[s_at + m] = '\t';
+                if (lane == 20u && !has_q) L.line[q_at] = '*';
+                if (lane == 21u) L.line[p - 1u] = '\n';
+                _Pragma("unroll 1") for (uint32_t k = lane; k < m; k += 64) L.line[s_at + k] = A.D.reads[off + k];
+                if (has_q) { _Pragma("unroll 1") for (uint32_t k = lane; k < m; k += 64) L.line[q_at + k] = F.quals[off + k]; }
             }
-            // ---- the segments of the line (sam.hpp:144-188): segment i's kind, value and length from i alone, its offset by a scan ----
-            const uint32_t n_seg = aligned ? 36u + 6u * n_alt : 6u;
-            const uint32_t has_q = F.quals ? 1u : 0u;
-            auto seg = [&](uint32_t i, uint32_t& kind, uint32_t& val) -> uint32_t {
-                auto lit = [&](uint32_t at, uint32_t len) { kind = SK_LIT; val = at; return len; };
-                auto num = [&](int v) { if (v < 0) { const uint32_t u = 0u - (uint32_t)v; kind = SK_NEG; val = u; return afs_ndig(u) + 1u; } kind = SK_NUM; val = (uint32_t)v; return afs_ndig((uint32_t)v); };
-                if (!aligned) {
-                    switch (i) {
-                    case 0: kind = SK_RNAME; val = 0; return (uint32_t)(n1 - n0);
-                    case 1: return lit(LT_UNAL, 19);
-                    case 2: kind = SK_SEQ; val = 0; return m;
-                    case 3: return lit(LT_TAB, 1);
-                    case 4: if (has_q) { kind = SK_QUAL; val = 0; return m; } return lit(LT_STAR, 1);
-                    default: return lit(LT_NL, 1);
-                    }
-                }
-                if (i >= 35u && i < 35u + 6u * n_alt) {
-                    const uint32_t k = (i - 35u) / 6u, x = (i - 35u) % 6u;
-                    const uint32_t s2 = L.hdr[AFP_ALT + 3 * k];
-                    switch (x) {
-                    case 0: kind = SK_NAME; val = s2; return NAME_LEN(s2);
-                    case 1: return lit(LT_COMMA, 1);
-                    case 2: return num((int)L.hdr[AFP_ALT + 3 * k + 1]);
-                    case 3: return lit(LT_COMMA, 1);
-                    case 4: return num((int)L.hdr[AFP_ALT + 3 * k + 2]);
-                    default: return lit(LT_SEMI, 1);
-                    }
-                }
-                if (i >= 35u) return lit(LT_NL, 1);
-                switch (i) {
-                case 0: kind = SK_RNAME; val = 0; return (uint32_t)(n1 - n0);
-                case 1: return lit(LT_TAB, 1);
-                case 2: return num(strand ? 16 : 0);
-                case 3: return lit(LT_TAB, 1);
-                case 4: if (mapped) { kind = SK_NAME; val = lsid; return NAME_LEN(lsid); } return lit(LT_STAR, 1);
-                case 5: return lit(LT_TAB, 1);
-                case 6: return num(mapped ? pos1 : 0);
-                case 7: return lit(LT_TAB, 1);
-                case 8: return num(mapq);
-                case 9: return lit(LT_TAB, 1);
-                case 10: if (mapped) { kind = SK_CIG; val = 0u | (n_lcig << 1); return w_lcig; } return lit(LT_STAR, 1);
-                case 11: return lit(LT_MATE, 7);
-                case 12: kind = SK_SEQ; val = 0; return m;
-                case 13: return lit(LT_TAB, 1);
-                case 14: if (has_q) { kind = SK_QUAL; val = 0; return m; } return lit(LT_STAR, 1);
-                case 15: return lit(LT_AS, 6);
-                case 16: return num(score);
-                case 17: return lit(LT_NM, 6);
-                case 18: return num(mapped ? nm : 0);
-                case 19: return score2 != 0 ? lit(LT_ZS, 6) : lit(LT_ZS, 0);
-                case 20: if (score2 != 0) return num(score2); return lit(LT_ZS, 0);
-                case 21: return lit(LT_MD, 6);
-                case 22: kind = SK_MD; val = n_md; return w_md;
-                case 23: return lit(LT_OA, 6);
-                case 24: kind = SK_NAME; val = sid; return NAME_LEN(sid);
-                case 25: return lit(LT_COMMA, 1);
-                case 26: return num(oa_pos);
-                case 27: return lit(strand ? LT_MINUS : LT_PLUS, 3);
-                case 28: kind = SK_CIG; val = 1u | (n_cig << 1); return w_cig;
-                case 29: return lit(LT_COMMA, 1);
-                case 30: return num(mapq);
-                case 31: return lit(LT_COMMA, 1);
-                case 32: return num(lift_nm);
-                case 33: return lit(LT_SEMI, 1);
-                default: return lit(LT_AA, 6);          // 34
-                }
+        }
+        else if (!to_host) {
+            const uint32_t n_alt = (flags >> 8) & 0xFFu, n_seg = 36u + 6u * n_alt, ncw = afr_lane(hw, AFP_H_NCIG);
+            const uint32_t n_cig = min(ncw & 0xFFFFu, (uint32_t)AFS_CIG), n_lcig = min(ncw >> 16, (uint32_t)AFS_LCIG), n_md = min(afr_lane(hw, AFP_H_NMD), (uint32_t)AFS_MAXMD);
+            afr_read_t R;
+            R.mapped = (flags & AFP_F_MAPPED) ? 1u : 0u; R.strand = strand; R.has_q = has_q; R.has_zs = rec.score2 != 0 ? 1u : 0u; R.rname_len = rn; R.m = m;
+            // ---- the CIGAR operations and the MD items, one per lane: the widths of their texts, and where each starts ----
+            const uint32_t c_it = lane < n_cig ? S[AFP_CIG + lane] : 0u, l_it = lane < n_lcig ? S[AFP_LCIG + lane] : 0u, d_it = lane < n_md ? S[AFP_MD + lane] : 0u;
+            const uint32_t c_len = lane < n_cig ? afr_cig_len(c_it) : 0u, l_len = lane < n_lcig ? afr_cig_len(l_it) : 0u, d_len = lane < n_md ? afr_md_len(d_it) : 0u;
+            const uint32_t c_inc = afr_wave_scan(c_len), l_inc = afr_wave_scan(l_len), d_inc = afr_wave_scan(d_len);
+            R.w_cig = afr_lane(c_inc, 63); R.w_lcig = afr_lane(l_inc, 63); R.w_md = afr_lane(d_inc, 63);
+            for (uint32_t k0 = 64; k0 < n_lcig; k0 += 64) R.w_lcig += afr_lane(afr_wave_scan(k0 + lane < n_lcig ? afr_cig_len(S[AFP_LCIG + k0 + lane]) : 0u), 63);
+            for (uint32_t k0 = 64; k0 < n_md; k0 += 64) R.w_md += afr_lane(afr_wave_scan(k0 + lane < n_md ? afr_md_len(S[AFP_MD + k0 + lane]) : 0u), 63);
+            // ---- the segments of the line (sam.hpp:144-188): lane i has segment i; beyond the wavefront there are only alternatives ----
+            auto alt_seg = [&](uint32_t i) {
+                afr_seg_t s = afr_alt_seg(i, n_alt, (uint32_t)__shfl((int)hw, (int)(afr_alt_word(i) & 63u)));
+                if (s.kind == SK_NAME) s.len = name_len(s.val);
+                return s;
             };
-            p = afr_scan(n_seg, L.seg_off, [&](uint32_t i) { uint32_t kind = 0, val = 0; const uint32_t len = seg(i, kind, val); L.seg_kind[i] = (uint8_t)kind; L.seg_val[i] = val; return len; });
-            __syncthreads();
-            if (p > AFS_LINE) { to_host = true; if (lane == 0) atomicAdd(&G.ctr[AFC_WHY + AF_WHY_CAPACITY], 1u); }
-            if (!to_host) {
-                // ---- SEQ and QUAL are plain copies; every lane renders its share of the other bytes of the line ----
-                const uint32_t s_at = L.seg_off[aligned ? 12 : 2], q_at = has_q ? (uint32_t)L.seg_off[aligned ? 14 : 4] : ~0u, holes = m + (q_at != ~0u ? m : 0u);
-                if (s_at + m <= AFS_LINE) for (uint32_t k = lane; k < m; k += 64) L.line[s_at + k] = L.seq[k];
-                if (q_at != ~0u && q_at + m <= AFS_LINE) for (uint32_t k = lane; k < m; k += 64) L.line[q_at + k] = F.quals[strand ? off + m - 1 - k : off + k];
-                for (uint32_t i = lane; i + holes < p; i += 64) {
-                    uint32_t b = i;
-                    if (b >= s_at) b += m;
-                    if (q_at != ~0u && b >= q_at) b += m;
-                    uint32_t lo = 0, hi = n_seg;                       // last segment that starts at or before b (an empty segment shares its offset with the next: never the last such)
-                    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if ((uint32_t)L.seg_off[mid] <= b) lo = mid; else hi = mid; }
-                    const uint32_t d = b - L.seg_off[lo], kind = L.seg_kind[lo], val = L.seg_val[lo];
-                    uint8_t ch;
-                    if (kind == SK_LIT) ch = (uint8_t)afs_lit[val + d];
-                    else if (kind == SK_NUM || kind == SK_NEG) {
-                        const uint32_t len = (uint32_t)L.seg_off[lo + 1] - L.seg_off[lo];
-                        if (kind == SK_NEG && d == 0) ch = '-';
-                        else { uint32_t u = val; for (uint32_t t = d + 1; t < len; ++t) u /= 10u; ch = (uint8_t)('0' + u % 10u); }
-                    }
-                    else if (kind == SK_SEQ) ch = L.seq[d];
-                    else if (kind == SK_QUAL) ch = F.quals[strand ? off + m - 1 - d : off + d];
-                    else if (kind == SK_NAME) ch = names_lds ? L.names[L.name_off[val] + d] : F.snames[F.sname_off[val] + d];
-                    else if (kind == SK_RNAME) ch = F.rnames[n0 + d];
-                    else if (kind == SK_CIG) {          // operation k of a CIGAR: its length, then its letter
-                        const uint16_t* offs = (val & 1u) ? L.cig_off : L.lcig_off; const uint32_t* cg = (val & 1u) ? L.cig : L.lcig;
-                        uint32_t a = 0, z = val >> 1;
-                        while (z - a > 1) { const uint32_t mid = (a + z) >> 1; if ((uint32_t)offs[mid] <= d) a = mid; else z = mid; }
-                        const uint32_t e = d - offs[a], nd = (uint32_t)offs[a + 1] - offs[a] - 1u;
-                        if (e == nd) ch = (uint8_t)afs_lit[LT_OPS + (cg[a] & 0xfu)];
-                        else { uint32_t u = cg[a] >> 4; for (uint32_t t = e + 1; t < nd; ++t) u /= 10u; ch = (uint8_t)('0' + u % 10u); }
-                    } else {                            // SK_MD: item k of the MD string: the count of matches, then the base or ^ and the deleted bases
-                        uint32_t a = 0, z = val;
-                        while (z - a > 1) { const uint32_t mid = (a + z) >> 1; if ((uint32_t)L.md_off[mid] <= d) a = mid; else z = mid; }
-                        const uint32_t it = L.md_item[a], ty = it & 3u, run = (it >> 2) & 0x3FFu, e = d - L.md_off[a], nd = afs_ndig(run);
-                        if (e < nd) { uint32_t u = run; for (uint32_t t = e + 1; t < nd; ++t) u /= 10u; ch = (uint8_t)('0' + u % 10u); }
-                        else if (ty == 1) { const uint32_t bc = (it >> 12) & 7u; ch = (uint8_t)afs_lit[LT_BASES + (bc > 4 ? 4 : bc)]; }
-                        else if (e == nd) ch = '^';
-                        else { const uint64_t ta = lifted + (it >> 21) + (e - nd - 1u); ch = (uint8_t)afs_lit[LT_BASES + dp_nt4(ta < A.D.n_text ? A.D.text[ta] : 0u)]; }
-                    }
-                    L.line[b] = ch;
-                }
+            afr_seg_t sg;
+            {
+                const uint32_t raw = (uint32_t)__shfl((int)hw, (int)(lane < AFR_NFIX ? (ent >> 4) & 0xFu : afr_alt_word(lane)));
+                if (lane < AFR_NFIX) sg = afr_fixed_seg(ent, ent_lit, raw, R); else sg = afr_alt_seg(lane, n_alt, raw);
+                if (sg.kind == SK_NAME) sg.len = name_len(sg.val);
             }
+            const uint32_t inc = afr_wave_scan(sg.len), at = inc - sg.len;
+            p = afr_lane(inc, 63);
+            for (uint32_t i0 = 64; i0 < n_seg; i0 += 64) p += afr_lane(afr_wave_scan(alt_seg(i0 + lane).len), 63);
+            if (afr_fits(p)) {
+                // ---- literals, numbers and sequence names by the lanes that own them ----
+                uint32_t base = 0;
+                for (uint32_t i0 = 0; i0 < n_seg; i0 += 64) {
+                    afr_seg_t s = sg; uint32_t in2 = inc;
+                    if (i0) { s = alt_seg(i0 + lane); in2 = afr_wave_scan(s.len); }
+                    put_seg(base + in2 - s.len, s, i0 != 0 || lane >= AFR_NFIX);
+                    base += afr_lane(in2, 63);
+                }
+                // ---- the long segments by all lanes: the two sequence names, the CIGARs and MD (an operation or an item per lane), SEQ and QUAL ----
+                const uint32_t sids = afr_lane(hw, AFP_H_SIDS);
+                if (R.mapped) put_name(afr_lane(at, AFR_SEG_REF), sids >> 16, afr_lane(sg.len, AFR_SEG_REF));
+                put_name(afr_lane(at, AFR_SEG_OA), sids & 0xFFFFu, afr_lane(sg.len, AFR_SEG_OA));
+                const uint32_t lc_at = afr_lane(at, AFR_SEG_LCIG), s_at = afr_lane(at, AFR_SEG_SEQ), q_at = afr_lane(at, AFR_SEG_QUAL), md_at = afr_lane(at, AFR_SEG_MD), c_at = afr_lane(at, AFR_SEG_CIG);
+                if (lane < n_cig) afr_put_cig(L.line + c_at + c_inc - c_len, c_it, lit);
+                uint32_t b = lc_at;
+                for (uint32_t k0 = 0; k0 < (R.mapped ? n_lcig : 0u); k0 += 64) {
+                    const bool on = k0 + lane < n_lcig;
+                    uint32_t it = l_it, len = l_len, in2 = l_inc;
+                    if (k0) { it = on ? S[AFP_LCIG + k0 + lane] : 0u; len = on ? afr_cig_len(it) : 0u; in2 = afr_wave_scan(len); }
+                    if (on) afr_put_cig(L.line + b + in2 - len, it, lit);
+                    b += afr_lane(in2, 63);
+                }
+                const uint64_t lifted = (uint64_t)afr_lane(hw, AFP_H_LIFTED_LO) | ((uint64_t)afr_lane(hw, AFP_H_LIFTED_HI) << 32);
+                auto base_at = [&](uint32_t o) { const uint64_t ta = lifted + o; return dp_nt4(ta < A.D.n_text ? A.D.text[ta] : 0u); };      // a deleted base comes from the text, not from the read
+                b = md_at;
+                for (uint32_t k0 = 0; k0 < n_md; k0 += 64) {
+                    const bool on = k0 + lane < n_md;
+                    uint32_t it = d_it, len = d_len, in2 = d_inc;
+                    if (k0) { it = on ? S[AFP_MD + k0 + lane] : 0u; len = on ? afr_md_len(it) : 0u; in2 = afr_wave_scan(len); }
+                    if (on) afr_put_md(L.line + b + in2 - len, it, lit, base_at);
+                    b += afr_lane(in2, 63);
+                }
+                if (strand) { _Pragma("unroll 2") for (uint32_t k = lane; k < m; k += 64) L.line[s_at + k] = ak_compl(A.D.reads[off + m - 1 - k]); }
+                else { _Pragma("unroll 2") for (uint32_t k = lane; k < m; k += 64) L.line[s_at + k] = A.D.reads[off + k]; }
+                if (has_q) { _Pragma("unroll 2") for (uint32_t k = lane; k < m; k += 64) L.line[q_at + k] = F.quals[strand ? off + m - 1 - k : off + k]; }
+            }
+        }
+        if (!to_host) {
+            if (!afr_fits(p)) { to_host = true; if (lane == 0) atomicAdd(&G.ctr[AFC_WHY + AF_WHY_CAPACITY], 1u); }
+            else { _Pragma("unroll 1") for (uint32_t k = lane; k < rn; k += 64) L.line[k] = (uint8_t)F.rnames[n0 + k]; }
         }
         __syncthreads();
         // ---- out: the text pool (8-byte words, bump-allocated), coalesced; the record ----
@@ -3400,7 +3359,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6)))
             }
         }
     }
-#undef NAME_LEN
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
