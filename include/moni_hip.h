@@ -158,6 +158,31 @@ int moni_ms_query_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, uint64_
  * lengths of every read as given (forward strand), pointers[offsets[i] - offsets[0] + k] / lengths[...] for read offset k. */
 int moni_ms_lengths_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, uint64_t *pointers, uint64_t *lengths);
 
+/* The same for patterns of genome length (a chromosome, an assembly): every pattern is cut into segments that are walked side by side, each
+ * from `overlap` bases to the right of its end, the match lengths measured at the pointers tell which segments the cut cannot have touched,
+ * and the others are walked once more, a run of neighbours by one lane, from the state of the accepted segment behind them (csrc/mslong_core.h,
+ * DESIGN.md 7.7).  Output layout of moni_ms_lengths_batch; either output pointer may be NULL, not both.
+ *   lengths  - the matching statistics: identical to moni_ms_lengths_batch's and to the reference's.
+ *   pointers - valid (the text at pointers[k] agrees with the pattern over lengths[k] bases) but, where a pattern was cut, not necessarily the
+ *              positions moni_ms_lengths_batch reports: any position with a maximal match qualifies.  With seg_len >= the longest pattern nothing
+ *              is cut and they are identical too.
+ * Device memory: the bytes, 8 bytes of pointer and 4 of length per base, 48 bytes per segment.  A pattern may have up to 2^32 - 1 bases
+ * (MONI_ERANGE beyond); batch totals are 64-bit.  MONI_EINVAL: seg_len < 8, a non-zero reserved word, a NULL ctx / batch / params, both outputs
+ * NULL.  An empty batch and empty patterns give MONI_OK.  The call replaces the resident batch by one no other entry point can run on
+ * (moni_reads_upload again first).  seg_len is taken down to a multiple of 8 and a pattern's first segment shortened so that the later ones begin
+ * at a multiple of 8 of the output index; a pattern of at most seg_len bases is one segment.  moni_last_kernel_ms(ctx, 0, ..) then gives the
+ * speculative walk's time, (ctx, 1, ..) the length pass's, (ctx, 2, ..) the chain round's. */
+typedef struct { uint32_t seg_len;   /* bases per segment, >= 8; default 4096 */
+                 uint32_t overlap;   /* bases walked beyond a segment's end before it, >= 0; default 256 */
+                 uint32_t reserved[2]; } moni_mslong_params_t;
+typedef struct { uint64_t patterns, bases, segments, flagged, chain_runs;
+                 uint64_t steps_spec, steps_chain, jumps;      /* LF steps of rounds 1 and 3, threshold jumps of both */
+                 double t_walk, t_len, t_chain, t_total;       /* seconds, HIP events, transfers excluded except in t_total */
+               } moni_mslong_stats_t;
+void moni_mslong_params_default(moni_mslong_params_t *p);
+int  moni_ms_long_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const moni_mslong_params_t *prm,
+                        uint64_t *pointers, uint64_t *lengths, moni_mslong_stats_t *stats);
+
 /* ---- seeds: seed_finder::find_mems + populate_seeds (seed_finder.hpp:126-166, 258-318) ----- */
 /* Device-only run (ms + mems + occurrences) over the resident batch. */
 int moni_seed_run(moni_ctx_t *ctx, const moni_seed_params_t *prm);

@@ -32,6 +32,7 @@ EXPORTS = [
     "moni_pml_batch", "moni_pml_run", "moni_pml_fetch", "moni_pml_sizes",
     "moni_locate_params_default", "moni_locate_run", "moni_locate_sizes", "moni_locate_fetch", "moni_locate_batch",
     "moni_seqcount_params_default", "moni_seqcount_run", "moni_seqcount_sizes", "moni_seqcount_fetch", "moni_seqcount_batch",
+    "moni_mslong_params_default", "moni_ms_long_batch",
 ]
 
 
@@ -100,6 +101,16 @@ class LocateParamsC(C.Structure):
 
 class SeqcountParamsC(C.Structure):
     _fields_ = [("strands", C.c_uint32), ("reserved", C.c_uint32), ("max_walk", C.c_uint64)]
+
+
+class MslongParamsC(C.Structure):
+    _fields_ = [("seg_len", C.c_uint32), ("overlap", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class MslongStatsC(C.Structure):
+    _fields_ = [("patterns", C.c_uint64), ("bases", C.c_uint64), ("segments", C.c_uint64), ("flagged", C.c_uint64), ("chain_runs", C.c_uint64),
+                ("steps_spec", C.c_uint64), ("steps_chain", C.c_uint64), ("jumps", C.c_uint64),
+                ("t_walk", C.c_double), ("t_len", C.c_double), ("t_chain", C.c_double), ("t_total", C.c_double)]
 
 
 class DpParamsC(C.Structure):
@@ -213,6 +224,9 @@ def lib():
         L.moni_last_counters.argtypes = [C.c_void_p, C.c_void_p]
         L.moni_seed_occ_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.moni_ms_lengths_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.c_void_p, C.c_void_p]
+        L.moni_mslong_params_default.argtypes = [C.POINTER(MslongParamsC)]
+        L.moni_mslong_params_default.restype = None
+        L.moni_ms_long_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.POINTER(MslongParamsC), C.c_void_p, C.c_void_p, C.POINTER(MslongStatsC)]
         L.moni_report_mems_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AlignParamsC),
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_ldx_info.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
@@ -696,6 +710,26 @@ class Ctx:
         _chk(self._L.moni_ms_lengths_batch(self._h, C.byref(b), ptr.ctypes.data, ln.ctypes.data), "moni_ms_lengths_batch")
         self.n_reads = len(offsets) - 1
         return ptr, ln
+
+    def ms_long_batch(self, seq: np.ndarray, offsets: np.ndarray, seg_len: int = None, overlap: int = None, want_pointers: bool = True, want_lengths: bool = True):
+        """matching statistics of genome-length patterns (moni_ms_long_batch): (pointers or None, lengths or None, stats) in the layout of
+        ms_lengths_batch.  The lengths are identical to ms_lengths_batch's; the pointers are valid but may differ where a pattern was cut into
+        segments (seg_len >= the longest pattern: identical).  The call replaces the resident batch: upload() again before any *_run call."""
+        b, keep = self._batch(seq, offsets)
+        total = int(keep[1][-1] - keep[1][0])
+        p = MslongParamsC()
+        self._L.moni_mslong_params_default(C.byref(p))
+        if seg_len is not None:
+            p.seg_len = seg_len
+        if overlap is not None:
+            p.overlap = overlap
+        ptr = np.empty(total, dtype=np.uint64) if want_pointers else None
+        ln = np.empty(total, dtype=np.uint64) if want_lengths else None
+        st = MslongStatsC()
+        _chk(self._L.moni_ms_long_batch(self._h, C.byref(b), C.byref(p), ptr.ctypes.data if want_pointers else None, ln.ctypes.data if want_lengths else None, C.byref(st)),
+             "moni_ms_long_batch")
+        self.n_reads = 0
+        return ptr, ln, {f: getattr(st, f) for f, _ in MslongStatsC._fields_}
 
     def report_mems_batch(self, seq, offsets, names, name_off, quals=None, **overrides) -> bytes:
         b, keep = self._batch(seq, offsets)

@@ -9,6 +9,7 @@
 #include <unistd.h>
 #include <cstring>
 #include <atomic>
+#include <chrono>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -41,6 +42,7 @@
 #include "pml_kernels.hip"
 #include "locate_kernels.hip"
 #include "seqcount_kernels.hip"
+#include "mslong_kernels.hip"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "moni_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return MONI_ENODEV; } } while (0)
 
@@ -216,6 +218,11 @@ struct moni_ctx {
         uint64_t n_tasks = 0, n_segs = 0; uint32_t n_seq = 0; bool valid = false;
         void release() { lres.release(); res.release(); toe.release(); cnt.release(); off.release(); counts.release(); k_lo.release(); valid = false; }
     } sc;
+    struct MslBufs {        // matching statistics of long patterns (mslong_api.inc): pointers and lengths in pattern order, the segment table, the runs; grow-only
+        DBuf<uint64_t> ptr, cnt, seg_off, head, run_idx; DBuf<uint32_t> lens, flags; DBuf<mslong_seg_t> segs; DBuf<mslong_state_t> states; DBuf<mslong_run_t> runs;
+        DBuf<unsigned long long> counters;
+        void release() { ptr.release(); cnt.release(); seg_off.release(); head.release(); run_idx.release(); lens.release(); flags.release(); segs.release(); states.release(); runs.release(); counters.release(); }
+    } msl;
     int n_cu_cached = 0, pe_occ_cached = 0;          // hipGetDeviceProperties / the occupancy query take a millisecond each: asked once per context
 };
 
@@ -533,7 +540,7 @@ void moni_ctx_destroy(moni_ctx_t* c) {
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (auto e : c->ak_begin) (void)hipEventDestroy(e);
     for (auto e : c->ak_done) (void)hipEventDestroy(e);
-    c->ex.release(); c->pml.release(); c->loc.release(); c->sc.release();
+    c->ex.release(); c->pml.release(); c->loc.release(); c->sc.release(); c->msl.release();
     c->ak_recs.release(); c->ak_cig.release(); c->ak_alt.release(); c->ak_minscore.release(); c->pe.release();
     if (c->d_ak_cursors) (void)hipFree(c->d_ak_cursors);
     if (c->out_buf) (void)hipHostFree(c->out_buf);
@@ -1959,5 +1966,6 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "pml_api.inc"
 #include "locate_api.inc"
 #include "seqcount_api.inc"
+#include "mslong_api.inc"
 
 }  // extern "C"

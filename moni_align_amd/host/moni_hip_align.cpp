@@ -18,6 +18,10 @@
 // modes take the older path: a reader thread parses ahead into a bounded queue, two workers per GPU, a writer thread with a bounded
 // in-order window.  -m writes the report-MEMs records (aligner_ksw2.hpp:346-373);
 // --ms / --mems write the legacy `moni ms` / `moni mems` text outputs (src/matching_statistics.cpp:520-610, src/mems.cpp:520-600).
+// --ms / --mems --split [--seg-len N] [--overlap N] take patterns of genome length (a chromosome, an assembly) through moni_ms_long_batch: every pattern
+// is cut into segments of N bases that are walked side by side, and batches are sized by bases, not by reads.  .lengths and the (offset,length) pairs
+// of .mems are byte-identical to the run without --split; .pointers may differ where a pattern was cut - every pointer is a position of a maximal
+// match, but not necessarily the one the reference reports.
 // --extend writes the SAM file of the legacy `moni extend` (extender_ksw2.hpp, extend_reads_dispatcher.hpp:435-486; moni_extend_batch) - single-end
 // reads, the same path as -m; its @HD line has the tabs of moni_sam_header where the reference's extender writes blanks.
 // --pseudo-ms writes <out>.pseudo_lengths, the text of the legacy `moni pseudo-ms` (src/spumoni/run_spumoni.cpp:466-501; moni_pml_batch): per read a
@@ -189,6 +193,7 @@ struct Args {
     moni_align_params_t P;
     bool report_mems = false, csv = false, no_lcp = false, shaped_slp = false, secondary = false;
     bool legacy_ms = false, legacy_mems = false;      // --ms / --mems
+    bool split = false; uint32_t seg_len = 0, overlap = 0; bool seg_len_set = false, overlap_set = false;      // --ms / --mems --split [--seg-len N] [--overlap N]: long patterns, moni_ms_long_batch
     bool extend = false;                              // --extend: the legacy `moni extend` (longest MEM of each strand, extended to both sides)
     bool pseudo_ms = false;                           // --pseudo-ms: the legacy `moni pseudo-ms` (pseudo-matching lengths of every read)
     bool locate = false, both_strands = false;        // --locate [--both-strands]: exact-match count and locate of every pattern
@@ -217,6 +222,9 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--ctx-per-gpu") && i + 1 < argc) { a.ctx_per_gpu = std::max(1, atoi(argv[++i])); continue; }
         if (!strcmp(argv[i], "--ms")) { a.legacy_ms = true; continue; }
         if (!strcmp(argv[i], "--mems")) { a.legacy_mems = true; continue; }
+        if (!strcmp(argv[i], "--split")) { a.split = true; continue; }
+        if (!strcmp(argv[i], "--seg-len") && i + 1 < argc) { a.seg_len = (uint32_t)strtoul(argv[++i], nullptr, 10); a.seg_len_set = true; continue; }
+        if (!strcmp(argv[i], "--overlap") && i + 1 < argc) { a.overlap = (uint32_t)strtoul(argv[++i], nullptr, 10); a.overlap_set = true; continue; }
         if (!strcmp(argv[i], "--extend")) { a.extend = true; continue; }
         if (!strcmp(argv[i], "--pseudo-ms")) { a.pseudo_ms = true; continue; }
         if (!strcmp(argv[i], "--locate")) { a.locate = true; continue; }
@@ -228,7 +236,8 @@ static void parse(int argc, char** argv, Args& a) {
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems | --extend | --pseudo-ms | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands]]\n";
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands]]\n"
+                              "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n";
     int c;
     char* s;
     optind = 1;
@@ -740,6 +749,9 @@ int main(int argc, char** argv) {
     const bool paired = !a.mate1.empty() || !a.mate2.empty();
     if (paired && (a.mate1.empty() || a.mate2.empty())) die("paired-end alignment needs both -1 and -2");
     if (paired && (a.legacy_ms || a.legacy_mems)) die("--ms / --mems take single-end input (-p)");
+    if (a.split && !(a.legacy_ms || a.legacy_mems)) die("--split belongs to --ms / --mems");
+    if ((a.seg_len_set || a.overlap_set) && !a.split) die("--seg-len / --overlap belong to --split");
+    if (a.seg_len_set && a.seg_len < 8) die("--seg-len must be at least 8");
     if (a.pseudo_ms) {       // pseudo-matching lengths: single-end reads, one mode at a time
         if (paired) die("--pseudo-ms takes single-end input (-p), not -1 / -2");
         if (a.report_mems) die("--pseudo-ms cannot be combined with -m");
@@ -953,6 +965,7 @@ int main(int argc, char** argv) {
             // which take long patterns, close a batch when that product passes 2^28 entries (4 GB)
             size_t longest = 0;
             while (b->n() < batch_cap && next_record(*b)) {
+                if (a.split) { if (b->seq.size() >= ((size_t)1 << 28)) break; continue; }      // --split: a batch is closed by its bases (12 bytes each on the device), not by its reads
                 if (!legacy) continue;
                 longest = std::max(longest, (size_t)(b->off[b->n()] - b->off[b->n() - 1]));
                 if (b->n() * longest > ((size_t)1 << 28)) break;
@@ -1007,7 +1020,13 @@ int main(int argc, char** argv) {
             const double a0 = now();
             if (legacy) {
                 std::vector<uint64_t> ptr(b.seq.size() + 1), len(b.seq.size() + 1);
-                if (moni_ms_lengths_batch(C, &rb, ptr.data(), len.data())) die("moni_ms_lengths_batch failed");
+                if (a.split) {
+                    moni_mslong_params_t sp; moni_mslong_params_default(&sp);
+                    if (a.seg_len_set) sp.seg_len = a.seg_len;
+                    if (a.overlap_set) sp.overlap = a.overlap;
+                    const int sr = moni_ms_long_batch(C, &rb, &sp, ptr.data(), len.data(), nullptr);
+                    if (sr) die("moni_ms_long_batch failed (" + std::to_string(sr) + ")");
+                } else if (moni_ms_lengths_batch(C, &rb, ptr.data(), len.data())) die("moni_ms_lengths_batch failed");
                 std::string sa, sb;
                 for (size_t r = 0; r < b.n(); ++r) {
                     const std::string hdr = ">" + std::string((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r])) + "\n";
