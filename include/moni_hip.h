@@ -433,6 +433,53 @@ int  moni_seqcount_fetch(moni_ctx_t *ctx, moni_seqcount_res_t *res, uint64_t *co
 int  moni_seqcount_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const moni_seqcount_params_t *prm,
                          moni_seqcount_res_t *res, uint64_t *counts);
 
+/* ---- k-mismatch count and locate: every string within Hamming distance k of a pattern that occurs in the index ---- */
+/* Tasks, strands and bytes are moni_locate's (task t = pattern * strands + strand; strand 1 is the reverse complement by the aligner's table).  Only
+ * substitutions are searched.  A text window of the pattern's length occurs at distance e where it differs from the pattern at exactly e <= k
+ * places and the TEXT byte at every such place is one of upper-case A, C, G, T.  So the pattern's own byte matches itself as in a moni_locate_batch search (N against
+ * N; a byte <= 1 or one the BWT does not hold never does, but its place can be paid for as a mismatch), and a window that holds a separator, the
+ * terminator or an N where the pattern holds another byte does not occur.  Distinct matching strings have disjoint suffix-array intervals: the
+ * counts are counts of text positions, and with k = 0 cnt[0] is moni_locate's count.
+ * The search tree of a task is cut into pieces of chunk_len pattern places that run in parallel; max_steps bounds the backward-search steps of ONE
+ * piece, so that no batch turns into minutes of kernel time: a task one of whose pieces stopped there has complete = 0 and lower bounds. */
+#define MONI_APPROX_MAX_K 3
+#define MONI_APPROX_MAX_STEPS_DEFAULT (1ull << 20)
+#define MONI_APPROX_CHUNK_LEN_DEFAULT (1u << 30)   /* one piece per task: what the measurement favours */
+typedef struct { uint32_t strands;    /* 1: forward only, 2: forward and reverse complement */
+                 uint32_t k;          /* mismatches allowed, 0 .. MONI_APPROX_MAX_K */
+                 uint32_t max_hits;   /* matching strings (intervals) kept per task; 0 = counts only */
+                 uint32_t max_occ;    /* positions kept per kept hit; 0 = none (needs max_hits > 0 otherwise) */
+                 uint32_t chunk_len;  /* pattern places per piece, >= 1; >= the pattern's length: one piece per task */
+                 uint32_t reserved;   /* 0 */
+                 uint64_t max_steps;  /* backward-search steps of one piece; 0 = no limit */
+               } moni_approx_params_t;
+/* cnt[e]: text positions at distance exactly e (entries above k are 0).  n_hits: distinct matching strings, exact and uncapped; n_kept =
+ * min(n_hits, max_hits) of them lie at hit_off of the hit list.  complete: 0 where max_steps stopped a piece of the task - cnt and n_hits are then
+ * lower bounds.  matched: as in moni_locate_res_t, the length of the longest suffix of the pattern that occurs exactly. */
+typedef struct { uint64_t cnt[4], n_hits, hit_off; uint32_t n_kept, complete, matched, reserved; } moni_approx_res_t;
+/* One matching string of a task: its distance, its interval [sa_lo, sa_lo + count - 1], and n_occ = min(count, max_occ) positions at occ_off of
+ * pos / seq / seq_off - as moni_locate lists them: the n_occ highest ranks of the interval in decreasing rank order, no lift-over.  The list is
+ * grouped by task and sorted by (n_mis, sa_lo) inside a task.  Where n_hits > max_hits, which hits are kept is not specified; each is a true one. */
+typedef struct { uint64_t task; uint32_t n_mis, n_occ; uint64_t sa_lo, count, occ_off; } moni_approx_hit_t;
+void moni_approx_params_default(moni_approx_params_t *p);   /* strands 1, k 1, max_hits 0, max_occ 0, chunk_len MONI_APPROX_CHUNK_LEN_DEFAULT, max_steps MONI_APPROX_MAX_STEPS_DEFAULT */
+/* Device-only run over the batch that moni_reads_upload made resident; the results stay in HBM, in buffers of their own (a locate or seqcount
+ * result of the context stays fetchable).  MONI_EINVAL: strands outside {1, 2}, k > 3, chunk_len 0, max_occ > 0 with max_hits 0, a non-zero
+ * reserved, no resident batch; MONI_ENOMEM: the hit region of n_tasks * max_hits records cannot be had (nothing is written then).
+ * moni_last_kernel_ms(ctx, 0, ..) then gives the exact pass's time, (ctx, 3, ..) the tree pass's with the scans and the compaction of the hits,
+ * (ctx, 4, ..) the position walk's, (ctx, 6, ..) the whole run's; moni_last_counters: [0] the steps of the search tree - every attempted
+ * (node, letter) step once -, [1] fast rows fetched, [2] phi steps = the sum of n_occ - 1 over the kept hits, [3] steps that took the general
+ * path.  Works on an index without LCP samples. */
+int  moni_approx_run(moni_ctx_t *ctx, const moni_approx_params_t *prm);
+/* What moni_approx_fetch would write (any pointer may be NULL); MONI_EINVAL before any run, and after another batch was made resident. */
+int  moni_approx_sizes(moni_ctx_t *ctx, uint64_t *n_tasks, uint64_t *n_hits_kept, uint64_t *n_occ);
+/* The results of the last moni_approx_run on this context: res holds *n_tasks records, hits *n_hits_kept, pos / seq / seq_off *n_occ values each
+ * (any pointer may be NULL; the three position arrays are taken together, with hits). */
+int  moni_approx_fetch(moni_ctx_t *ctx, moni_approx_res_t *res, moni_approx_hit_t *hits, uint64_t *pos, uint32_t *seq, uint64_t *seq_off);
+/* Host-buffer form: upload, run, fetch.  res: batch->n_reads * strands records (the caller's); *hits / *pos / *seq / *seq_off are malloc'ed
+ * (moni_free; NULL where empty), *n_hits_kept / *n_occ (may be NULL) their lengths.  An empty batch gives MONI_OK. */
+int  moni_approx_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const moni_approx_params_t *prm, moni_approx_res_t *res,
+                       moni_approx_hit_t **hits, uint64_t **pos, uint32_t **seq, uint64_t **seq_off, uint64_t *n_hits_kept, uint64_t *n_occ);
+
 /* ---- the reference's on-disk liftidx (<prefix>.ldx: include/aligner/liftidx.hpp:117-143 over include/common/seqidx.hpp:197-238) ---- */
 /* Both layouts load: the current one (u64 w after u) and the older one the reference's fixture data/Chr21.10.ldx has. */
 int moni_ldx_info(const char *path, uint64_t *n_seq, uint64_t *u, uint64_t *w, int *has_w);

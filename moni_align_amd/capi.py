@@ -32,6 +32,7 @@ EXPORTS = [
     "moni_pml_batch", "moni_pml_run", "moni_pml_fetch", "moni_pml_sizes",
     "moni_locate_params_default", "moni_locate_run", "moni_locate_sizes", "moni_locate_fetch", "moni_locate_batch",
     "moni_seqcount_params_default", "moni_seqcount_run", "moni_seqcount_sizes", "moni_seqcount_fetch", "moni_seqcount_batch",
+    "moni_approx_params_default", "moni_approx_run", "moni_approx_sizes", "moni_approx_fetch", "moni_approx_batch",
     "moni_mslong_params_default", "moni_ms_long_batch",
 ]
 
@@ -103,6 +104,11 @@ class SeqcountParamsC(C.Structure):
     _fields_ = [("strands", C.c_uint32), ("reserved", C.c_uint32), ("max_walk", C.c_uint64)]
 
 
+class ApproxParamsC(C.Structure):
+    _fields_ = [("strands", C.c_uint32), ("k", C.c_uint32), ("max_hits", C.c_uint32), ("max_occ", C.c_uint32), ("chunk_len", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_steps", C.c_uint64)]
+
+
 class MslongParamsC(C.Structure):
     _fields_ = [("seg_len", C.c_uint32), ("overlap", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
@@ -128,7 +134,11 @@ DP_RESULT_DTYPE = np.dtype([("max", "<i4"), ("max_q", "<i4"), ("max_t", "<i4"), 
                             ("zdropped", "<i4"), ("n_cigar", "<u4"), ("cigar_off", "<u4")])
 LOCATE_RES_DTYPE = np.dtype([("count", "<u8"), ("sa_lo", "<u8"), ("occ_off", "<u8"), ("n_occ", "<u4"), ("matched", "<u4")])
 SEQCOUNT_RES_DTYPE = np.dtype([("count", "<u8"), ("sa_lo", "<u8"), ("matched", "<u4"), ("n_seqs", "<u4"), ("walked", "<u4"), ("n_segs", "<u4")])
-assert LOCATE_RES_DTYPE.itemsize == 32 and SEQCOUNT_RES_DTYPE.itemsize == 32
+APPROX_RES_DTYPE = np.dtype([("cnt", "<u8", (4,)), ("n_hits", "<u8"), ("hit_off", "<u8"), ("n_kept", "<u4"), ("complete", "<u4"), ("matched", "<u4"), ("reserved", "<u4")])
+APPROX_HIT_DTYPE = np.dtype([("task", "<u8"), ("n_mis", "<u4"), ("n_occ", "<u4"), ("sa_lo", "<u8"), ("count", "<u8"), ("occ_off", "<u8")])
+APPROX_MAX_STEPS_DEFAULT = 1 << 20
+APPROX_CHUNK_LEN_DEFAULT = 1 << 30
+assert LOCATE_RES_DTYPE.itemsize == 32 and SEQCOUNT_RES_DTYPE.itemsize == 32 and APPROX_RES_DTYPE.itemsize == 64 and APPROX_HIT_DTYPE.itemsize == 40
 assert MEM_DTYPE.itemsize == 48 and DP_TASK_DTYPE.itemsize == 32 and DP_RESULT_DTYPE.itemsize == 48
 
 DEFAULT_MAT = [2, -4, -4, -4, 0, -4, 2, -4, -4, 0, -4, -4, 2, -4, 0, -4, -4, -4, 2, 0, 0, 0, 0, 0, 0]
@@ -217,6 +227,12 @@ def lib():
         L.moni_seqcount_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.moni_seqcount_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.moni_seqcount_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.POINTER(SeqcountParamsC), C.c_void_p, C.c_void_p]
+        L.moni_approx_params_default.argtypes = [C.POINTER(ApproxParamsC)]
+        L.moni_approx_params_default.restype = None
+        L.moni_approx_run.argtypes = [C.c_void_p, C.POINTER(ApproxParamsC)]
+        L.moni_approx_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.moni_approx_fetch.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+        L.moni_approx_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.POINTER(ApproxParamsC), C.c_void_p] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_uint64)] * 2
         L.moni_locate_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.POINTER(LocateParamsC), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_sam_header.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -700,6 +716,62 @@ class Ctx:
         counts = np.zeros((nt, ns), dtype=np.uint64) if want_counts else None
         _chk(self._L.moni_seqcount_fetch(self._h, res.ctypes.data, counts.ctypes.data if want_counts else None), "moni_seqcount_fetch")
         return res, counts
+
+    def _approx_params(self, strands, k, max_hits, max_occ, chunk_len, max_steps) -> "ApproxParamsC":
+        p = ApproxParamsC()
+        self._L.moni_approx_params_default(C.byref(p))
+        p.strands, p.k, p.max_hits, p.max_occ = strands, k, max_hits, max_occ
+        if chunk_len is not None:
+            p.chunk_len = chunk_len
+        if max_steps is not None:
+            p.max_steps = max_steps
+        return p
+
+    def approx_batch(self, seq: np.ndarray, offsets: np.ndarray, strands: int = 1, k: int = 1, max_hits: int = 0, max_occ: int = 0, chunk_len: Optional[int] = None,
+                     max_steps: Optional[int] = None):
+        """k-mismatch count and locate (moni_approx_batch): (res, hits, pos, seq, seq_off) - res[i * strands + s] (APPROX_RES_DTYPE: cnt[4], the text
+        positions at distance 0..3; n_hits, hit_off, n_kept, complete, matched) of pattern i on strand s; hits (APPROX_HIT_DTYPE: task, n_mis, n_occ,
+        sa_lo, count, occ_off) the n_kept = min(n_hits, max_hits) matching strings kept of each task at res["hit_off"], sorted by (n_mis, sa_lo); and
+        the text position, sequence index and offset inside the sequence of the n_occ = min(count, max_occ) positions kept of each hit, at
+        hits["occ_off"].  chunk_len: pattern places per piece of a search tree, max_steps: backward-search steps per piece (None: the library's defaults; max_steps 0: no limit)."""
+        b, keep = self._batch(seq, offsets)
+        n = len(offsets) - 1
+        p = self._approx_params(strands, k, max_hits, max_occ, chunk_len, max_steps)
+        res = np.zeros(n * strands, dtype=APPROX_RES_DTYPE)
+        hh, hp, hs, ho, nh, no = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _chk(self._L.moni_approx_batch(self._h, C.byref(b), C.byref(p), res.ctypes.data, C.byref(hh), C.byref(hp), C.byref(hs), C.byref(ho), C.byref(nh), C.byref(no)),
+             "moni_approx_batch")
+        self.n_reads = n
+        try:
+            take = lambda h, k_, dt: np.frombuffer(C.string_at(h, k_ * np.dtype(dt).itemsize), dtype=dt).copy() if k_ else np.zeros(0, dtype=dt)
+            return res, take(hh, nh.value, APPROX_HIT_DTYPE), take(hp, no.value, np.uint64), take(hs, no.value, np.uint32), take(ho, no.value, np.uint64)
+        finally:
+            for h in (hh, hp, hs, ho):
+                self._L.moni_free(h)
+
+    def approx_run(self, strands: int = 1, k: int = 1, max_hits: int = 0, max_occ: int = 0, chunk_len: Optional[int] = None, max_steps: Optional[int] = None):
+        """moni_approx_run over the batch made resident by upload(): device only, the results wait for approx_fetch()"""
+        p = self._approx_params(strands, k, max_hits, max_occ, chunk_len, max_steps)
+        _chk(self._L.moni_approx_run(self._h, C.byref(p)), "moni_approx_run")
+
+    def approx_sizes(self):
+        """(n_tasks, hits kept, positions) of the last approx_run()"""
+        nt, nh, no = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _chk(self._L.moni_approx_sizes(self._h, C.byref(nt), C.byref(nh), C.byref(no)), "moni_approx_sizes")
+        return nt.value, nh.value, no.value
+
+    def approx_fetch(self, want_hits: bool = True):
+        """(res, hits, pos, seq, seq_off) of the last approx_run(), sized by moni_approx_sizes; want_hits=False fetches the records alone (the four
+        arrays come back empty)"""
+        nt, nh, no = self.approx_sizes()
+        if not want_hits:
+            nh = no = 0
+        res = np.zeros(nt, dtype=APPROX_RES_DTYPE)
+        hits = np.zeros(nh, dtype=APPROX_HIT_DTYPE)
+        pos, sq, so = np.zeros(no, dtype=np.uint64), np.zeros(no, dtype=np.uint32), np.zeros(no, dtype=np.uint64)
+        _chk(self._L.moni_approx_fetch(self._h, res.ctypes.data, hits.ctypes.data if nh else None, pos.ctypes.data if no else None, sq.ctypes.data if no else None,
+                                       so.ctypes.data if no else None), "moni_approx_fetch")
+        return res, hits, pos, sq, so
 
     def ms_lengths_batch(self, seq: np.ndarray, offsets: np.ndarray):
         """legacy `moni ms`: (pointers, lengths) of the forward strand of every read"""

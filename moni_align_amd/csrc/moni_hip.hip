@@ -42,6 +42,7 @@
 #include "pml_kernels.hip"
 #include "locate_kernels.hip"
 #include "seqcount_kernels.hip"
+#include "approx_kernels.hip"
 #include "mslong_kernels.hip"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "moni_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return MONI_ENODEV; } } while (0)
@@ -218,6 +219,12 @@ struct moni_ctx {
         uint64_t n_tasks = 0, n_segs = 0; uint32_t n_seq = 0; bool valid = false;
         void release() { lres.release(); res.release(); toe.release(); cnt.release(); off.release(); counts.release(); k_lo.release(); valid = false; }
     } sc;
+    struct ApxBufs {        // k-mismatch queries (approx_api.inc): the last run's records, hits and positions, on the device until moni_approx_fetch; grow-only
+        DBuf<moni_approx_res_t> res; DBuf<moni_approx_hit_t> slots, hits; DBuf<apx_ckpt_t> ckpt; DBuf<uint64_t> cnt, ck_off, hit_off, occ_cnt, occ_off, pos, seq_off; DBuf<uint32_t> seq;
+        uint64_t n_tasks = 0, n_hits = 0, n_occ = 0; bool valid = false;
+        void release() { res.release(); slots.release(); hits.release(); ckpt.release(); cnt.release(); ck_off.release(); hit_off.release(); occ_cnt.release(); occ_off.release(); pos.release();
+                         seq_off.release(); seq.release(); valid = false; }
+    } apx;
     struct MslBufs {        // matching statistics of long patterns (mslong_api.inc): pointers and lengths in pattern order, the segment table, the runs; grow-only
         DBuf<uint64_t> ptr, cnt, seg_off, head, run_idx; DBuf<uint32_t> lens, flags; DBuf<mslong_seg_t> segs; DBuf<mslong_state_t> states; DBuf<mslong_run_t> runs;
         DBuf<unsigned long long> counters;
@@ -540,7 +547,7 @@ void moni_ctx_destroy(moni_ctx_t* c) {
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (auto e : c->ak_begin) (void)hipEventDestroy(e);
     for (auto e : c->ak_done) (void)hipEventDestroy(e);
-    c->ex.release(); c->pml.release(); c->loc.release(); c->sc.release(); c->msl.release();
+    c->ex.release(); c->pml.release(); c->loc.release(); c->sc.release(); c->apx.release(); c->msl.release();
     c->ak_recs.release(); c->ak_cig.release(); c->ak_alt.release(); c->ak_minscore.release(); c->pe.release();
     if (c->d_ak_cursors) (void)hipFree(c->d_ak_cursors);
     if (c->out_buf) (void)hipHostFree(c->out_buf);
@@ -594,7 +601,7 @@ static int reads_upload(moni_ctx* c, const moni_read_batch_t* b, bool keep_host_
     c->h_blk.swap(blk);
     if (keep_host_copy) { c->h_seq.assign(b->seq + b->offsets[0], b->seq + b->offsets[0] + total); c->h_offs = rel; }
     else { c->h_seq.clear(); c->h_offs.clear(); }
-    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false;
+    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false; c->apx.valid = false;
     return MONI_OK;
 }
 
@@ -606,7 +613,7 @@ int moni_reads_swap(moni_ctx_t* c, uint32_t slot) {
     moni_ctx::Stash& x = c->stash[slot];
     std::swap(c->seq, x.seq); std::swap(c->offs, x.offs); std::swap(c->blk, x.blk); c->h_blk.swap(x.h_blk); std::swap(c->n_reads, x.n_reads); std::swap(c->total_len, x.total_len); std::swap(c->max_len, x.max_len);
     c->h_seq.swap(x.h_seq); c->h_offs.swap(x.h_offs);
-    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false;
+    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false; c->apx.valid = false;
     return MONI_OK;
 }
 
@@ -1966,6 +1973,7 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "pml_api.inc"
 #include "locate_api.inc"
 #include "seqcount_api.inc"
+#include "approx_api.inc"
 #include "mslong_api.inc"
 
 }  // extern "C"
