@@ -665,6 +665,12 @@ struct Aligner {
     // of the align-kernel path runs per read (same bytes as the two functions above and below produce; sam.hpp:144-188,249-287).
     struct OutBuf {                    // grow-only text buffer (kept by the caller across batches: its pages stay mapped)
         char* base = nullptr; size_t len = 0, cap = 0;
+        OutBuf() = default;
+        OutBuf(const OutBuf&) = delete;
+        OutBuf& operator=(const OutBuf&) = delete;
+        OutBuf(OutBuf&& o) noexcept : base(o.base), len(o.len), cap(o.cap) { o.base = nullptr; o.len = o.cap = 0; }
+        OutBuf& operator=(OutBuf&& o) noexcept { if (this != &o) { release(); base = o.base; len = o.len; cap = o.cap; o.base = nullptr; o.len = o.cap = 0; } return *this; }
+        ~OutBuf() { release(); }
         bool ensure(size_t extra) {
             if (len + extra <= cap) return true;
             size_t nc = cap ? cap + cap / 2 : (size_t)1 << 20;

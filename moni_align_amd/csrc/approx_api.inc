@@ -30,14 +30,14 @@ static int approx_run_resident(moni_ctx* c, const moni_approx_params_t* prm) {
         return rc;
     }
     apx_args_t A;
-    A.rows = I->d_rows; A.frows = I->d_frows; A.cr = I->d_cr; A.recs = I->d_recs; A.pat = c->pat.p; A.offs = c->offs.p; A.blk = c->blk.p;
+    A.rows = I->d_rows.p; A.frows = I->d_frows.p; A.cr = I->d_cr.p; A.recs = I->d_recs.p; A.pat = c->pat.p; A.offs = c->offs.p; A.blk = c->blk.p;
     A.strands = prm->strands; A.k = prm->k; A.max_hits = prm->max_hits; A.max_occ = prm->max_occ; A.chunk_len = prm->chunk_len; A.max_steps = prm->max_steps;
     A.res = B.res.p; A.slots = B.slots.p;
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
     rec(c, EV_ALL0);
     const unsigned task_grid = (unsigned)((n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK);          // (one thread more than tasks: it closes the counts for the scans)
     if (nr) {
-        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_pack + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, c->seq.p, c->offs.p, c->blk.p, n_pack,
+        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_pack + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, c->seq.p, c->offs.p, c->blk.p, n_pack,
                            c->pat.p, c->pflag.p);
         if (prm->k) {
             hipLaunchKernelGGL(approx_plan_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, c->offs.p, n_tasks, prm->strands, prm->chunk_len, B.cnt.p);
@@ -47,16 +47,16 @@ static int approx_run_resident(moni_ctx* c, const moni_approx_params_t* prm) {
     }
     rec(c, EV_MS0);
     if (nr)
-        hipLaunchKernelGGL(approx_exact_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, A, n_tasks, prm->k ? B.ck_off.p : nullptr,
-                           prm->k ? B.ckpt.p : nullptr, c->d_counters);
+        hipLaunchKernelGGL(approx_exact_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, A, n_tasks, prm->k ? B.ck_off.p : nullptr,
+                           prm->k ? B.ckpt.p : nullptr, c->d_counters.p);
     rec(c, EV_MS1);
     HIPCHK(hipGetLastError());
     rec(c, EV_PC0);
     uint64_t n_hits = 0, n_occ = 0;
     if (nr && prm->k && ck_bound) {
         const uint64_t blocks = (ck_bound + MS_BLOCK - 1) / MS_BLOCK;
-        hipLaunchKernelGGL(approx_tree_kernel, dim3((unsigned)std::min<uint64_t>(blocks, APX_MAX_GRID)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, A, n_tasks, B.ck_off.p,
-                           B.ckpt.p, c->d_counters);
+        hipLaunchKernelGGL(approx_tree_kernel, dim3((unsigned)std::min<uint64_t>(blocks, APX_MAX_GRID)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, A, n_tasks, B.ck_off.p,
+                           B.ckpt.p, c->d_counters.p);
         HIPCHK(hipGetLastError());
     }
     if (nr && prm->max_hits) {
@@ -81,9 +81,9 @@ static int approx_run_resident(moni_ctx* c, const moni_approx_params_t* prm) {
     rec(c, EV_PE0);
     if (n_occ) {
         if ((rc = B.pos.ensure(n_occ)) || (rc = B.seq.ensure(n_occ)) || (rc = B.seq_off.ensure(n_occ))) return rc;
-        phi_tab_t P; P.recs = I->d_phi; P.dir = I->d_phi_dir;
-        hipLaunchKernelGGL(approx_walk_kernel, dim3((unsigned)((n_hits + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, P, I->d_seq_starts, n_hits, B.hits.p,
-                           B.occ_off.p, B.pos.p, B.seq.p, B.seq_off.p, c->d_counters);
+        phi_tab_t P; P.recs = I->d_phi.p; P.dir = I->d_phi_dir.p;
+        hipLaunchKernelGGL(approx_walk_kernel, dim3((unsigned)((n_hits + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, P, I->d_seq_starts.p, n_hits, B.hits.p,
+                           B.occ_off.p, B.pos.p, B.seq.p, B.seq_off.p, c->d_counters.p);
     }
     rec(c, EV_PE1);
     rec(c, EV_ALL1);

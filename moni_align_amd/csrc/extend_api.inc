@@ -22,7 +22,7 @@ static int dp_run_device(moni_ctx* c, const moni_extend_params_t* prm, const uin
     // ksw_gen_simple_mat(5, mat, smatch, -smismatch) (extender_ksw2.hpp:174, 579-592): a wildcard on either side scores 0, which extz_wave takes as -gape
     P.sc_mch = prm->smatch < 0 ? -prm->smatch : prm->smatch; P.sc_mis = prm->smismatch > 0 ? -prm->smismatch : prm->smismatch; P.sc_N = -prm->gape;
     P.wild = 4; P.qo = prm->gapo; P.e = prm->gape; P.end_bonus = prm->end_bonus;
-    P.reads = reads; P.text = c->idx->d_text; P.n_text = c->idx->K.n_text;
+    P.reads = reads; P.text = c->idx->d_text.p; P.n_text = c->idx->K.n_text;
     const unsigned grid = (unsigned)std::min<uint64_t>(task_cap, (uint64_t)ctx_n_cu(c) * 32);
     if (!grid) return MONI_OK;
     if (t_max <= 64) hipLaunchKernelGGL(extend_dp_kernel<1>, dim3(grid), dim3(64), 0, c->stream, P, n_tasks, task_cap);
@@ -33,14 +33,7 @@ static int dp_run_device(moni_ctx* c, const moni_extend_params_t* prm, const uin
 }
 
 static int ex_out_reserve(moni_ctx* c, size_t used, size_t need) {          // the context's pinned text buffer, its first `used` bytes kept
-    if (need <= c->out_cap) return MONI_OK;
-    const size_t want = need + need / 2 + 4096;
-    char* nb = nullptr;
-    if (hipHostMalloc((void**)&nb, want, hipHostMallocDefault) != hipSuccess) return MONI_ENOMEM;
-    if (c->out_buf && used) memcpy(nb, c->out_buf, used);
-    if (c->out_buf) (void)hipHostFree(c->out_buf);
-    c->out_buf = nb; c->out_cap = want;
-    return MONI_OK;
+    return need <= c->out_buf.cap ? MONI_OK : c->out_buf.ensure_keep(need + need / 2 + 4096, used);
 }
 
 static int extend_core(moni_ctx* c, const uint8_t* names, const uint64_t* name_off, const uint8_t* quals, const moni_extend_params_t* prm,
@@ -63,17 +56,17 @@ static int extend_core(moni_ctx* c, const uint8_t* names, const uint64_t* name_o
     HIPCHK(hipSetDevice(I->device));
     auto& B = c->ex;
     int rc;
-    if (!B.tables) {          // the index tables with extend's complement (ext_complement) for pack_kernel
-        moni_tables_t* t = nullptr;
-        if (hipMalloc((void**)&t, sizeof(moni_tables_t)) != hipSuccess) return MONI_ENOMEM;
+    if (!B.tables.p) {          // the index tables with extend's complement (ext_complement) for pack_kernel
+        DBuf<moni_tables_t> t;
+        if ((rc = t.alloc_exact(1))) return rc;
         uint8_t tab[256];
         for (int b = 0; b < 256; ++b) tab[b] = ext_complement((uint8_t)b);
-        if (hipMemcpy(t, I->d_tables, sizeof(moni_tables_t), hipMemcpyDeviceToDevice) != hipSuccess ||
-            hipMemcpy(reinterpret_cast<uint8_t*>(t) + offsetof(moni_tables_t, compl_tab), tab, 256, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(t); return MONI_ENODEV; }
-        B.tables = t;
+        if (hipMemcpy(t.p, I->d_tables.p, sizeof(moni_tables_t), hipMemcpyDeviceToDevice) != hipSuccess ||
+            hipMemcpy(reinterpret_cast<uint8_t*>(t.p) + offsetof(moni_tables_t, compl_tab), tab, 256, hipMemcpyHostToDevice) != hipSuccess) return MONI_ENODEV;
+        B.tables = std::move(t);
     }
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, 4 * sizeof(unsigned long long), c->stream));
-    if ((rc = ms_launch(c, B.tables))) return rc;
+    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    if ((rc = ms_launch(c, B.tables.p))) return rc;
     // both strands' sequences in one buffer: DP queries and SEQ are read from it by position
     if ((rc = B.seq2.ensure(2 * total + 32))) return rc;
     HIPCHK(hipMemcpyAsync(B.seq2.p, c->seq.p, total, hipMemcpyDeviceToDevice, c->stream));
@@ -123,13 +116,13 @@ static int extend_core(moni_ctx* c, const uint8_t* names, const uint64_t* name_o
         return rc;
     ext_args_t X;
     memset(&X, 0, sizeof X);
-    X.K = I->K; X.text = I->d_text; X.pat = c->pat.p; X.offs = c->offs.p; X.blk = c->blk.p; X.ptr = c->ptr.p;
+    X.K = I->K; X.text = I->d_text.p; X.pat = c->pat.p; X.offs = c->offs.p; X.blk = c->blk.p; X.ptr = c->ptr.p;
     X.seq2 = B.seq2.p; X.total_len = total;
     X.min_len = prm->min_len; X.ext_len = prm->ext_len; X.smatch = prm->smatch < 0 ? -prm->smatch : prm->smatch;
     X.plans = B.plans.p; X.tasks = B.tasks.p; X.dir_off = B.dir_off.p; X.cig_off = B.cig_off.p; X.cur = B.cur.p;
     X.task_cap = task_cap; X.dir_cap = dir_cap; X.cig_cap = cig_cap;
     X.res = B.res.p; X.cig = B.cig.p; X.min_score_of_len = B.minscore.p;
-    X.seq_starts = I->d_seq_starts; X.snames = I->d_snames; X.sname_off = I->d_sname_off; X.n_seq = I->K.n_seq;
+    X.seq_starts = I->d_seq_starts.p; X.snames = I->d_snames.p; X.sname_off = I->d_sname_off.p; X.n_seq = I->K.n_seq;
     X.rnames = B.rnames.p; X.rname_off = B.rname_off.p; X.quals = quals ? B.quals.p : nullptr;
     X.lines = B.lines.p; X.slot = slot; X.len = B.len.p; X.off = B.off.p;
     const int n_cu = ctx_n_cu(c);
@@ -158,12 +151,12 @@ static int extend_core(moni_ctx* c, const uint8_t* names, const uint64_t* name_o
         if (h[EXC_ERR]) return MONI_ERANGE;          // a line or a CIGAR beyond the staging, or a list beyond its capacity: nothing was written out of bounds
         const uint64_t bytes = h[EXC_BYTES];
         if ((rc = ex_out_reserve(c, used, used + bytes + 1))) return rc;
-        if (bytes) HIPCHK(hipMemcpy(c->out_buf + used, B.block.p, bytes, hipMemcpyDeviceToHost));
+        if (bytes) HIPCHK(hipMemcpy(c->out_buf.p + used, B.block.p, bytes, hipMemcpyDeviceToHost));
         used += bytes;
         if (stats) { stats->records += h[EXC_RECORDS]; stats->extended += h[EXC_EXTENDED]; stats->dp_tasks += h[EXC_TASKS]; stats->dp_cells += h[EXC_CELLS]; }
     }
     if ((rc = ex_out_reserve(c, used, used + 1))) return rc;
-    c->out_buf[used] = 0;
+    c->out_buf.p[used] = 0;
     if (stats) stats->t_kernel = k_ms * 1e-3;
     *sam_len = used;
     return MONI_OK;
@@ -177,7 +170,7 @@ int moni_extend_run(moni_ctx_t* c, const uint8_t* names, const uint64_t* name_of
         const int rc = extend_core(c, names, name_off, quals, prm, sam_len, stats);
         if (rc) { *sam_len = 0; return rc; }
     } catch (const std::bad_alloc&) { *sam_len = 0; return MONI_ENOMEM; }
-    *sam = c->out_buf;
+    *sam = c->out_buf.p;
     return MONI_OK;
 }
 

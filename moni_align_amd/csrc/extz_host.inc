@@ -67,7 +67,7 @@ static int dp_run(moni_ctx_t* c, const moni_dp_params_t* prm, const uint8_t* qse
     P.dirs = c->dp_dir.p; P.cig_tmp = c->dp_cig.p; P.results = c->dp_res.p;
     P.sc_mch = prm->mat[0]; P.sc_mis = prm->mat[1]; P.sc_N = prm->mat[m * m - 1] == 0 ? -prm->e : prm->mat[m * m - 1];
     P.wild = m - 1; P.qo = prm->q; P.e = prm->e; P.end_bonus = prm->end_bonus;
-    P.reads = c->seq.p; P.text = c->idx->d_text; P.n_text = c->idx->K.n_text;
+    P.reads = c->seq.p; P.text = c->idx->d_text.p; P.n_text = c->idx->K.n_text;
     rec(c, EV_DP0);
     if (c->extz_lds) {          // LDS-tiled form for every size it takes (the one align_kernel uses)
         P.order = (const uint32_t*)c->dp_ws.p;

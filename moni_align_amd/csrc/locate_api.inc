@@ -20,15 +20,15 @@ static int locate_run_resident(moni_ctx* c, const moni_locate_params_t* prm) {
     if ((rc = c->pat.ensure(c->h_blk.back().y + 1)) || (rc = c->pflag.ensure(n_pack + 8)) || (rc = B.res.ensure(n_tasks + 1)) || (rc = B.toe.ensure(n_tasks + 1)) ||
         (rc = B.cnt.ensure(n_tasks + 2)) || (rc = B.off.ensure(n_tasks + 2)))
         return rc;
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
     rec(c, EV_ALL0);
     if (nr)
-        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_pack + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, c->seq.p, c->offs.p, c->blk.p, n_pack,
+        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_pack + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, c->seq.p, c->offs.p, c->blk.p, n_pack,
                            c->pat.p, c->pflag.p);
     rec(c, EV_MS0);
     if (nr)          // (one thread more than tasks: it closes the counts for the scan)
-        hipLaunchKernelGGL(count_kernel, dim3((unsigned)((n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, I->d_rows, I->d_frows, I->d_cr,
-                           I->d_recs, c->pat.p, c->offs.p, c->blk.p, n_tasks, prm->strands, prm->max_occ, B.res.p, B.toe.p, B.cnt.p, c->d_counters);
+        hipLaunchKernelGGL(count_kernel, dim3((unsigned)((n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, I->d_rows.p, I->d_frows.p, I->d_cr.p,
+                           I->d_recs.p, c->pat.p, c->offs.p, c->blk.p, n_tasks, prm->strands, prm->max_occ, B.res.p, B.toe.p, B.cnt.p, c->d_counters.p);
     rec(c, EV_MS1);
     HIPCHK(hipGetLastError());
     uint64_t total = 0;
@@ -40,9 +40,9 @@ static int locate_run_resident(moni_ctx* c, const moni_locate_params_t* prm) {
     rec(c, EV_PC0);
     if (total) {          // no occurrence to list: no walk launch
         if ((rc = B.pos.ensure(total)) || (rc = B.seq.ensure(total)) || (rc = B.seq_off.ensure(total))) return rc;
-        phi_tab_t P; P.recs = I->d_phi; P.dir = I->d_phi_dir;
-        hipLaunchKernelGGL(locate_walk_kernel, dim3((unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, P, I->d_seq_starts, n_tasks, B.res.p, B.toe.p,
-                           B.off.p, B.pos.p, B.seq.p, B.seq_off.p, c->d_counters);
+        phi_tab_t P; P.recs = I->d_phi.p; P.dir = I->d_phi_dir.p;
+        hipLaunchKernelGGL(locate_walk_kernel, dim3((unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, P, I->d_seq_starts.p, n_tasks, B.res.p, B.toe.p,
+                           B.off.p, B.pos.p, B.seq.p, B.seq_off.p, c->d_counters.p);
     }
     rec(c, EV_PC1);
     rec(c, EV_ALL1);

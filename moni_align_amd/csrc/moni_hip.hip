@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/moni_hip.h"
+#include "owned_buf.hpp"
 #include "image.hpp"
 #include "lift_build.hpp"
 #include "ref_index_io.hpp"
@@ -49,23 +50,55 @@
 
 enum { EV_MS0 = 0, EV_MS1, EV_MC0, EV_MC1, EV_ME0, EV_ME1, EV_PC0, EV_PC1, EV_PE0, EV_PE1, EV_DP0, EV_DP1, EV_ALL0, EV_ALL1, EV_N };
 
+// Where a Buf's memory lives (owned_buf.hpp).  The slack of `grown` is what the buffers have always had: memory use depends on it.
+struct DeviceMem {
+    static constexpr bool host_addressable = false;
+    static void* alloc(size_t bytes) { void* p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }
+    static void free(void* p) { (void)hipFree(p); }
+    static size_t grown(size_t need) { return need + need / 8 + 64; }
+};
+struct PinnedMem {
+    static constexpr bool host_addressable = true;
+    static void* alloc(size_t bytes) { void* p = nullptr; return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr; }
+    static void free(void* p) { (void)hipHostFree(p); }
+    static size_t grown(size_t n) { return n + n / 4; }
+};
+template <class Tp> using DBuf = Buf<Tp, DeviceMem>;
+template <class Tp> using HBuf = Buf<Tp, PinnedMem>;      // pinned host buffer
+
+// A stream or an event that is destroyed with its owner.  It converts to the handle, so launch lines read as with a bare handle; it is created into `h`.
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(const Handle&) = delete;
+    Handle& operator=(const Handle&) = delete;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept { if (this != &o) { reset(); h = o.h; o.h = nullptr; } return *this; }
+    ~Handle() { reset(); }
+    void reset() { if (h) (void)Destroy(h); h = nullptr; }
+    operator H() const { return h; }
+};
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+
 struct moni_index {
     int device = 0;
     moni_consts_t K;
-    moni_tables_t* d_tables = nullptr;
-    moni_row_t* d_rows = nullptr;
-    moni_frow_t* d_frows = nullptr;
-    uint32_t* d_cr = nullptr;
-    moni_rec_t* d_recs = nullptr;
-    moni_phi_t *d_phi = nullptr, *d_phi_inv = nullptr;
-    uint32_t *d_phi_dir = nullptr, *d_phi_inv_dir = nullptr;
-    uint8_t* d_text = nullptr;
-    uint64_t* d_text2 = nullptr; uint32_t* d_exc = nullptr; uint32_t exc_sh = 10, exc_words = 0;      // 2-bit text and its exception bitmap (seed_core.h: mem_fast_t)
-    uint64_t* d_seq_starts = nullptr;
-    uint32_t* d_name_id = nullptr;
-    uint8_t* d_snames = nullptr; uint32_t* d_sname_off = nullptr;      // sequence names, ragged (SAM text in align_kernel)
-    moni_lift_seq_t* d_lift_seqs = nullptr; moni_lift_run_t* d_lift_runs = nullptr;   // liftidx::lifts (lift_core.h)
-    uint64_t* d_pdir = nullptr;
+    DBuf<moni_tables_t> d_tables;
+    DBuf<moni_row_t> d_rows;
+    DBuf<moni_frow_t> d_frows;
+    DBuf<uint32_t> d_cr;
+    DBuf<moni_rec_t> d_recs;
+    DBuf<moni_phi_t> d_phi, d_phi_inv;
+    DBuf<uint32_t> d_phi_dir, d_phi_inv_dir;
+    DBuf<uint8_t> d_text;
+    DBuf<uint64_t> d_text2; DBuf<uint32_t> d_exc; uint32_t exc_sh = 10, exc_words = 0;      // 2-bit text and its exception bitmap (seed_core.h: mem_fast_t)
+    DBuf<uint64_t> d_seq_starts;
+    DBuf<uint32_t> d_name_id;
+    DBuf<uint8_t> d_snames; DBuf<uint32_t> d_sname_off;      // sequence names, ragged (SAM text in align_kernel)
+    DBuf<moni_lift_seq_t> d_lift_seqs; DBuf<moni_lift_run_t> d_lift_runs;   // liftidx::lifts (lift_core.h)
+    DBuf<uint64_t> d_pdir;
     bool lifts_null = true;
     uint64_t bytes = 0;
     // host copies for the host stages of the full path (chaining, MD/NM, SAM)
@@ -73,55 +106,25 @@ struct moni_index {
     mh::HostIndex hix;
 };
 
-template <class Tp>
-struct DBuf {
-    Tp* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t need) {
-        if (need <= cap) return MONI_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        size_t want = need + need / 8 + 64;
-        if (hipMalloc((void**)&p, want * sizeof(Tp)) != hipSuccess) { p = nullptr; return MONI_ENOMEM; }
-        cap = want;
-        return MONI_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-template <class Tp>
-struct HBuf {                  // pinned host buffer, grow-only
-    Tp* p = nullptr; size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return MONI_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = n + n / 4;
-        if (hipHostMalloc((void**)&p, want * sizeof(Tp), hipHostMallocDefault) != hipSuccess) { p = nullptr; return MONI_ENOMEM; }
-        cap = want; return MONI_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
-
 #define PE_NSET 1          // sets of the staged paired kernels' large buffers (pe_api.inc): the chunks' staged kernels run one after the other on one stream, what outlives them is per chunk
 #define PE_NSTREAM 4       // hand-over launches of the paired path in flight, one stream and one slot array each
 #ifndef AK_NSET
 #define AK_NSET 2
 #endif                     // launch streams of the align stage, each with its own buffer set: sub-batch k runs on set k % AK_NSET
-struct moni_ctx {
-    moni_index* idx = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[EV_N];
-    bool ev_valid[EV_N];
-    // resident batch
+struct ResidentBatch {      // a batch of reads in HBM: the one a context works on, or one parked beside it
     DBuf<uint8_t> seq;
     DBuf<uint64_t> offs;
     uint64_t n_reads = 0, total_len = 0, max_len = 0;
-    DBuf<moni_u64x2> blk; std::vector<moni_u64x2> h_blk;      // workspace layout of the resident batch (seed_core.h: ws_ptr_base / ws_pat_base), n_blocks + 1 entries
-    std::vector<uint8_t> h_seq;              // host copy of the resident batch (SAM SEQ, MD/NM)
+    DBuf<moni_u64x2> blk; std::vector<moni_u64x2> h_blk;      // workspace layout of the batch (seed_core.h: ws_ptr_base / ws_pat_base), n_blocks + 1 entries
+    std::vector<uint8_t> h_seq;              // host copy of the batch (SAM SEQ, MD/NM)
     std::vector<uint64_t> h_offs;
-    struct Stash { DBuf<uint8_t> seq; DBuf<uint64_t> offs; DBuf<moni_u64x2> blk; std::vector<moni_u64x2> h_blk; uint64_t n_reads = 0, total_len = 0, max_len = 0; std::vector<uint8_t> h_seq; std::vector<uint64_t> h_offs; };
-    std::vector<Stash> stash;                // moni_reads_swap: further batches kept in HBM beside the resident one
+};
+struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
+    moni_index* idx = nullptr;
+    Stream stream;
+    Event ev[EV_N];
+    bool ev_valid[EV_N] = {};
+    std::vector<ResidentBatch> stash;        // moni_reads_swap: further batches kept in HBM beside the resident one
     // workspaces
     DBuf<uint64_t> ptr, pat; DBuf<uint8_t> pflag;      // pflag: per seeding task, its pattern holds a byte outside A / C / G / T (pack_kernel)
     DBuf<uint32_t> cnt_m, cnt_s;
@@ -138,8 +141,8 @@ struct moni_ctx {
     uint64_t occ_stats[6] = {0, 0, 0, 0, 0, 0};      // moni_seed_occ_stats
     DBuf<uint32_t> pool;
     DBuf<uint8_t> scan_tmp;
-    occ_small_t* d_small = nullptr;         // seed_core.h
-    unsigned long long* d_counters = nullptr;   // 4
+    DBuf<occ_small_t> d_small;              // seed_core.h (one)
+    DBuf<unsigned long long> d_counters;    // 4
     uint64_t n_mems = 0, n_occs = 0;
     uint32_t dirs_scale = 1;                                   // direction-bit budget multiplier (doubles after a batch that overflowed it)
     uint32_t tmp_cap = 16;
@@ -160,8 +163,6 @@ struct moni_ctx {
     struct AfSet {          // device buffers of the staged align kernels (align_fast.hip), one set per launch stream
         DBuf<af_plan_t> plans; DBuf<moni_dp_task_t> tasks; DBuf<af_res_t> res; DBuf<uint32_t> bin_q, task_pos, tb_task, big_list, ctr; DBuf<uint8_t> ntasks;
         DBuf<af_chunk_t> chunks; DBuf<uint8_t> dirs, fin; DBuf<uint32_t> recipes; DBuf<af_ctab_t> ctab; DBuf<af_tb_t> tb; DBuf<uint64_t> bnd; DBuf<unsigned long long> prof, prep_prof, txt_cur;
-        void release() { ctab.release(); ntasks.release(); bnd.release(); prof.release(); big_list.release(); txt_cur.release(); plans.release(); tasks.release(); res.release(); bin_q.release(); task_pos.release(); tb_task.release(); ctr.release();
-                         chunks.release(); dirs.release(); fin.release(); recipes.release(); tb.release(); }
     } af[AK_NSET], af_pe[PE_NSET];
     HBuf<unsigned long long> pe_hcur;       // paired path, per chunk: the pool cursors / DP counters (8 words) and the number of pairs handed over, copied behind the chunk's kernels
     HBuf<uint32_t> af_ctr_host;             // counters of the last batch's launches (64 words per sub-batch), pinned
@@ -173,10 +174,10 @@ struct moni_ctx {
     DBuf<uint8_t> ak_rnames, ak_quals; DBuf<uint64_t> ak_rname_off, ak_txt; DBuf<double> ak_mapq_tab;      // SAM text in the kernel
     HBuf<uint64_t> h_txt;                                 // pinned staging of one sub-batch's text
     uint64_t ak_waves_full = 0;
-    hipStream_t ak_stream[AK_NSET] = {}, copy_stream = nullptr, fb_stream[AK_NSET] = {}, pe_stream[PE_NSTREAM] = {};
-    std::vector<hipEvent_t> ak_fin;                // staged kernels of a sub-batch queued; the handed-over reads follow on fb_stream
-    std::vector<hipEvent_t> af_ev;                 // per sub-batch: after the chaining kernels, after the DP kernels, after selection + traceback (HIP-event kernel times)
-    std::vector<hipEvent_t> ak_begin, ak_done;
+    Stream ak_stream[AK_NSET], copy_stream, fb_stream[AK_NSET], pe_stream[PE_NSTREAM];
+    std::vector<Event> ak_fin;                // staged kernels of a sub-batch queued; the handed-over reads follow on fb_stream
+    std::vector<Event> af_ev;                 // per sub-batch: after the chaining kernels, after the DP kernels, after selection + traceback (HIP-event kernel times)
+    std::vector<Event> ak_begin, ak_done;
     HBuf<moni_aln_rec_t> h_recs; HBuf<uint32_t> h_cig; HBuf<moni_alt_t> h_alt; HBuf<uint64_t> h_md;      // pinned staging of one sub-batch's records
     std::vector<mh::Aligner::OutBuf> pieces;          // per host thread: the text it is writing (kept across batches)
     std::vector<std::vector<char>> md_scratch;
@@ -185,14 +186,12 @@ struct moni_ctx {
     DBuf<moni_alt_t> ak_alt;
     DBuf<int32_t> ak_minscore;
     struct PeBufs { DBuf<pe_slot_t> slots; DBuf<ak_wave_t> waves; DBuf<pe_rec_t> recs; DBuf<uint32_t> cig; DBuf<moni_alt_t> alt; DBuf<unsigned long long> cur; DBuf<int32_t> minscore;
-                    DBuf<pe_sel_t> sel[PE_NSET]; DBuf<uint32_t> fb[PE_NSET];
+                    DBuf<pe_sel_t> sel[PE_NSET]; DBuf<uint32_t> fb[PE_NSET];      // staged paired kernels (pe_fast.hip): per chunk in flight, what pe_select_kernel decided; the hand-over list (16 words of counter, then the pairs)
                     DBuf<uint64_t> txt_pool, block, dev_len, dev_off, dev_pos; DBuf<int32_t> subn_tab; DBuf<double> pen_tab; DBuf<pe_pslot_t> park, k1_slots; DBuf<uint8_t> k1_dirs; DBuf<uint32_t> parked; DBuf<pe_orec_t> orec; uint32_t tag = 0;      // pe_orphan_kernel: parked pairs, their chains' scores
                     DBuf<uint8_t> scan_tmp[PE_NSTREAM]; bool subn_ready = false;      // the lines written on the GPU (pe_lines.hip)
-                             // staged paired kernels (pe_fast.hip): per chunk in flight, what pe_select_kernel decided; the hand-over list (16 words of counter, then the pairs)
-                    void release() { slots.release(); waves.release(); recs.release(); cig.release(); alt.release(); cur.release(); minscore.release(); for (int x = 0; x < PE_NSET; ++x) { sel[x].release(); fb[x].release(); }
-                                     txt_pool.release(); block.release(); dev_len.release(); dev_off.release(); dev_pos.release(); subn_tab.release(); pen_tab.release(); park.release(); k1_slots.release(); k1_dirs.release(); parked.release(); orec.release(); for (int x = 0; x < PE_NSTREAM; ++x) scan_tmp[x].release(); } } pe;      // paired-end path (pe_api.inc)
-    unsigned long long* d_ak_cursors = nullptr;
-    char* out_buf = nullptr; size_t out_cap = 0;      // moni_align_run's text buffer, kept across calls; pinned (hipHostMalloc): the in-order blocks of the
+    } pe;      // paired-end path (pe_api.inc)
+    DBuf<unsigned long long> d_ak_cursors;
+    HBuf<char> out_buf;                               // moni_align_run's text buffer, kept across calls; pinned (hipHostMalloc): the in-order blocks of the
                                                       // sub-batches land in it by DMA
     DBuf<uint64_t> ak_block;                          // per sub-batch: its SAM lines in read order (gather_lines_kernel)
     DBuf<uint64_t> ak_dev_len, ak_dev_off, ak_dev_pos; DBuf<unsigned long long> ak_dev_sum;
@@ -202,33 +201,25 @@ struct moni_ctx {
     struct ExBufs {         // extend mode (extend_api.inc): per chunk of reads, the plans, the device-resident DP task list and its results, the lines' staging
         DBuf<uint8_t> seq2, rnames, quals, lines, block, dirs; DBuf<uint64_t> rname_off, dir_off, cig_off, len, off, pos; DBuf<ext_plan_t> plans; DBuf<moni_dp_task_t> tasks;
         DBuf<moni_dp_result_t> res; DBuf<uint32_t> cig; DBuf<int32_t> minscore; DBuf<unsigned long long> cur; HBuf<unsigned long long> hcur;
-        moni_tables_t* tables = nullptr;          // the index tables with extend's strand-1 complement (ext_complement)
-        void release() { seq2.release(); rnames.release(); quals.release(); lines.release(); block.release(); dirs.release(); rname_off.release(); dir_off.release(); cig_off.release(); len.release(); off.release();
-                         pos.release(); plans.release(); tasks.release(); res.release(); cig.release(); minscore.release(); cur.release(); hcur.release(); if (tables) (void)hipFree(tables); tables = nullptr; }
+        DBuf<moni_tables_t> tables;               // the index tables with extend's strand-1 complement (ext_complement)
     } ex;
     struct PmlBufs {        // pseudo-matching lengths (pml_api.inc): the last run's results, on the device until moni_pml_fetch
         DBuf<uint32_t> lens, mx, hits; uint64_t n_reads = 0, total = 0; bool valid = false;
-        void release() { lens.release(); mx.release(); hits.release(); valid = false; }
     } pml;
     struct LocBufs {        // exact-match count / locate (locate_api.inc): the last run's results, on the device until moni_locate_fetch; grow-only
         DBuf<moni_locate_res_t> res; DBuf<uint64_t> toe, cnt, off, pos, seq_off; DBuf<uint32_t> seq; uint64_t n_tasks = 0, n_occ = 0; bool valid = false;
-        void release() { res.release(); toe.release(); cnt.release(); off.release(); pos.release(); seq_off.release(); seq.release(); valid = false; }
     } loc;
     struct ScBufs {         // sequence counts (seqcount_api.inc): the last run's records and table, on the device until moni_seqcount_fetch; grow-only
         DBuf<moni_locate_res_t> lres; DBuf<moni_seqcount_res_t> res; DBuf<uint64_t> toe, cnt, off, counts; DBuf<uint32_t> k_lo;
         uint64_t n_tasks = 0, n_segs = 0; uint32_t n_seq = 0; bool valid = false;
-        void release() { lres.release(); res.release(); toe.release(); cnt.release(); off.release(); counts.release(); k_lo.release(); valid = false; }
     } sc;
     struct ApxBufs {        // k-mismatch queries (approx_api.inc): the last run's records, hits and positions, on the device until moni_approx_fetch; grow-only
         DBuf<moni_approx_res_t> res; DBuf<moni_approx_hit_t> slots, hits; DBuf<apx_ckpt_t> ckpt; DBuf<uint64_t> cnt, ck_off, hit_off, occ_cnt, occ_off, pos, seq_off; DBuf<uint32_t> seq;
         uint64_t n_tasks = 0, n_hits = 0, n_occ = 0; bool valid = false;
-        void release() { res.release(); slots.release(); hits.release(); ckpt.release(); cnt.release(); ck_off.release(); hit_off.release(); occ_cnt.release(); occ_off.release(); pos.release();
-                         seq_off.release(); seq.release(); valid = false; }
     } apx;
     struct MslBufs {        // matching statistics of long patterns (mslong_api.inc): pointers and lengths in pattern order, the segment table, the runs; grow-only
         DBuf<uint64_t> ptr, cnt, seg_off, head, run_idx; DBuf<uint32_t> lens, flags; DBuf<mslong_seg_t> segs; DBuf<mslong_state_t> states; DBuf<mslong_run_t> runs;
         DBuf<unsigned long long> counters;
-        void release() { ptr.release(); cnt.release(); seg_off.release(); head.release(); run_idx.release(); lens.release(); flags.release(); segs.release(); states.release(); runs.release(); counters.release(); }
     } msl;
     int n_cu_cached = 0, pe_occ_cached = 0;          // hipGetDeviceProperties / the occupancy query take a millisecond each: asked once per context
 };
@@ -236,10 +227,10 @@ struct moni_ctx {
 namespace {
 
 template <class Tp>
-int upload(Tp** d, const std::vector<Tp>& h, uint64_t& bytes) {
+int upload(DBuf<Tp>& d, const std::vector<Tp>& h, uint64_t& bytes) {
     size_t nb = h.size() * sizeof(Tp);
-    if (hipMalloc((void**)d, nb ? nb : 8) != hipSuccess) return MONI_ENOMEM;
-    if (nb && hipMemcpy(*d, h.data(), nb, hipMemcpyHostToDevice) != hipSuccess) return MONI_ENODEV;
+    if (d.alloc_bytes(nb ? nb : 8)) return MONI_ENOMEM;
+    if (nb && hipMemcpy(d.p, h.data(), nb, hipMemcpyHostToDevice) != hipSuccess) return MONI_ENODEV;
     bytes += nb;
     return MONI_OK;
 }
@@ -296,36 +287,35 @@ __global__ void __launch_bounds__(256) text_rebuild_kernel(const moni_row_t* __r
     wave_add(wrote, n_written);
 }
 
-// f.text == NULL: the text rebuilt on the device from the rows already uploaded (I->d_rows); checked against the BWT's own symbol counts
+// f.text == NULL: the text rebuilt on the device from the rows already uploaded (I->d_rows.p); checked against the BWT's own symbol counts
 static int rebuild_text(moni_index* I, const moni_flat_index_t& f, std::vector<uint8_t>& text) {
     const uint64_t r = f.r, n_text = f.n - 1, ns = 2 * r;
-    uint64_t *d_k[2] = {nullptr, nullptr}, *d_v[2] = {nullptr, nullptr}; uint8_t *d_heads = nullptr, *d_text = nullptr; void* d_tmp = nullptr; unsigned long long* d_cnt = nullptr;
-    auto done = [&](int code) { void* ps[] = {d_k[0], d_k[1], d_v[0], d_v[1], d_heads, d_text, d_tmp, d_cnt}; for (void* p : ps) if (p) (void)hipFree(p); return code; };
+    DBuf<uint64_t> d_k[2], d_v[2]; DBuf<uint8_t> d_heads, d_text, d_tmp; DBuf<unsigned long long> d_cnt;
     try {
         std::vector<uint64_t> hk(ns), hv(ns);
         for (uint64_t k = 0; k < r; ++k) { hk[2 * k] = f.ssa[k]; hv[2 * k] = k << 1; hk[2 * k + 1] = f.esa[k]; hv[2 * k + 1] = (k << 1) | 1; }
-        for (int x = 0; x < 2; ++x) if (hipMalloc((void**)&d_k[x], ns * 8) != hipSuccess || hipMalloc((void**)&d_v[x], ns * 8) != hipSuccess) return done(MONI_ENOMEM);
-        if (hipMalloc((void**)&d_heads, r + 8) != hipSuccess || hipMalloc((void**)&d_text, n_text + 16) != hipSuccess || hipMalloc((void**)&d_cnt, 8) != hipSuccess) return done(MONI_ENOMEM);
-        if (hipMemcpy(d_k[0], hk.data(), ns * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_v[0], hv.data(), ns * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_heads, f.heads, r, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_cnt, 0, 8) != hipSuccess || hipMemset(d_text, 0, n_text + 16) != hipSuccess) return done(MONI_ENODEV);
+        for (int x = 0; x < 2; ++x) if (d_k[x].alloc_exact(ns) || d_v[x].alloc_exact(ns)) return MONI_ENOMEM;
+        if (d_heads.alloc_exact(r + 8) || d_text.alloc_exact(n_text + 16) || d_cnt.alloc_exact(1)) return MONI_ENOMEM;
+        if (hipMemcpy(d_k[0].p, hk.data(), ns * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_v[0].p, hv.data(), ns * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_heads.p, f.heads, r, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_cnt.p, 0, 8) != hipSuccess || hipMemset(d_text.p, 0, n_text + 16) != hipSuccess) return MONI_ENODEV;
         size_t tmp_bytes = 0;
-        if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_k[0], d_k[1], d_v[0], d_v[1], (size_t)ns, 0u, 40u, (hipStream_t)0) != hipSuccess) return done(MONI_ENODEV);
-        if (hipMalloc(&d_tmp, tmp_bytes + 16) != hipSuccess) return done(MONI_ENOMEM);
-        if (rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_k[0], d_k[1], d_v[0], d_v[1], (size_t)ns, 0u, 40u, (hipStream_t)0) != hipSuccess) return done(MONI_ENODEV);
-        hipLaunchKernelGGL(text_rebuild_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, 0, I->d_rows, r, d_heads, d_k[1], d_v[1], ns, d_text, n_text, d_cnt);
+        if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_k[0].p, d_k[1].p, d_v[0].p, d_v[1].p, (size_t)ns, 0u, 40u, (hipStream_t)0) != hipSuccess) return MONI_ENODEV;
+        if (d_tmp.alloc_exact(tmp_bytes + 16)) return MONI_ENOMEM;
+        if (rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, d_k[0].p, d_k[1].p, d_v[0].p, d_v[1].p, (size_t)ns, 0u, 40u, (hipStream_t)0) != hipSuccess) return MONI_ENODEV;
+        hipLaunchKernelGGL(text_rebuild_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, 0, I->d_rows.p, r, d_heads.p, d_k[1].p, d_v[1].p, ns, d_text.p, n_text, d_cnt.p);
         unsigned long long wrote = 0;
         text.resize(n_text);
-        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&wrote, d_cnt, 8, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(text.data(), d_text, n_text, hipMemcpyDeviceToHost) != hipSuccess) return done(MONI_ENODEV);
-        if (wrote != n_text) { fprintf(stderr, "moni_hip: the BWT walk wrote %llu of %llu text positions: samples and runs disagree\n", wrote, (unsigned long long)n_text); return done(MONI_ERANGE); }
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&wrote, d_cnt.p, 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(text.data(), d_text.p, n_text, hipMemcpyDeviceToHost) != hipSuccess) return MONI_ENODEV;
+        if (wrote != n_text) { fprintf(stderr, "moni_hip: the BWT walk wrote %llu of %llu text positions: samples and runs disagree\n", wrote, (unsigned long long)n_text); return MONI_ERANGE; }
         // every symbol as often as the BWT holds it (the terminator is stored as byte 1 in the run heads and is not part of the text)
         uint64_t cnt[256] = {0}, bw[256] = {0};
         for (uint64_t i = 0; i < n_text; ++i) cnt[text[i]]++;
         for (uint64_t k = 0; k < r; ++k) bw[f.heads[k]] += f.starts[k + 1] - f.starts[k];
         cnt[1]++;
-        for (int b = 0; b < 256; ++b) if (cnt[b] != bw[b]) { fprintf(stderr, "moni_hip: the rebuilt text holds byte %d %llu times, the BWT %llu times\n", b, (unsigned long long)cnt[b], (unsigned long long)bw[b]); return done(MONI_ERANGE); }
-        return done(MONI_OK);
-    } catch (const std::bad_alloc&) { return done(MONI_ENOMEM); }
+        for (int b = 0; b < 256; ++b) if (cnt[b] != bw[b]) { fprintf(stderr, "moni_hip: the rebuilt text holds byte %d %llu times, the BWT %llu times\n", b, (unsigned long long)cnt[b], (unsigned long long)bw[b]); return MONI_ERANGE; }
+        return MONI_OK;
+    } catch (const std::bad_alloc&) { return MONI_ENOMEM; }
 }
 
 // The paired path keeps ~11 streams busy (staged kernels, transfers, up to PE_NSTREAM hand-over kernels of ~30 ms each); streams beyond the runtime's
@@ -361,7 +351,7 @@ int moni_index_create(const moni_flat_index_t* f, int device, moni_index_t** out
     std::vector<uint8_t> text;
     if (f->text) text.assign(f->text, f->text + (f->n - 1));
     else {
-        if ((rc = upload(&I->d_rows, img.rows, I->bytes)) || (rc = rebuild_text(I, *f, text))) { moni_index_destroy(I); return rc; }
+        if ((rc = upload(I->d_rows, img.rows, I->bytes)) || (rc = rebuild_text(I, *f, text))) { moni_index_destroy(I); return rc; }
     }
     I->h_text = text;
     text.resize(text.size() + 16, 0);            // text_byte() reads aligned 8-byte words
@@ -382,12 +372,12 @@ int moni_index_create(const moni_flat_index_t* f, int device, moni_index_t** out
     I->hix.n_text = f->n - 1; I->hix.w = f->w; I->hix.text = I->h_text.data();
     I->hix.seq_starts.assign(f->seq_starts, f->seq_starts + f->n_seq + 1);
     I->hix.lift_seqs = lt.seqs; I->hix.lift_runs = lt.runs;
-    if ((rc = upload(&I->d_pdir, lt.pdir, I->bytes)) || (rc = upload(&I->d_lift_seqs, lt.seqs, I->bytes)) || (rc = upload(&I->d_lift_runs, lt.runs, I->bytes)) || (rc = upload(&I->d_tables, tv, I->bytes)) || (!I->d_rows && (rc = upload(&I->d_rows, img.rows, I->bytes))) || (rc = upload(&I->d_frows, img.frows, I->bytes)) ||
-        (rc = upload(&I->d_cr, img.cr, I->bytes)) || (rc = upload(&I->d_recs, img.recs, I->bytes)) ||
-        (rc = upload(&I->d_phi, img.phi, I->bytes)) || (rc = upload(&I->d_phi_inv, img.phi_inv, I->bytes)) ||
-        (rc = upload(&I->d_phi_dir, img.phi_dir, I->bytes)) || (rc = upload(&I->d_phi_inv_dir, img.phi_inv_dir, I->bytes)) ||
-        (rc = upload(&I->d_text, text, I->bytes)) || (rc = upload(&I->d_seq_starts, img.seq_starts, I->bytes)) ||
-        (rc = upload(&I->d_name_id, name_id, I->bytes)) || (rc = upload(&I->d_snames, sname_blob, I->bytes)) || (rc = upload(&I->d_sname_off, sname_off, I->bytes))) {
+    if ((rc = upload(I->d_pdir, lt.pdir, I->bytes)) || (rc = upload(I->d_lift_seqs, lt.seqs, I->bytes)) || (rc = upload(I->d_lift_runs, lt.runs, I->bytes)) || (rc = upload(I->d_tables, tv, I->bytes)) || (!I->d_rows.p && (rc = upload(I->d_rows, img.rows, I->bytes))) || (rc = upload(I->d_frows, img.frows, I->bytes)) ||
+        (rc = upload(I->d_cr, img.cr, I->bytes)) || (rc = upload(I->d_recs, img.recs, I->bytes)) ||
+        (rc = upload(I->d_phi, img.phi, I->bytes)) || (rc = upload(I->d_phi_inv, img.phi_inv, I->bytes)) ||
+        (rc = upload(I->d_phi_dir, img.phi_dir, I->bytes)) || (rc = upload(I->d_phi_inv_dir, img.phi_inv_dir, I->bytes)) ||
+        (rc = upload(I->d_text, text, I->bytes)) || (rc = upload(I->d_seq_starts, img.seq_starts, I->bytes)) ||
+        (rc = upload(I->d_name_id, name_id, I->bytes)) || (rc = upload(I->d_snames, sname_blob, I->bytes)) || (rc = upload(I->d_sname_off, sname_off, I->bytes))) {
         moni_index_destroy(I);
         return rc;
     }
@@ -395,10 +385,10 @@ int moni_index_create(const moni_flat_index_t* f, int device, moni_index_t** out
         const uint64_t n_text = f->n - 1, n_words = n_text / 32 + 2;
         I->exc_sh = text2_exc_shift(n_text, MONI_EXC_BITS);
         I->exc_words = (uint32_t)((((n_text >> I->exc_sh) + 1) + 31) / 32);
-        if (hipMalloc((void**)&I->d_text2, n_words * 8) != hipSuccess || hipMalloc((void**)&I->d_exc, (size_t)I->exc_words * 4 + 4) != hipSuccess) { moni_index_destroy(I); return MONI_ENOMEM; }
+        if (I->d_text2.alloc_exact(n_words) || I->d_exc.alloc_exact((size_t)I->exc_words + 1)) { moni_index_destroy(I); return MONI_ENOMEM; }
         I->bytes += n_words * 8 + (uint64_t)I->exc_words * 4;
-        if (hipMemset(I->d_exc, 0, (size_t)I->exc_words * 4 + 4) != hipSuccess) { moni_index_destroy(I); return MONI_ENODEV; }
-        hipLaunchKernelGGL(text2_build_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, 0, I->d_text, n_text, n_words, I->d_text2, I->d_exc, I->exc_sh);
+        if (hipMemset(I->d_exc.p, 0, (size_t)I->exc_words * 4 + 4) != hipSuccess) { moni_index_destroy(I); return MONI_ENODEV; }
+        hipLaunchKernelGGL(text2_build_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, 0, I->d_text.p, n_text, n_words, I->d_text2.p, I->d_exc.p, I->exc_sh);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { moni_index_destroy(I); return MONI_ENODEV; }
     }
     *out = I;
@@ -494,9 +484,7 @@ int moni_index_load(const char* path, int device, moni_index_t** out) {
 
 void moni_index_destroy(moni_index_t* I) {
     if (!I) return;
-    (void)hipSetDevice(I->device);
-    void* ps[] = {I->d_tables, I->d_rows, I->d_frows, I->d_cr, I->d_recs, I->d_phi, I->d_phi_inv, I->d_phi_dir, I->d_phi_inv_dir, I->d_text, I->d_text2, I->d_exc, I->d_seq_starts, I->d_name_id, I->d_snames, I->d_sname_off, I->d_lift_seqs, I->d_lift_runs, I->d_pdir};
-    for (void* p : ps) if (p) (void)hipFree(p);
+    (void)hipSetDevice(I->device);          // the members free their device memory: on this index's GPU
     delete I;
 }
 uint64_t moni_index_n(const moni_index_t* I) { return I ? I->K.n : 0; }
@@ -515,11 +503,10 @@ int moni_ctx_create(moni_index_t* I, moni_ctx_t** out) {
     c->idx = I;
     if (const char* v = getenv("MONI_MS_VARIANT")) c->ms_variant = atoi(v);
     if (const char* v = getenv("MONI_EXTZ_LDS")) c->extz_lds = atoi(v);
-    for (int i = 0; i < EV_N; ++i) { c->ev[i] = nullptr; c->ev_valid[i] = false; }
-    bool ok = hipStreamCreate(&c->stream) == hipSuccess;
-    for (int i = 0; ok && i < EV_N; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
-    ok = ok && hipMalloc((void**)&c->d_small, sizeof(occ_small_t)) == hipSuccess && hipMalloc((void**)&c->d_counters, 4 * sizeof(unsigned long long)) == hipSuccess &&
-         hipMemset(c->d_small, 0, sizeof(occ_small_t)) == hipSuccess && hipMemset(c->d_counters, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
+    bool ok = hipStreamCreate(&c->stream.h) == hipSuccess;
+    for (int i = 0; ok && i < EV_N; ++i) ok = hipEventCreate(&c->ev[i].h) == hipSuccess;
+    ok = ok && c->d_small.alloc_exact(1) == MONI_OK && c->d_counters.alloc_exact(4) == MONI_OK &&
+         hipMemset(c->d_small.p, 0, sizeof(occ_small_t)) == hipSuccess && hipMemset(c->d_counters.p, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) { fprintf(stderr, "moni_hip: context creation failed on device %d\n", I->device); moni_ctx_destroy(c); return MONI_ENODEV; }
     *out = c;
     return MONI_OK;
@@ -527,37 +514,14 @@ int moni_ctx_create(moni_index_t* I, moni_ctx_t** out) {
 
 void moni_ctx_destroy(moni_ctx_t* c) {
     if (!c) return;
-    (void)hipSetDevice(c->idx->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& x : c->stash) { x.seq.release(); x.offs.release(); x.blk.release(); }
-    c->blk.release(); c->seq.release(); c->offs.release(); c->ptr.release(); c->pat.release(); c->pflag.release(); c->cnt_m.release(); c->cnt_s.release(); c->mem_slots.release(); c->tot.release();
-    c->read_mem_off.release(); c->mems.release(); c->aux.release(); c->lowers.release(); c->tmp.release();
-    c->occ_cnt.release(); c->occ_off.release(); c->occs.release(); c->mems_compact.release(); c->long_list.release(); c->pool.release(); c->scan_tmp.release();
-    for (int x = 0; x < AK_NSET; ++x) c->af[x].release();
-    for (int x = 0; x < PE_NSET; ++x) c->af_pe[x].release();
-    for (int x = 0; x < PE_NSTREAM; ++x) if (c->pe_stream[x]) (void)hipStreamDestroy(c->pe_stream[x]);
-    c->af_ctr_host.release(); c->pe_hcur.release(); c->fb_all.release();
-    c->dp_q.release(); c->dp_t.release(); c->dp_dir.release(); c->dp_tasks.release(); c->dp_res.release(); c->dp_cig.release();
-    c->dp_off.release(); c->dp_ws.release(); c->dp_big.release(); c->dp_dir_big.release(); c->ak_slots.release(); c->ak_waves.release(); c->ak_cursors.release(); c->ak_rnames.release(); c->ak_quals.release(); c->ak_rname_off.release(); c->ak_txt.release(); c->ak_mapq_tab.release(); c->h_txt.release(); c->h_recs.release(); c->h_cig.release(); c->h_alt.release(); c->h_md.release();
-    for (auto& ob : c->pieces) ob.release();
-    for (int x = 0; x < AK_NSET; ++x) if (c->ak_stream[x]) (void)hipStreamDestroy(c->ak_stream[x]);
-    for (int x = 0; x < AK_NSET; ++x) if (c->fb_stream[x]) (void)hipStreamDestroy(c->fb_stream[x]);
-    for (auto e : c->ak_fin) (void)hipEventDestroy(e);
-    for (auto e : c->af_ev) (void)hipEventDestroy(e);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    for (auto e : c->ak_begin) (void)hipEventDestroy(e);
-    for (auto e : c->ak_done) (void)hipEventDestroy(e);
-    c->ex.release(); c->pml.release(); c->loc.release(); c->sc.release(); c->apx.release(); c->msl.release();
-    c->ak_recs.release(); c->ak_cig.release(); c->ak_alt.release(); c->ak_minscore.release(); c->pe.release();
-    if (c->d_ak_cursors) (void)hipFree(c->d_ak_cursors);
-    if (c->out_buf) (void)hipHostFree(c->out_buf);
-    for (int x = 0; x < AK_NSET; ++x) c->gather_tmp[x].release();
-    c->ak_block.release(); c->ak_dev_len.release(); c->ak_dev_off.release(); c->ak_dev_pos.release(); c->ak_dev_sum.release(); c->h_sum.release();
-    if (c->d_small) (void)hipFree(c->d_small);
-    if (c->d_counters) (void)hipFree(c->d_counters);
-    for (int i = 0; i < EV_N; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    (void)hipSetDevice(c->idx->device);          // the members free their memory, streams and events: on this context's GPU,
+    if (c->stream) (void)hipStreamSynchronize(c->stream);      // ... with its stream idle
     delete c;
+}
+
+// A new batch is resident (uploaded, or swapped in): what the last runs left in the context describes another batch
+static void results_invalidate(moni_ctx* c) {
+    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false; c->apx.valid = false;
 }
 
 static int reads_upload(moni_ctx* c, const moni_read_batch_t* b, bool keep_host_copy);
@@ -601,7 +565,7 @@ static int reads_upload(moni_ctx* c, const moni_read_batch_t* b, bool keep_host_
     c->h_blk.swap(blk);
     if (keep_host_copy) { c->h_seq.assign(b->seq + b->offsets[0], b->seq + b->offsets[0] + total); c->h_offs = rel; }
     else { c->h_seq.clear(); c->h_offs.clear(); }
-    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false; c->apx.valid = false;
+    results_invalidate(c);
     return MONI_OK;
 }
 
@@ -610,17 +574,15 @@ int moni_reads_swap(moni_ctx_t* c, uint32_t slot) {
     HIPCHK(hipSetDevice(c->idx->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     try { if (c->stash.size() <= slot) c->stash.resize(slot + 1); } catch (const std::bad_alloc&) { return MONI_ENOMEM; }
-    moni_ctx::Stash& x = c->stash[slot];
-    std::swap(c->seq, x.seq); std::swap(c->offs, x.offs); std::swap(c->blk, x.blk); c->h_blk.swap(x.h_blk); std::swap(c->n_reads, x.n_reads); std::swap(c->total_len, x.total_len); std::swap(c->max_len, x.max_len);
-    c->h_seq.swap(x.h_seq); c->h_offs.swap(x.h_offs);
-    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false; c->apx.valid = false;
+    std::swap(static_cast<ResidentBatch&>(*c), c->stash[slot]);
+    results_invalidate(c);
     return MONI_OK;
 }
 
 // tabs: the byte tables pack_kernel derives strand 1 with (default: the index's own, kpbseq.h:120-137; extend mode brings its complement)
 static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr) {
     moni_index* I = c->idx;
-    if (!tabs) tabs = I->d_tables;
+    if (!tabs) tabs = I->d_tables.p;
     const uint64_t n_tasks = 2 * c->n_reads;
     int rc;
     if (c->h_blk.empty()) return MONI_EINVAL;
@@ -632,7 +594,7 @@ static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr) {
     if (n_tasks) {
 #define MS_LAUNCH(NCH, MINW) do { const uint64_t nl = (n_tasks + (NCH) - 1) / (NCH); \
         hipLaunchKernelGGL((ms_lf_kernel<NCH, MINW>), dim3((unsigned)((nl + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, \
-                           I->K, tabs, I->d_rows, I->d_frows, I->d_cr, I->d_recs, c->pat.p, c->offs.p, c->blk.p, n_tasks, c->ptr.p, c->d_counters); } while (0)
+                           I->K, tabs, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p, n_tasks, c->ptr.p, c->d_counters.p); } while (0)
         switch (c->ms_variant) {
             case 1: MS_LAUNCH(1, 8); break;
             case 2: MS_LAUNCH(2, 8); break;
@@ -651,7 +613,7 @@ static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr) {
 int moni_ms_run(moni_ctx_t* c) {
     if (!c) return MONI_EINVAL;
     HIPCHK(hipSetDevice(c->idx->device));
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
     rec(c, EV_ALL0);
     int rc = ms_launch(c);
     rec(c, EV_ALL1);
@@ -693,21 +655,20 @@ int moni_ms_lengths_batch(moni_ctx_t* c, const moni_read_batch_t* b, uint64_t* p
     if (!nr) return MONI_OK;
     DBuf<uint32_t> lens;
     if ((rc = lens.ensure(c->total_len + 1))) return rc;
-    hipLaunchKernelGGL(ms_len_kernel, dim3((unsigned)((nr + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, I->d_text, c->pat.p, c->offs.p, c->blk.p, nr,
+    hipLaunchKernelGGL(ms_len_kernel, dim3((unsigned)((nr + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, I->d_text.p, c->pat.p, c->offs.p, c->blk.p, nr,
                        c->ptr.p, lens.p);
     try {
         std::vector<uint64_t> h(c->h_blk.back().x);
         std::vector<uint32_t> hl(c->total_len + 1);
         bool ok = hipStreamSynchronize(c->stream) == hipSuccess && (h.empty() || hipMemcpy(h.data(), c->ptr.p, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) &&
                   hipMemcpy(hl.data(), lens.p, c->total_len * 4, hipMemcpyDeviceToHost) == hipSuccess;
-        lens.release();
         if (!ok) return MONI_ENODEV;
         const uint64_t base = b->offsets[0];
         for (uint64_t rd = 0; rd < nr; ++rd) {
             const uint64_t off = b->offsets[rd] - base, m = b->offsets[rd + 1] - b->offsets[rd];
             for (uint64_t k = 0; k < m; ++k) { pointers[off + k] = ws_ptr_host(c, h, 2 * rd, m - 1 - k); lengths[off + k] = hl[off + k]; }
         }
-    } catch (const std::bad_alloc&) { lens.release(); return MONI_ENOMEM; }
+    } catch (const std::bad_alloc&) { return MONI_ENOMEM; }
     return MONI_OK;
 }
 
@@ -724,8 +685,8 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
     uint64_t* tot = c->tot.p; uint64_t* rmo = c->read_mem_off.p;
     moni_u64x2* slots = c->mem_slots.p;
     const uint64_t* offs = c->offs.p;
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, 4 * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_small, 0, sizeof(occ_small_t), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_small.p, 0, sizeof(occ_small_t), c->stream));
     rec(c, EV_ALL0);
     if ((rc = ms_launch(c))) return rc;                              // (allocates pat / ptr)
     const uint64_t* pat = c->pat.p; const uint64_t* ptr = c->ptr.p;
@@ -733,12 +694,12 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
     const uint32_t split_on = prm->report_mems ? 0u : 1u;
     // the 2-bit comparison holds a lane's pattern in LDS: 5 words (160 bases) or 8 (256); reads beyond that compare bytes (MONI_MEM_BYTES=1: all do)
     static const bool mem_bytes = getenv("MONI_MEM_BYTES") != nullptr;
-    const uint64_t* text2 = mem_bytes ? nullptr : I->d_text2;
+    const uint64_t* text2 = mem_bytes ? nullptr : I->d_text2.p;
 #define MEM_LAUNCH(EMIT, RMO, MEMS, AUX) do { \
-        if (c->max_len <= 160) hipLaunchKernelGGL((mem_kernel<EMIT, 5>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text, text2, I->d_exc, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
-                                                  n_tasks, ptr, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters); \
-        else hipLaunchKernelGGL((mem_kernel<EMIT, 8>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text, text2, I->d_exc, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
-                                n_tasks, ptr, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters); } while (0)
+        if (c->max_len <= 160) hipLaunchKernelGGL((mem_kernel<EMIT, 5>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, text2, I->d_exc.p, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
+                                                  n_tasks, ptr, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters.p); \
+        else hipLaunchKernelGGL((mem_kernel<EMIT, 8>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, text2, I->d_exc.p, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
+                                n_tasks, ptr, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters.p); } while (0)
     rec(c, EV_MC0);
     if (n_tasks)
         MEM_LAUNCH(false, (const uint64_t*)nullptr, (moni_mem_t*)nullptr, (uint32_t*)nullptr);
@@ -759,13 +720,13 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
         MEM_LAUNCH(true, (const uint64_t*)rmo, mems, aux);
     rec(c, EV_ME1);
     occ_args_t A;
-    A.phi.recs = I->d_phi; A.phi.dir = I->d_phi_dir; A.phi_inv.recs = I->d_phi_inv; A.phi_inv.dir = I->d_phi_inv_dir;
-    A.text = I->d_text;
-    A.seq_starts = I->d_seq_starts; A.name_id = I->d_name_id; A.mems = mems; A.aux = aux; A.read_mem_off = rmo;
+    A.phi.recs = I->d_phi.p; A.phi.dir = I->d_phi_dir.p; A.phi_inv.recs = I->d_phi_inv.p; A.phi_inv.dir = I->d_phi_inv_dir.p;
+    A.text = I->d_text.p;
+    A.seq_starts = I->d_seq_starts.p; A.name_id = I->d_name_id.p; A.mems = mems; A.aux = aux; A.read_mem_off = rmo;
     A.n_mems = n_mems; A.occs = nullptr; A.tmp = nullptr; A.lowers = c->lowers.p; A.tmp_cap = c->tmp_cap;
     A.filter_seeds = prm->filter_seeds; A.n_seeds_thr = prm->n_seeds_thr; A.pool_rows = c->pool_rows; A.pool = c->pool.p;
-    A.pool_next = &c->d_small->pool_next; A.error_flag = &c->d_small->error_flag; A.counters = c->d_counters;
-    A.long_list = c->long_list.p; A.small = c->d_small;
+    A.pool_next = &c->d_small.p->pool_next; A.error_flag = &c->d_small.p->error_flag; A.counters = c->d_counters.p;
+    A.long_list = c->long_list.p; A.small = c->d_small.p;
     const unsigned grid_m = (unsigned)((n_mems + MS_BLOCK - 1) / MS_BLOCK);
     // The per-genome filter needs a row of per-name counters only for seeds with more than n_seeds_thr occurrences;
     // rows come from a bump-allocated pool.  If a pass asks for more rows than the pool holds, the pool is grown to the
@@ -776,12 +737,12 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
     for (int pool_tries = 0, ovf_tries = 0;;) {
         if ((rc = c->tmp.ensure(need * c->tmp_cap + c->ovf_cap + 1))) return rc;
         A.tmp = c->tmp.p; A.pool = c->pool.p; A.pool_rows = c->pool_rows;
-        HIPCHK(hipMemsetAsync(c->d_small, 0, sizeof small, c->stream));
-        HIPCHK(hipMemsetAsync(c->d_counters + 2, 0, sizeof(unsigned long long), c->stream));
+        HIPCHK(hipMemsetAsync(c->d_small.p, 0, sizeof small, c->stream));
+        HIPCHK(hipMemsetAsync(c->d_counters.p + 2, 0, sizeof(unsigned long long), c->stream));
         rec(c, EV_PC0);
         if (n_mems) hipLaunchKernelGGL(occ_kernel, dim3(grid_m), dim3(MS_BLOCK), 0, c->stream, I->K, A);
         rec(c, EV_PC1);
-        HIPCHK(hipMemcpyAsync(&small, c->d_small, sizeof small, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&small, c->d_small.p, sizeof small, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         ++attempts;
         if (small.error_flag) {
@@ -797,14 +758,14 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
     // the long lists: the listed seeds are walked again into their overflow space (they need no more pool rows than the count pass took)
     rec(c, EV_PE0);
     if (small.n_long) {
-        HIPCHK(hipMemsetAsync(c->d_small, 0, 8, c->stream));
+        HIPCHK(hipMemsetAsync(c->d_small.p, 0, 8, c->stream));
         hipLaunchKernelGGL(occ_long_kernel, dim3((small.n_long + MS_BLOCK - 1) / MS_BLOCK), dim3(MS_BLOCK), 0, c->stream, I->K, A, small.n_long);
     }
     rec(c, EV_PE1);
     rec(c, EV_ALL1);
     if (small.n_long) {
         uint32_t flag[2] = {0, 0};
-        HIPCHK(hipMemcpyAsync(flag, c->d_small, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(flag, c->d_small.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         if (flag[1]) { fprintf(stderr, "moni_hip: per-genome counter pool exhausted (%u rows)\n", c->pool_rows); return MONI_ENOMEM; }
     }
@@ -881,16 +842,16 @@ int moni_phi_lcp_batch(moni_ctx_t* c, const uint64_t* pos, uint64_t n, int inver
     moni_index* I = c->idx;
     HIPCHK(hipSetDevice(I->device));
     if (!n) return MONI_OK;
-    uint64_t* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, 3 * n * 8));
-    if (hipMemcpy(d, pos, n * 8, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return MONI_ENODEV; }
+    DBuf<uint64_t> buf;
+    if (buf.alloc_exact(3 * n)) { fprintf(stderr, "moni_hip: no device memory for %llu positions\n", (unsigned long long)n); return MONI_ENODEV; }      // (MONI_ENODEV: what this entry point has always reported)
+    uint64_t* const d = buf.p;
+    if (hipMemcpy(d, pos, n * 8, hipMemcpyHostToDevice) != hipSuccess) return MONI_ENODEV;
     phi_tab_t P;
-    P.recs = inverse ? I->d_phi_inv : I->d_phi;
-    P.dir = inverse ? I->d_phi_inv_dir : I->d_phi_dir;
+    P.recs = inverse ? I->d_phi_inv.p : I->d_phi.p;
+    P.dir = inverse ? I->d_phi_inv_dir.p : I->d_phi_dir.p;
     hipLaunchKernelGGL(phi_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, I->K, P, d, n, d + n, d + 2 * n);
     const bool ok = hipStreamSynchronize(c->stream) == hipSuccess && hipMemcpy(out_pos, d + n, n * 8, hipMemcpyDeviceToHost) == hipSuccess &&
                     hipMemcpy(out_lcp, d + 2 * n, n * 8, hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(d);
     return ok ? MONI_OK : MONI_ENODEV;
 }
 
@@ -913,7 +874,7 @@ int moni_last_counters(moni_ctx_t* c, uint64_t out[4]) {
     if (!c || !out) return MONI_EINVAL;
     HIPCHK(hipSetDevice(c->idx->device));
     unsigned long long h[4];
-    HIPCHK(hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h, c->d_counters.p, sizeof(h), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; ++i) out[i] = h[i];
     return MONI_OK;
 }
@@ -994,14 +955,14 @@ static int genome_hi_lo(moni_ctx* c, const moni_align_params_t& prm, std::vector
     if (!n_mems) return MONI_OK;
     occ_args_t A;
     memset(&A, 0, sizeof A);
-    A.text = I->d_text;
-    A.phi.recs = I->d_phi; A.phi.dir = I->d_phi_dir; A.phi_inv.recs = I->d_phi_inv; A.phi_inv.dir = I->d_phi_inv_dir;
-    A.seq_starts = I->d_seq_starts; A.name_id = I->d_name_id; A.mems = c->mems.p; A.aux = c->aux.p; A.read_mem_off = c->read_mem_off.p;
+    A.text = I->d_text.p;
+    A.phi.recs = I->d_phi.p; A.phi.dir = I->d_phi_dir.p; A.phi_inv.recs = I->d_phi_inv.p; A.phi_inv.dir = I->d_phi_inv_dir.p;
+    A.seq_starts = I->d_seq_starts.p; A.name_id = I->d_name_id.p; A.mems = c->mems.p; A.aux = c->aux.p; A.read_mem_off = c->read_mem_off.p;
     A.n_mems = n_mems; A.lowers = c->lowers.p; A.filter_seeds = prm.filter_seeds; A.n_seeds_thr = prm.n_seeds_thr;
     const uint64_t chunk = std::max<uint64_t>(1, (256ull << 20) / (4ull * I->K.n_seq));          // rows of per-name counters: 256 MB at a time
     DBuf<uint32_t> rows; DBuf<uint64_t> hl;
     int rc;
-    if ((rc = rows.ensure(std::min(chunk, n_mems) * I->K.n_seq + 1)) || (rc = hl.ensure(n_mems + 1))) { rows.release(); hl.release(); return rc; }
+    if ((rc = rows.ensure(std::min(chunk, n_mems) * I->K.n_seq + 1)) || (rc = hl.ensure(n_mems + 1))) return rc;
     bool ok = true;
     for (uint64_t g0 = 0; g0 < n_mems && ok; g0 += chunk) {
         const uint64_t g1 = std::min(n_mems, g0 + chunk);
@@ -1009,7 +970,6 @@ static int genome_hi_lo(moni_ctx* c, const moni_align_params_t& prm, std::vector
         if (ok) hipLaunchKernelGGL(genome_kernel, dim3((unsigned)((g1 - g0 + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, A, g0, g1, rows.p, hl.p);
     }
     ok = ok && hipStreamSynchronize(c->stream) == hipSuccess && hipMemcpy(out.data(), hl.p, n_mems * 8, hipMemcpyDeviceToHost) == hipSuccess;
-    rows.release(); hl.release();
     return ok ? MONI_OK : MONI_ENODEV;
 }
 
@@ -1119,15 +1079,10 @@ int moni_align_stream(moni_ctx_t* c, const moni_read_batch_t* b, const uint8_t* 
     int rc = moni_align_batch(c, b, names, name_off, quals, prm, &tmp, &len, stats);
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->idx->device));
-    if (c->out_cap < len + 1) {
-        char* nb = nullptr;
-        if (hipHostMalloc((void**)&nb, len + 1, hipHostMallocDefault) != hipSuccess) { free(tmp); return MONI_ENOMEM; }
-        if (c->out_buf) (void)hipHostFree(c->out_buf);
-        c->out_buf = nb; c->out_cap = len + 1;
-    }
-    memcpy(c->out_buf, tmp, len); c->out_buf[len] = 0;
+    if (c->out_buf.ensure_keep(len + 1, 0)) { free(tmp); return MONI_ENOMEM; }
+    memcpy(c->out_buf.p, tmp, len); c->out_buf.p[len] = 0;
     free(tmp);
-    *sam = c->out_buf; *sam_len = len;
+    *sam = c->out_buf.p; *sam_len = len;
     return MONI_OK;
 }
 
@@ -1209,15 +1164,12 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         double host_busy = 0;
         // the batch's text is assembled as the sub-batches finish (inside the overlapped host stage), as long as no read
         // has been handed back
-        char* abuf = ctx_out ? c->out_buf : nullptr; size_t acap = ctx_out ? c->out_cap : 0, alen = 0; uint64_t eager_upto = 0; bool eager_ok = true, eager_oom = false;
+        char* abuf = ctx_out ? c->out_buf.p : nullptr; size_t acap = ctx_out ? c->out_buf.cap : 0, alen = 0; uint64_t eager_upto = 0; bool eager_ok = true, eager_oom = false;
         auto drop_abuf = [&]() { if (!ctx_out) free(abuf); abuf = nullptr; };
         auto grow_abuf = [&](size_t cap) -> bool {        // keeps the first alen bytes
             if (!ctx_out) { char* nb = (char*)realloc(abuf, cap); if (!nb) return false; abuf = nb; acap = cap; return true; }
-            char* nb = nullptr;
-            if (hipHostMalloc((void**)&nb, cap, hipHostMallocDefault) != hipSuccess) return false;
-            if (abuf && alen) memcpy(nb, abuf, alen);
-            if (abuf) (void)hipHostFree(abuf);
-            abuf = nb; acap = cap; c->out_buf = nb; c->out_cap = cap;
+            if (c->out_buf.ensure_keep(cap, alen)) return false;
+            abuf = c->out_buf.p; acap = c->out_buf.cap;
             return true;
         };
         double prof[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -1234,7 +1186,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         if (gpu_text) {
             const uint64_t nb_names = name_off[NR] - name_off[0], nb_q = quals ? b->offsets[NR] - b->offsets[0] : 0;
             if ((rc = c->ak_rnames.ensure(nb_names + 16)) || (rc = c->ak_rname_off.ensure(NR + 1)) || (rc = c->ak_quals.ensure(nb_q + 16))) return rc;
-            if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+            if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream.h, hipStreamNonBlocking));
             uploader = std::thread([&, nb_names, nb_q]() {
                 if (hipSetDevice(I->device) != hipSuccess) { rc_up = MONI_ENODEV; return; }
                 std::vector<uint64_t> rel(NR + 1);
@@ -1323,12 +1275,12 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         }
         // the launches alternate between the context's stream and one more: HIP multiplexes streams onto a handful of hardware queues
         // (4 by default), and two streams that land on the same queue run their kernels one after the other
-        for (int x = 0; x < AK_NSET; ++x) if (!c->ak_stream[x]) HIPCHK(hipStreamCreateWithFlags(&c->ak_stream[x], hipStreamNonBlocking));
-        if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-        while (c->ak_done.size() < n_sub) { hipEvent_t e0, e1, e2; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventCreate(&e2));
-                                            c->ak_begin.push_back(e0); c->ak_done.push_back(e1); c->ak_fin.push_back(e2); }
-        for (int x = 0; x < AK_NSET; ++x) if (use_fast && !c->fb_stream[x]) HIPCHK(hipStreamCreateWithFlags(&c->fb_stream[x], hipStreamNonBlocking));
-        while (c->af_ev.size() < 3 * n_sub) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); c->af_ev.push_back(e); }
+        for (int x = 0; x < AK_NSET; ++x) if (!c->ak_stream[x]) HIPCHK(hipStreamCreateWithFlags(&c->ak_stream[x].h, hipStreamNonBlocking));
+        if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream.h, hipStreamNonBlocking));
+        while (c->ak_done.size() < n_sub) { Event e0, e1, e2; HIPCHK(hipEventCreate(&e0.h)); HIPCHK(hipEventCreate(&e1.h)); HIPCHK(hipEventCreate(&e2.h));
+                                            c->ak_begin.push_back(std::move(e0)); c->ak_done.push_back(std::move(e1)); c->ak_fin.push_back(std::move(e2)); }
+        for (int x = 0; x < AK_NSET; ++x) if (use_fast && !c->fb_stream[x]) HIPCHK(hipStreamCreateWithFlags(&c->fb_stream[x].h, hipStreamNonBlocking));
+        while (c->af_ev.size() < 3 * n_sub) { Event e; HIPCHK(hipEventCreate(&e.h)); c->af_ev.push_back(std::move(e)); }
         if (use_fast) { if ((rc = c->fb_all.ensure(16 * n_sub + n_sub * (sub_reads + 1) + 16))) return rc; HIPCHK(hipMemsetAsync(c->fb_all.p, 0, 16 * n_sub * sizeof(uint32_t), c->stream)); }
         HIPCHK(hipMemsetAsync(c->ak_cursors.p, 0, (AK_CUR * n_sub + AK_CUR) * sizeof(unsigned long long), c->stream));
         HIPCHK(hipMemcpyAsync(c->ak_minscore.p, msc.data(), msc.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -1472,10 +1424,10 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
             A.P.smatch = prm->smatch; A.P.gapo = prm->gapo; A.P.gapo2 = prm->gapo2; A.P.gape = prm->gape; A.P.gape2 = prm->gape2;
             A.P.max_dist_x = prm->max_dist_x; A.P.max_dist_y = prm->max_dist_y; A.P.max_iter = prm->max_iter; A.P.max_pred = prm->max_pred;
             A.P.min_chain_score = prm->min_chain_score; A.P.min_chain_length = prm->min_chain_length;
-            A.P.n_text = I->K.n_text; A.P.n_seq = I->K.n_seq; A.P.seq_starts = I->d_seq_starts;
-            A.P.lift_seqs = I->d_lift_seqs; A.P.lift_runs = I->d_lift_runs; A.P.pdir = I->d_pdir;
+            A.P.n_text = I->K.n_text; A.P.n_seq = I->K.n_seq; A.P.seq_starts = I->d_seq_starts.p;
+            A.P.lift_seqs = I->d_lift_seqs.p; A.P.lift_runs = I->d_lift_runs.p; A.P.pdir = I->d_pdir.p;
             A.D.sc_mch = prm->smatch; A.D.sc_mis = -prm->smismatch; A.D.sc_N = -prm->gape; A.D.wild = 4; A.D.qo = prm->gapo; A.D.e = prm->gape;
-            A.D.end_bonus = prm->end_bonus; A.D.reads = c->seq.p; A.D.text = I->d_text; A.D.n_text = I->K.n_text;
+            A.D.end_bonus = prm->end_bonus; A.D.reads = c->seq.p; A.D.text = I->d_text.p; A.D.n_text = I->K.n_text;
             A.D.reads_limit = (c->total_len + 8) & ~7ull; A.D.text_limit = (I->K.n_text + 8) & ~7ull;       // both buffers carry 16 bytes of padding
             A.mems = c->mems.p; A.occs = c->tmp.p; A.read_mem_off = c->read_mem_off.p; A.offs = c->offs.p;
             A.min_score_of_len = c->ak_minscore.p; A.max_len = (uint32_t)c->max_len + 1; A.read_lo = r0; A.n_reads = nr;
@@ -1486,7 +1438,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
             A.alt_cap = alt_per; A.md_pool = c->h_md.p + k * md_per; A.md_cap = md_per; A.cursors = c->ak_cursors.p + AK_CUR * k;
             if (gpu_text) {
                 A.fmt.rnames = c->ak_rnames.p; A.fmt.rname_off = c->ak_rname_off.p; A.fmt.quals = quals ? c->ak_quals.p : nullptr;
-                A.fmt.snames = I->d_snames; A.fmt.sname_off = I->d_sname_off; A.fmt.mapq_tab = c->ak_mapq_tab.p; A.fmt.mapq_tab_n = 8192;
+                A.fmt.snames = I->d_snames.p; A.fmt.sname_off = I->d_sname_off.p; A.fmt.mapq_tab = c->ak_mapq_tab.p; A.fmt.mapq_tab_n = 8192;
                 A.fmt.min_len = (int32_t)prm->min_len; A.fmt.smatch = prm->smatch; A.fmt.smismatch = prm->smismatch;
                 A.fmt.txt_pool = c->ak_txt.p + k * txt_per; A.fmt.txt_cap = (use_fast && nr > 0) ? txt_per / (AF_TXT_SHARDS + 1) : txt_per;
             }
@@ -1506,7 +1458,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                 G.chunks = S.chunks.p; G.chunk_cap = af_chunk_cap; G.dirs = S.dirs.p; G.dirs_cap = af_dirs_cap; G.tb_task = S.tb_task.p; G.tb = S.tb.p; G.tb_cap = af_tb_cap;
                 G.fb_n = c->fb_all.p + 16 * k; G.fb_list = c->fb_all.p + 16 * n_sub + k * (sub_reads + 1); G.big_list = S.big_list.p; G.huge_list = S.big_list.p + (sub_reads + 1); G.list0 = S.big_list.p + 2 * (sub_reads + 1); G.fin_scratch = S.fin.p; G.fin_stride = sizeof(af_fin_t); G.ctr = S.ctr.p;
                 G.bnd = S.bnd.p;
-                G.pat = c->pat.p; G.blk = c->blk.p; G.text2 = I->d_text2; G.exc = I->d_exc; G.exc_sh = I->exc_sh; G.pflag = c->pflag.p; G.wave_max = af_wave_max();
+                G.pat = c->pat.p; G.blk = c->blk.p; G.text2 = I->d_text2.p; G.exc = I->d_exc.p; G.exc_sh = I->exc_sh; G.pflag = c->pflag.p; G.wave_max = af_wave_max();
                 G.txt_cur = S.txt_cur.p; G.txt_shard_words = txt_per / (AF_TXT_SHARDS + 1);
                 HIPCHK(hipMemsetAsync(S.txt_cur.p, 0, AF_TXT_SHARDS * 8 * sizeof(unsigned long long), sx));
 #ifdef AF_PROFILE
@@ -1741,13 +1693,8 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
     if (!out_done) {
         char* dst;
         if (ctx_out) {
-            if (c->out_cap < out.size() + 1) {
-                char* nb = nullptr;
-                if (hipHostMalloc((void**)&nb, out.size() + 1, hipHostMallocDefault) != hipSuccess) return MONI_ENOMEM;
-                if (c->out_buf) (void)hipHostFree(c->out_buf);
-                c->out_buf = nb; c->out_cap = out.size() + 1;
-            }
-            dst = c->out_buf;
+            if (c->out_buf.ensure_keep(out.size() + 1, 0)) return MONI_ENOMEM;
+            dst = c->out_buf.p;
         } else if (!(dst = (char*)malloc(out.size() + 1))) return MONI_ENOMEM;
         memcpy(dst, out.data(), out.size());
         dst[out.size()] = 0;
@@ -1944,17 +1891,16 @@ int moni_ldx_lift_batch(const char* path, int device, const uint64_t* pos, uint6
     LiftTables lt; std::string err;
     if ((rc = lt.build(f, err))) { fprintf(stderr, "moni_hip: %s\n", err.c_str()); return rc; }
     uint64_t bytes = 0;
-    moni_lift_seq_t* d_seqs = nullptr; moni_lift_run_t* d_runs = nullptr; uint64_t *d_pdir = nullptr, *d_starts = nullptr, *d_io = nullptr;
-    auto done = [&](int code) { void* ps[] = {d_seqs, d_runs, d_pdir, d_starts, d_io}; for (void* p : ps) if (p) (void)hipFree(p); return code; };
-    if ((rc = upload(&d_seqs, lt.seqs, bytes)) || (rc = upload(&d_runs, lt.runs, bytes)) || (rc = upload(&d_pdir, lt.pdir, bytes)) || (rc = upload(&d_starts, F.seq_starts, bytes))) return done(rc);
-    if (!n) return done(MONI_OK);
-    if (hipMalloc((void**)&d_io, 2 * n * 8) != hipSuccess) return done(MONI_ENOMEM);
-    if (hipMemcpy(d_io, pos, n * 8, hipMemcpyHostToDevice) != hipSuccess) return done(MONI_ENODEV);
+    DBuf<moni_lift_seq_t> d_seqs; DBuf<moni_lift_run_t> d_runs; DBuf<uint64_t> d_pdir, d_starts, d_io;
+    if ((rc = upload(d_seqs, lt.seqs, bytes)) || (rc = upload(d_runs, lt.runs, bytes)) || (rc = upload(d_pdir, lt.pdir, bytes)) || (rc = upload(d_starts, F.seq_starts, bytes))) return rc;
+    if (!n) return MONI_OK;
+    if (d_io.alloc_exact(2 * n)) return MONI_ENOMEM;
+    if (hipMemcpy(d_io.p, pos, n * 8, hipMemcpyHostToDevice) != hipSuccess) return MONI_ENODEV;
     ac_params_t P; memset(&P, 0, sizeof P);
-    P.n_text = f.n - 1; P.n_seq = (uint32_t)f.n_seq; P.seq_starts = d_starts; P.lift_seqs = d_seqs; P.lift_runs = d_runs; P.pdir = d_pdir;
-    hipLaunchKernelGGL(lift_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, P, (const uint64_t*)d_io, n, d_io + n);
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d_io + n, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return done(MONI_ENODEV);
-    return done(MONI_OK);
+    P.n_text = f.n - 1; P.n_seq = (uint32_t)f.n_seq; P.seq_starts = d_starts.p; P.lift_seqs = d_seqs.p; P.lift_runs = d_runs.p; P.pdir = d_pdir.p;
+    hipLaunchKernelGGL(lift_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, P, (const uint64_t*)d_io.p, n, d_io.p + n);
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d_io.p + n, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return MONI_ENODEV;
+    return MONI_OK;
     } catch (const std::bad_alloc&) { return MONI_ENOMEM; }
 }
 

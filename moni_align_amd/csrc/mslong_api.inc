@@ -59,11 +59,11 @@ int moni_ms_long_batch(moni_ctx_t* c, const moni_read_batch_t* b, const moni_msl
     const unsigned g256 = (unsigned)((n_segs + 1 + 255) / 256), gseg = (unsigned)((n_segs + MS_BLOCK - 1) / MS_BLOCK);
     hipLaunchKernelGGL(mslong_table_kernel, dim3(g256), dim3(256), 0, c->stream, c->offs.p, B.seg_off.p, nr, n_segs, prm->seg_len, prm->overlap, B.segs.p, B.flags.p);
     rec(c, EV_MS0);
-    hipLaunchKernelGGL(mslong_walk_kernel, dim3(gseg), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, I->d_rows, I->d_frows, I->d_cr, I->d_recs, c->seq.p, c->offs.p, B.segs.p, n_segs,
+    hipLaunchKernelGGL(mslong_walk_kernel, dim3(gseg), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->seq.p, c->offs.p, B.segs.p, n_segs,
                        B.ptr.p, B.states.p, B.counters.p);
     rec(c, EV_MS1);
     rec(c, EV_MC0);
-    hipLaunchKernelGGL(mslong_len_kernel, dim3(gseg), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text, c->seq.p, c->offs.p, B.segs.p, n_segs, B.ptr.p, B.lens.p, B.flags.p, B.counters.p);
+    hipLaunchKernelGGL(mslong_len_kernel, dim3(gseg), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, c->seq.p, c->offs.p, B.segs.p, n_segs, B.ptr.p, B.lens.p, B.flags.p, B.counters.p);
     rec(c, EV_MC1);
     // runs of flagged segments: heads, their exclusive scan, one entry per run
     hipLaunchKernelGGL(mslong_head_kernel, dim3(g256), dim3(256), 0, c->stream, B.flags.p, n_segs, B.head.p);
@@ -76,9 +76,9 @@ int moni_ms_long_batch(moni_ctx_t* c, const moni_read_batch_t* b, const moni_msl
         if ((rc = B.runs.ensure(n_runs + 1))) return rc;
         const unsigned grun = (unsigned)((n_runs + MS_BLOCK - 1) / MS_BLOCK);
         hipLaunchKernelGGL(mslong_runs_kernel, dim3(g256), dim3(256), 0, c->stream, B.flags.p, n_segs, B.run_idx.p, B.runs.p);
-        hipLaunchKernelGGL(mslong_chain_kernel, dim3(grun), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, I->d_rows, I->d_frows, I->d_cr, I->d_recs, c->seq.p, c->offs.p, B.segs.p, n_segs,
+        hipLaunchKernelGGL(mslong_chain_kernel, dim3(grun), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->seq.p, c->offs.p, B.segs.p, n_segs,
                            B.runs.p, n_runs, B.ptr.p, B.states.p, B.counters.p);
-        hipLaunchKernelGGL(mslong_relen_kernel, dim3(grun), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text, c->seq.p, c->offs.p, B.segs.p, B.runs.p, n_runs, B.ptr.p, B.lens.p);
+        hipLaunchKernelGGL(mslong_relen_kernel, dim3(grun), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, c->seq.p, c->offs.p, B.segs.p, B.runs.p, n_runs, B.ptr.p, B.lens.p);
     }
     rec(c, EV_ME1);
     rec(c, EV_ALL1);

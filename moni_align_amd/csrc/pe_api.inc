@@ -55,7 +55,7 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
         const uint64_t NR = b->n_reads;
         const uint64_t nb_names = txt->name_off[NR] - txt->name_off[0], nb_q = txt->quals ? b->offsets[NR] - b->offsets[0] : 0;
         if ((rc = c->ak_rnames.ensure(nb_names + 16)) || (rc = c->ak_rname_off.ensure(NR + 1)) || (rc = c->ak_quals.ensure(nb_q + 16))) return rc;
-        if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+        if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream.h, hipStreamNonBlocking));
         const PeText* const txt_up = txt;          // (by value: the thread never reads the caller's variable)
         uploader = std::thread([&, NR, nb_names, nb_q, txt_up]() {
             const PeText* const txt = txt_up;
@@ -145,7 +145,7 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
     if (o_split && c->pe.orec.cap < (size_t)NST * o_cap * AC_MAX_CHAINS) { if ((rc = c->pe.orec.ensure((size_t)NST * o_cap * AC_MAX_CHAINS))) return rc; HIPCHK(hipMemset(c->pe.orec.p, 0, c->pe.orec.cap * sizeof(pe_orec_t))); }
     if ((rc = c->pe.slots.ensure(NST * n_waves * NL)) || (rc = c->pe.waves.ensure(NST * n_waves)) || (rc = c->pe.recs.ensure(n_chunks * (CH + 1))) || (rc = c->pe.cig.ensure(n_chunks * cig_cap)) ||
         (rc = c->pe.alt.ensure(n_chunks * alt_cap)) || (rc = c->pe.cur.ensure(8 * n_chunks)) || (rc = c->pe.minscore.ensure(msc.size()))) return rc;
-    if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream.h, hipStreamNonBlocking));
     const uint64_t ln_per = 2 * CH + 8;                          // lines of a chunk (two per pair)
     size_t scan_bytes = 0;
     if (txt) {
@@ -171,9 +171,8 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
         HIPCHK(hipMemsetAsync(c->ak_dev_sum.p, 0, (160 * n_chunks + 8) * sizeof(unsigned long long), c->stream));
         memset(c->h_sum.p, 0, (4 * n_chunks + 4) * sizeof(unsigned long long));
     }
-    std::vector<hipEvent_t> ev(n_chunks, nullptr), ev_staged(n_chunks, nullptr);
-    struct EvGuard { std::vector<hipEvent_t>& e; ~EvGuard() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev_guard{ev}, ev_guard2{ev_staged};
-    for (uint64_t i = 0; i < n_chunks; ++i) { HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_staged[i], hipEventDisableTiming)); }
+    std::vector<Event> ev(n_chunks), ev_staged(n_chunks);
+    for (uint64_t i = 0; i < n_chunks; ++i) { HIPCHK(hipEventCreateWithFlags(&ev[i].h, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_staged[i].h, hipEventDisableTiming)); }
     HIPCHK(hipMemcpyAsync(c->pe.minscore.p, msc.data(), msc.size() * 4, hipMemcpyHostToDevice, c->stream));
     pe_args_t A;
     memset(&A, 0, sizeof A);
@@ -183,8 +182,8 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
     P.smatch = prm->smatch; P.gapo = prm->gapo; P.gapo2 = prm->gapo2; P.gape = prm->gape; P.gape2 = prm->gape2;
     P.max_dist_x = prm->max_dist_x; P.max_dist_y = prm->max_dist_y; P.max_iter = prm->max_iter; P.max_pred = prm->max_pred;
     P.min_chain_score = prm->min_chain_score; P.min_chain_length = prm->min_chain_length;
-    P.n_text = I->K.n_text; P.n_seq = I->K.n_seq; P.seq_starts = I->d_seq_starts;
-    P.lift_seqs = I->d_lift_seqs; P.lift_runs = I->d_lift_runs; P.pdir = I->d_pdir;
+    P.n_text = I->K.n_text; P.n_seq = I->K.n_seq; P.seq_starts = I->d_seq_starts.p;
+    P.lift_seqs = I->d_lift_seqs.p; P.lift_runs = I->d_lift_runs.p; P.pdir = I->d_pdir.p;
     A.PP.smismatch = prm->smismatch; A.PP.max_penalty = (int32_t)(int8_t)std::max(prm->smatch + prm->smismatch, prm->gapo + prm->gape);
     A.PP.filter_dir = pe->filter_dir; A.PP.finalize = finalize ? 1u : 0u; A.PP.dir_thr = pe->dir_thr; A.PP.mean = (float)mean; A.PP.std_dev = (float)std_dev;
     A.PP.secondary_chains = pe->secondary_chains ? 1u : 0u;
@@ -198,7 +197,7 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
     HIPCHK(hipStreamSynchronize(c->stream));
     A.PP.pen_tab = c->pe.pen_tab.p; A.PP.pen_tab_n = PE_PEN_TAB;
     A.D.sc_mch = prm->smatch; A.D.sc_mis = -prm->smismatch; A.D.sc_N = -prm->gape; A.D.wild = 4; A.D.qo = prm->gapo; A.D.e = prm->gape;
-    A.D.end_bonus = prm->end_bonus; A.D.reads = c->seq.p; A.D.text = I->d_text; A.D.n_text = I->K.n_text;
+    A.D.end_bonus = prm->end_bonus; A.D.reads = c->seq.p; A.D.text = I->d_text.p; A.D.n_text = I->K.n_text;
     A.D.reads_limit = (c->total_len + 8) & ~7ull; A.D.text_limit = (I->K.n_text + 8) & ~7ull;
     A.mems = c->mems.p; A.occs = c->tmp.p; A.read_mem_off = c->read_mem_off.p; A.aux = c->aux.p; A.offs = c->offs.p;
     A.min_score_of_len = c->pe.minscore.p; A.max_len = (uint32_t)c->max_len + 1;
@@ -230,7 +229,7 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
             uint32_t* const fbk = c->pe.fb[0].p + (size_t)k * (CH + 16);
             G.fb_n = fbk; G.fb_list = fbk + 16; G.big_list = S.big_list.p; G.huge_list = S.big_list.p + (CH + 1); G.list0 = S.big_list.p + 2 * (CH + 1);
             G.ctr = S.ctr.p; G.bnd = S.bnd.p;
-            G.pat = c->pat.p; G.blk = c->blk.p; G.text2 = I->d_text2; G.exc = I->d_exc; G.exc_sh = I->exc_sh; G.pflag = c->pflag.p; G.wave_max = af_wave_max();
+            G.pat = c->pat.p; G.blk = c->blk.p; G.text2 = I->d_text2.p; G.exc = I->d_exc.p; G.exc_sh = I->exc_sh; G.pflag = c->pflag.p; G.wave_max = af_wave_max();
             X.PP = A.PP; X.aux = A.aux; X.recs = A.recs; X.cig_pool = A.cig_pool; X.cig_cap = A.cig_cap; X.alt_pool = A.alt_pool; X.alt_cap = A.alt_cap; X.cursors = A.cursors;
             HIPCHK(hipMemsetAsync(S.ctr.p, 0, AF_NCTR * sizeof(uint32_t), c->stream));
             HIPCHK(hipMemsetAsync(fbk, 0, 16 * sizeof(uint32_t), c->stream));
@@ -261,7 +260,7 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
         // the hand-over pairs run on their own stream beside the next chunk's staged kernels (its other buffer set); the host takes this chunk when they are through
         hipStream_t sf = c->stream;
         if (staged) {
-            if (!c->pe_stream[st]) HIPCHK(hipStreamCreateWithFlags(&c->pe_stream[st], hipStreamNonBlocking));
+            if (!c->pe_stream[st]) HIPCHK(hipStreamCreateWithFlags(&c->pe_stream[st].h, hipStreamNonBlocking));
             sf = c->pe_stream[st];
             HIPCHK(hipStreamWaitEvent(sf, ev_staged[k], 0));
         }
@@ -283,7 +282,7 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
             memset(&Y, 0, sizeof Y);
             Y.P = A.PP.P; Y.D = A.D; Y.offs = A.offs;
             Y.F.rnames = c->ak_rnames.p; Y.F.rname_off = c->ak_rname_off.p; Y.F.quals = txt->quals ? c->ak_quals.p : nullptr;
-            Y.F.snames = I->d_snames; Y.F.sname_off = I->d_sname_off; Y.F.mapq_tab = c->ak_mapq_tab.p; Y.F.mapq_tab_n = 8192;
+            Y.F.snames = I->d_snames.p; Y.F.sname_off = I->d_sname_off.p; Y.F.mapq_tab = c->ak_mapq_tab.p; Y.F.mapq_tab_n = 8192;
             Y.F.min_len = (int32_t)prm->min_len; Y.F.smatch = prm->smatch; Y.F.smismatch = prm->smismatch;
             Y.recs = A.recs; Y.cig_pool = A.cig_pool; Y.alt_pool = A.alt_pool; Y.pair_lo = A.pair_lo; Y.n_pairs = A.n_pairs;
             Y.subn_tab = c->pe.subn_tab.p; Y.subn_tab_n = 1024; Y.min_score_of_len = A.min_score_of_len; Y.max_len = (uint32_t)c->max_len;
@@ -316,7 +315,7 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
             if (sm[1] == 0 && sm[0] <= CH * PEL_PAIR_WORDS * 8) {          // every line of the chunk was written by the kernels: the block goes straight into the text buffer
                 const double h0 = mh::now_s();
                 txt->pairs_upto = ch.lo + ch.n;
-                if (*txt->used + (size_t)sm[0] + 1 > c->out_cap) HIPCHK(hipStreamSynchronize(c->copy_stream));      // the buffer is about to move
+                if (*txt->used + (size_t)sm[0] + 1 > c->out_buf.cap) HIPCHK(hipStreamSynchronize(c->copy_stream));      // the buffer is about to move
                 char* dst = txt->room(*txt->used + (size_t)sm[0] + 1);
                 if (!dst) return MONI_ENOMEM;
                 // (no wait here: the transfers queue up on the copy stream behind one another while the host goes on to the next chunk; pe_run waits for
@@ -399,12 +398,11 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
                                           if (!lt.empty()) {
                                               DBuf<moni_dp_task_t> dt; DBuf<pe_sw_ws_t> dw; DBuf<moni_dp_result_t> dr;
                                               int rl;
-                                              if ((rl = dt.ensure(lt.size())) || (rl = dw.ensure(lt.size())) || (rl = dr.ensure(lt.size()))) { dt.release(); dw.release(); dr.release(); return rl; }
+                                              if ((rl = dt.ensure(lt.size())) || (rl = dw.ensure(lt.size())) || (rl = dr.ensure(lt.size()))) return rl;
                                               std::vector<moni_dp_result_t> lr(lt.size());
                                               bool ok = hipMemcpy(dt.p, lt.data(), lt.size() * sizeof(moni_dp_task_t), hipMemcpyHostToDevice) == hipSuccess;
                                               if (ok) { hipLaunchKernelGGL(pe_sw_kernel, dim3((unsigned)((lt.size() + 63) / 64)), dim3(64), 0, c->copy_stream, A.D, (const moni_dp_task_t*)dt.p, (uint32_t)lt.size(), dw.p, dr.p);
                                                         ok = hipStreamSynchronize(c->copy_stream) == hipSuccess && hipMemcpy(lr.data(), dr.p, lt.size() * sizeof(moni_dp_result_t), hipMemcpyDeviceToHost) == hipSuccess; }
-                                              dt.release(); dw.release(); dr.release();
                                               if (!ok) return MONI_ENODEV;
                                               for (size_t x = 0; x < lt.size(); ++x) r[li[x]] = lr[x];
                                           }
@@ -498,15 +496,10 @@ static int pe_align_text(moni_ctx_t* c, const moni_read_batch_t* b, const uint8_
         const uint64_t NP_all = b->n_reads / 2;
         PeText txt;
         auto room = [&](size_t need) -> char* {          // grows the pinned buffer (sized from the bytes per pair so far), keeps the first `used` bytes
-            if (need <= c->out_cap) return c->out_buf;
+            if (need <= c->out_buf.cap) return c->out_buf.p;
             size_t want = need + need / 8 + 65536;
             if (txt.pairs_upto) want = std::max<size_t>(want, (size_t)((double)need / (double)txt.pairs_upto * 1.06 * (double)NP_all) + 65536);
-            char* nb = nullptr;
-            if (hipHostMalloc((void**)&nb, want, hipHostMallocDefault) != hipSuccess) return nullptr;
-            if (c->out_buf && used) memcpy(nb, c->out_buf, used);
-            if (c->out_buf) (void)hipHostFree(c->out_buf);
-            c->out_buf = nb; c->out_cap = want;
-            return nb;
+            return c->out_buf.ensure_keep(want, used) ? nullptr : c->out_buf.p;
         };
         std::vector<size_t> at(T + 1, 0);
         txt.names = names; txt.name_off = name_off; txt.quals = quals; txt.room = room; txt.used = &used;

@@ -12,15 +12,15 @@ static int pml_run_resident(moni_ctx* c, uint32_t thr) {
     if ((rc = c->pat.ensure(c->h_blk.back().y + 1)) || (rc = c->pflag.ensure(n_tasks + 8)) || (rc = B.lens.ensure(c->total_len + 4)) || (rc = B.mx.ensure(nr + 1)) ||
         (rc = B.hits.ensure(nr + 1)))
         return rc;
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
     rec(c, EV_ALL0);
     if (nr)
-        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, c->seq.p, c->offs.p, c->blk.p, n_tasks,
+        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, c->seq.p, c->offs.p, c->blk.p, n_tasks,
                            c->pat.p, c->pflag.p);
     rec(c, EV_MS0);
     if (nr)
-        hipLaunchKernelGGL(pml_kernel, dim3((unsigned)((nr + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, I->d_rows, I->d_frows, I->d_cr, I->d_recs,
-                           c->pat.p, c->offs.p, c->blk.p, nr, thr, B.lens.p, B.mx.p, B.hits.p, c->d_counters);
+        hipLaunchKernelGGL(pml_kernel, dim3((unsigned)((nr + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p,
+                           c->pat.p, c->offs.p, c->blk.p, nr, thr, B.lens.p, B.mx.p, B.hits.p, c->d_counters.p);
     rec(c, EV_MS1);
     rec(c, EV_ALL1);
     HIPCHK(hipGetLastError());

@@ -28,22 +28,22 @@ static int seqcount_run_resident(moni_ctx* c, const moni_seqcount_params_t* prm)
         (void)hipGetLastError();          // (a refused allocation is reported by the return value alone)
         return rc;
     }
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
     rec(c, EV_ALL0);
     const unsigned task_grid = (unsigned)((n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK);          // (one thread more than tasks: it closes the counts for the scan)
     if (nr)
-        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_pack + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, c->seq.p, c->offs.p, c->blk.p, n_pack,
+        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_pack + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, c->seq.p, c->offs.p, c->blk.p, n_pack,
                            c->pat.p, c->pflag.p);
     rec(c, EV_MS0);
     if (nr)
-        hipLaunchKernelGGL(count_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables, I->d_rows, I->d_frows, I->d_cr, I->d_recs, c->pat.p, c->offs.p, c->blk.p,
-                           n_tasks, prm->strands, 0u, B.lres.p, B.toe.p, B.cnt.p, c->d_counters);
+        hipLaunchKernelGGL(count_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p,
+                           n_tasks, prm->strands, 0u, B.lres.p, B.toe.p, B.cnt.p, c->d_counters.p);
     rec(c, EV_MS1);
     HIPCHK(hipGetLastError());
     rec(c, EV_PC0);
     uint64_t total = 0;
     if (nr) {
-        hipLaunchKernelGGL(seqcount_plan_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_rows, n_tasks, prm->max_walk, B.lres.p, B.res.p, B.k_lo.p, B.cnt.p);
+        hipLaunchKernelGGL(seqcount_plan_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_rows.p, n_tasks, prm->max_walk, B.lres.p, B.res.p, B.k_lo.p, B.cnt.p);
         HIPCHK(hipGetLastError());
         if ((rc = exclusive_scan_u64(c, B.cnt.p, B.off.p, n_tasks + 1))) return rc;
         HIPCHK(hipMemcpyAsync(&total, B.off.p + n_tasks, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
@@ -51,10 +51,10 @@ static int seqcount_run_resident(moni_ctx* c, const moni_seqcount_params_t* prm)
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     if (total) {          // no segment: no walk launch, and every n_seqs stays 0
-        phi_tab_t P; P.recs = I->d_phi; P.dir = I->d_phi_dir;
+        phi_tab_t P; P.recs = I->d_phi.p; P.dir = I->d_phi_dir.p;
         const uint64_t blocks = (total + MS_BLOCK - 1) / MS_BLOCK;
-        hipLaunchKernelGGL(seqcount_walk_kernel, dim3((unsigned)std::min<uint64_t>(blocks, SC_MAX_GRID)), dim3(MS_BLOCK), 0, c->stream, I->K, P, I->d_rows, I->d_cr, I->d_recs,
-                           I->d_seq_starts, n_tasks, total, B.res.p, B.toe.p, B.k_lo.p, B.off.p, (unsigned long long*)B.counts.p, c->d_counters);
+        hipLaunchKernelGGL(seqcount_walk_kernel, dim3((unsigned)std::min<uint64_t>(blocks, SC_MAX_GRID)), dim3(MS_BLOCK), 0, c->stream, I->K, P, I->d_rows.p, I->d_cr.p, I->d_recs.p,
+                           I->d_seq_starts.p, n_tasks, total, B.res.p, B.toe.p, B.k_lo.p, B.off.p, (unsigned long long*)B.counts.p, c->d_counters.p);
         hipLaunchKernelGGL(seqcount_finish_kernel, dim3((unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, (uint32_t)n_seq, n_tasks,
                            (const unsigned long long*)B.counts.p, B.res.p);
     }
