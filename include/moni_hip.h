@@ -517,6 +517,16 @@ int moni_last_counters(moni_ctx_t *ctx, uint64_t out[4]);
  * overflow region was grown and the pass repeated), [4] launches of the long-seed kernel (0: skipped, there was no long seed),
  * [5] compactions done for moni_seed_fetch since that run (the align paths do none). */
 int moni_seed_occ_stats(moni_ctx_t *ctx, uint64_t out[6]);
+/* The strand prefilter of the seeding stage (csrc/prefilter_core.h): a task - one strand of one read - none of whose windows of min_len bases
+ * has all of its k-mers in the index's k-mer table can hold no MEM, and its LF walk and text comparison are left out.  mode 0: off;
+ * 1 (default): on in the align, paired, report-MEMs and csv entry points, off in moni_seed_run / moni_seed_batch; 2: on everywhere.
+ * MONI_SEED_PREFILTER=0|1|2 sets the mode of a new context.  The seeds are the same in every mode.  Where the filter runs, moni_last_counters
+ * counts the work done: [0] the steps walked, [1] the jumps taken and [3] the bytes compared, of the tasks that were not skipped.  The filter stands
+ * down by itself for a task whose pattern holds a byte outside A / C / G / T, when min_len is below the table's k, and for an index whose
+ * table is more than a quarter full.  The matching-statistics entry points and extend mode never filter: their pointers are complete. */
+int moni_seed_prefilter(moni_ctx_t *ctx, int mode);
+/* The filter in the last seeding run: out[0] tasks, [1] tasks skipped, [2] table lookups, [3] the table's density x 1e6. */
+int moni_seed_prefilter_stats(moni_ctx_t *ctx, uint64_t out[4]);
 const char *moni_version(void);
 
 #ifdef __cplusplus

@@ -24,6 +24,7 @@ EXPORTS = [
     "moni_index_device_bytes", "moni_index_text", "moni_ctx_create", "moni_ctx_destroy", "moni_reads_upload", "moni_reads_swap", "moni_ms_run",
     "moni_ms_query_batch", "moni_seed_run", "moni_seed_counts", "moni_seed_fetch", "moni_seed_batch", "moni_free",
     "moni_phi_lcp_batch", "moni_extz_batch", "moni_last_kernel_ms", "moni_last_counters", "moni_seed_occ_stats",
+    "moni_seed_prefilter", "moni_seed_prefilter_stats",
     "moni_align_params_default", "moni_align_batch", "moni_align_csv_batch", "moni_align_run", "moni_align_stream", "moni_sam_header",
     "moni_ldx_info", "moni_ldx_rewrite", "moni_ldx_lift_batch", "moni_ldx_write",
     "moni_ms_file_info", "moni_ms_file_read", "moni_ms_file_write", "moni_index_load_reference", "moni_ms_lengths_batch", "moni_report_mems_batch",
@@ -239,6 +240,8 @@ def lib():
         L.moni_last_kernel_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
         L.moni_last_counters.argtypes = [C.c_void_p, C.c_void_p]
         L.moni_seed_occ_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.moni_seed_prefilter.argtypes = [C.c_void_p, C.c_int]
+        L.moni_seed_prefilter_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.moni_ms_lengths_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.c_void_p, C.c_void_p]
         L.moni_mslong_params_default.argtypes = [C.POINTER(MslongParamsC)]
         L.moni_mslong_params_default.restype = None
@@ -846,6 +849,16 @@ class Ctx:
         out = np.zeros(6, dtype=np.uint64)
         _chk(self._L.moni_seed_occ_stats(self._h, out.ctypes.data), "moni_seed_occ_stats")
         return dict(zip(("long_seeds", "overflow_used", "overflow_cap", "count_passes", "long_launches", "compactions"), (int(v) for v in out)))
+
+    def seed_prefilter(self, mode: int) -> None:
+        """the strand prefilter of the seeding stage: 0 off, 1 in the align and paired paths (default), 2 in seed_run too (moni_seed_prefilter)"""
+        _chk(self._L.moni_seed_prefilter(self._h, int(mode)), "moni_seed_prefilter")
+
+    def seed_prefilter_stats(self) -> Dict[str, float]:
+        """the filter in the last seeding run (moni_seed_prefilter_stats)"""
+        out = np.zeros(4, dtype=np.uint64)
+        _chk(self._L.moni_seed_prefilter_stats(self._h, out.ctypes.data), "moni_seed_prefilter_stats")
+        return {"tasks": int(out[0]), "skipped": int(out[1]), "lookups": int(out[2]), "density": float(out[3]) / 1e6}
 
 
 def ldx_info(path: str):

@@ -94,6 +94,7 @@ struct moni_index {
     DBuf<uint32_t> d_phi_dir, d_phi_inv_dir;
     DBuf<uint8_t> d_text;
     DBuf<uint64_t> d_text2; DBuf<uint32_t> d_exc; uint32_t exc_sh = 10, exc_words = 0;      // 2-bit text and its exception bitmap (seed_core.h: mem_fast_t)
+    DBuf<uint32_t> d_kmers; uint32_t pf_k = 0; double pf_density = 0; bool pf_on = false; float pf_build_ms = 0;      // the text's k-mers, one bit each (prefilter_core.h); pf_on: sparse enough to filter with
     DBuf<uint64_t> d_seq_starts;
     DBuf<uint32_t> d_name_id;
     DBuf<uint8_t> d_snames; DBuf<uint32_t> d_sname_off;      // sequence names, ragged (SAM text in align_kernel)
@@ -128,6 +129,10 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
     // workspaces
     DBuf<uint64_t> ptr, pat; DBuf<uint8_t> pflag;      // pflag: per seeding task, its pattern holds a byte outside A / C / G / T (pack_kernel)
     DBuf<uint32_t> cnt_m, cnt_s;
+    DBuf<uint64_t> pf_flag, pf_pos, pf_live; DBuf<unsigned long long> pf_stats;      // strand prefilter: per task kept or not, the scan, the live tasks in order; skipped tasks and lookups
+    int seed_prefilter = 1;                    // moni_seed_prefilter: 0 off, 1 in the align and paired paths, 2 in moni_seed_run too
+    bool pf_active = false;                    // the last ms_launch filtered: pf_live / pf_pos[n_tasks] are the live list and its length
+    uint64_t pf_tasks = 0;                     // tasks of the last seeding run
     DBuf<moni_u64x2> mem_slots;
     DBuf<uint64_t> tot, read_mem_off;
     DBuf<moni_mem_t> mems;
@@ -391,6 +396,27 @@ int moni_index_create(const moni_flat_index_t* f, int device, moni_index_t** out
         hipLaunchKernelGGL(text2_build_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, 0, I->d_text.p, n_text, n_words, I->d_text2.p, I->d_exc.p, I->exc_sh);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { moni_index_destroy(I); return MONI_ENODEV; }
     }
+    {   // the k-mer table of the strand prefilter, from the byte text on the device (the 2-bit text codes a byte outside A / C / G / T as A)
+        const uint64_t n_text = f->n - 1, n_words = n_text / 32 + 1;
+        I->pf_k = pf_choose_k(n_text);
+        if (const char* v = getenv("MONI_PREFILTER_K")) { const int x = atoi(v); if (x >= (int)PF_K_MIN && x <= (int)PF_K_MAX) I->pf_k = (uint32_t)x; }
+        const uint64_t tw = pf_table_words(I->pf_k);
+        DBuf<unsigned long long> d_pop;
+        Event e0, e1;
+        if (I->d_kmers.alloc_exact(tw) || d_pop.alloc_exact(1)) { moni_index_destroy(I); return MONI_ENOMEM; }
+        I->bytes += tw * 4;
+        if (hipEventCreate(&e0.h) != hipSuccess || hipEventCreate(&e1.h) != hipSuccess || hipEventRecord(e0, 0) != hipSuccess ||
+            hipMemsetAsync(I->d_kmers.p, 0, tw * 4, 0) != hipSuccess || hipMemsetAsync(d_pop.p, 0, 8, 0) != hipSuccess) { moni_index_destroy(I); return MONI_ENODEV; }
+        hipLaunchKernelGGL(kmer_build_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, 0, I->d_text.p, n_text, n_words, I->pf_k, I->d_kmers.p);
+        hipLaunchKernelGGL(kmer_popcount_kernel, dim3((unsigned)std::min<uint64_t>((tw + 255) / 256, 4096)), dim3(256), 0, 0, I->d_kmers.p, tw, d_pop.p);
+        unsigned long long pop = 0;
+        if (hipEventRecord(e1, 0) != hipSuccess || hipGetLastError() != hipSuccess || hipMemcpy(&pop, d_pop.p, 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&I->pf_build_ms, e0, e1) != hipSuccess) { moni_index_destroy(I); return MONI_ENODEV; }
+        I->pf_density = (double)pop / (double)(1ull << (2 * I->pf_k));
+        I->pf_on = I->pf_density <= PF_DENSITY_MAX;
+        if (getenv("MONI_AK_PROFILE")) fprintf(stderr, "moni_hip: k-mer table of the strand prefilter: k = %u, %.1f MB, density %.4f (%s), built in %.2f ms\n", I->pf_k, tw * 4 / 1e6, I->pf_density,
+                                               I->pf_on ? "in use" : "too dense: the filter is off for this index", I->pf_build_ms);
+    }
     *out = I;
     return MONI_OK;
 }
@@ -503,10 +529,11 @@ int moni_ctx_create(moni_index_t* I, moni_ctx_t** out) {
     c->idx = I;
     if (const char* v = getenv("MONI_MS_VARIANT")) c->ms_variant = atoi(v);
     if (const char* v = getenv("MONI_EXTZ_LDS")) c->extz_lds = atoi(v);
+    if (const char* v = getenv("MONI_SEED_PREFILTER")) { const int x = atoi(v); if (x >= 0 && x <= 2) c->seed_prefilter = x; }
     bool ok = hipStreamCreate(&c->stream.h) == hipSuccess;
     for (int i = 0; ok && i < EV_N; ++i) ok = hipEventCreate(&c->ev[i].h) == hipSuccess;
-    ok = ok && c->d_small.alloc_exact(1) == MONI_OK && c->d_counters.alloc_exact(4) == MONI_OK &&
-         hipMemset(c->d_small.p, 0, sizeof(occ_small_t)) == hipSuccess && hipMemset(c->d_counters.p, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
+    ok = ok && c->d_small.alloc_exact(1) == MONI_OK && c->d_counters.alloc_exact(4) == MONI_OK && c->pf_stats.alloc_exact(2) == MONI_OK &&
+         hipMemset(c->pf_stats.p, 0, 2 * sizeof(unsigned long long)) == hipSuccess && hipMemset(c->d_small.p, 0, sizeof(occ_small_t)) == hipSuccess && hipMemset(c->d_counters.p, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) { fprintf(stderr, "moni_hip: context creation failed on device %d\n", I->device); moni_ctx_destroy(c); return MONI_ENODEV; }
     *out = c;
     return MONI_OK;
@@ -580,7 +607,9 @@ int moni_reads_swap(moni_ctx_t* c, uint32_t slot) {
 }
 
 // tabs: the byte tables pack_kernel derives strand 1 with (default: the index's own, kpbseq.h:120-137; extend mode brings its complement)
-static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr) {
+// filter_min_len > 0 (seed_all alone; it has made cnt_m / cnt_s): the strand prefilter runs behind pack_kernel, and the walk takes the live tasks only -
+// the pointers of a skipped task are not written.  Every other caller gets all of them.
+static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr, uint32_t filter_min_len = 0) {
     moni_index* I = c->idx;
     if (!tabs) tabs = I->d_tables.p;
     const uint64_t n_tasks = 2 * c->n_reads;
@@ -591,10 +620,21 @@ static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr) {
     if (n_tasks)
         hipLaunchKernelGGL(pack_kernel, dim3(grid), dim3(MS_BLOCK), 0, c->stream, I->K, tabs, c->seq.p, c->offs.p, c->blk.p, n_tasks, c->pat.p, c->pflag.p);
     rec(c, EV_MS0);
+    c->pf_active = false;
+    const uint64_t* live = nullptr; const uint64_t* n_live = nullptr;
+    if (n_tasks && filter_min_len) {          // flags, their scan (the live count stays on the device: no synchronisation), the list
+        if ((rc = c->pf_flag.ensure(n_tasks + 2)) || (rc = c->pf_pos.ensure(n_tasks + 2)) || (rc = c->pf_live.ensure(n_tasks + 2))) return rc;
+        hipLaunchKernelGGL(strand_filter_kernel, dim3((unsigned)((n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, c->pat.p, c->offs.p, c->blk.p, c->pflag.p, n_tasks,
+                           filter_min_len, I->pf_k, I->d_kmers.p, c->pf_flag.p, c->cnt_m.p, c->cnt_s.p, c->pf_stats.p);
+        if ((rc = exclusive_scan_u64(c, c->pf_flag.p, c->pf_pos.p, n_tasks + 1))) return rc;
+        hipLaunchKernelGGL(live_list_kernel, dim3((unsigned)((n_tasks + 255) / 256)), dim3(256), 0, c->stream, c->pf_flag.p, c->pf_pos.p, n_tasks, c->pf_live.p);
+        live = c->pf_live.p; n_live = c->pf_pos.p + n_tasks;
+        c->pf_active = true;
+    }
     if (n_tasks) {
 #define MS_LAUNCH(NCH, MINW) do { const uint64_t nl = (n_tasks + (NCH) - 1) / (NCH); \
         hipLaunchKernelGGL((ms_lf_kernel<NCH, MINW>), dim3((unsigned)((nl + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, \
-                           I->K, tabs, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p, n_tasks, c->ptr.p, c->d_counters.p); } while (0)
+                           I->K, tabs, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p, n_tasks, c->ptr.p, c->d_counters.p, live, n_live); } while (0)
         switch (c->ms_variant) {
             case 1: MS_LAUNCH(1, 8); break;
             case 2: MS_LAUNCH(2, 8); break;
@@ -674,7 +714,8 @@ int moni_ms_lengths_batch(moni_ctx_t* c, const moni_read_batch_t* b, uint64_t* p
 
 // The seeding stage over the resident batch: MS pointers, MEMs (count, scan, emit), occurrences (one pass that counts them and leaves the lists where it
 // wrote them; a second, small launch only for the seeds whose list is longer than tmp_cap).
-static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
+// align_path: called for the align, paired, report-MEMs and csv entry points (where mode 1 of moni_seed_prefilter filters) and not for moni_seed_run itself
+static int seed_all(moni_ctx* c, const moni_seed_params_t* prm, bool align_path) {
     moni_index* I = c->idx;
     const uint64_t nr = c->n_reads, n_tasks = 2 * nr;
     int rc;
@@ -687,22 +728,27 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
     const uint64_t* offs = c->offs.p;
     HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
     HIPCHK(hipMemsetAsync(c->d_small.p, 0, sizeof(occ_small_t), c->stream));
+    HIPCHK(hipMemsetAsync(c->pf_stats.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    c->pf_tasks = n_tasks;
+    // the strand prefilter: where the mode asks for it, the index's table is sparse enough and min_len leaves a window of k-mers (prefilter_core.h)
+    const bool filter = (c->seed_prefilter == 2 || (c->seed_prefilter == 1 && align_path)) && I->pf_on && prm->min_len >= I->pf_k;
     rec(c, EV_ALL0);
-    if ((rc = ms_launch(c))) return rc;                              // (allocates pat / ptr)
+    if ((rc = ms_launch(c, nullptr, filter ? prm->min_len : 0))) return rc;                              // (allocates pat / ptr)
+    const uint64_t* live = c->pf_active ? c->pf_live.p : nullptr; const uint64_t* n_live = c->pf_active ? c->pf_pos.p + n_tasks : nullptr;
     const uint64_t* pat = c->pat.p; const uint64_t* ptr = c->ptr.p;
     const unsigned grid_t = (unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK);
     const uint32_t split_on = prm->report_mems ? 0u : 1u;
     // the 2-bit comparison holds a lane's pattern in LDS: 5 words (160 bases) or 8 (256); reads beyond that compare bytes (MONI_MEM_BYTES=1: all do)
     static const bool mem_bytes = getenv("MONI_MEM_BYTES") != nullptr;
     const uint64_t* text2 = mem_bytes ? nullptr : I->d_text2.p;
-#define MEM_LAUNCH(EMIT, RMO, MEMS, AUX) do { \
+#define MEM_LAUNCH(EMIT, RMO, MEMS, AUX, LIVE, NLIVE) do { \
         if (c->max_len <= 160) hipLaunchKernelGGL((mem_kernel<EMIT, 5>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, text2, I->d_exc.p, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
-                                                  n_tasks, ptr, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters.p); \
+                                                  n_tasks, ptr, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters.p, LIVE, NLIVE); \
         else hipLaunchKernelGGL((mem_kernel<EMIT, 8>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, text2, I->d_exc.p, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
-                                n_tasks, ptr, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters.p); } while (0)
+                                n_tasks, ptr, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters.p, LIVE, NLIVE); } while (0)
     rec(c, EV_MC0);
     if (n_tasks)
-        MEM_LAUNCH(false, (const uint64_t*)nullptr, (moni_mem_t*)nullptr, (uint32_t*)nullptr);
+        MEM_LAUNCH(false, (const uint64_t*)nullptr, (moni_mem_t*)nullptr, (uint32_t*)nullptr, live, n_live);
     rec(c, EV_MC1);
     hipLaunchKernelGGL(read_totals_kernel, dim3((unsigned)((nr + 1 + 255) / 256)), dim3(256), 0, c->stream, cnt_m, cnt_s, nr, tot);
     if ((rc = exclusive_scan_u64(c, tot, rmo, nr + 1))) return rc;
@@ -717,7 +763,7 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm) {
     moni_mem_t* mems = c->mems.p; uint32_t* aux = c->aux.p;
     rec(c, EV_ME0);
     if (n_tasks)
-        MEM_LAUNCH(true, (const uint64_t*)rmo, mems, aux);
+        MEM_LAUNCH(true, (const uint64_t*)rmo, mems, aux, (const uint64_t*)nullptr, (const uint64_t*)nullptr);          // (a task without a MEM returns at once)
     rec(c, EV_ME1);
     occ_args_t A;
     A.phi.recs = I->d_phi.p; A.phi.dir = I->d_phi_dir.p; A.phi_inv.recs = I->d_phi_inv.p; A.phi_inv.dir = I->d_phi_inv_dir.p;
@@ -798,7 +844,28 @@ static int seed_compact(moni_ctx* c) {
 int moni_seed_run(moni_ctx_t* c, const moni_seed_params_t* prm) {
     if (!c || !prm) return MONI_EINVAL;
     HIPCHK(hipSetDevice(c->idx->device));
-    return seed_all(c, prm);
+    return seed_all(c, prm, false);
+}
+// the seeding stage of the align, paired, report-MEMs and csv entry points
+static int seed_run_align(moni_ctx* c, const moni_seed_params_t* prm) {
+    if (!c || !prm) return MONI_EINVAL;
+    HIPCHK(hipSetDevice(c->idx->device));
+    return seed_all(c, prm, true);
+}
+
+int moni_seed_prefilter(moni_ctx_t* c, int mode) {
+    if (!c || mode < 0 || mode > 2) return MONI_EINVAL;
+    c->seed_prefilter = mode;
+    return MONI_OK;
+}
+
+int moni_seed_prefilter_stats(moni_ctx_t* c, uint64_t out[4]) {
+    if (!c || !out) return MONI_EINVAL;
+    HIPCHK(hipSetDevice(c->idx->device));
+    unsigned long long h[2];
+    HIPCHK(hipMemcpy(h, c->pf_stats.p, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = c->pf_tasks; out[1] = h[0]; out[2] = h[1]; out[3] = (uint64_t)(c->idx->pf_density * 1e6 + 0.5);
+    return MONI_OK;
 }
 
 int moni_seed_counts(moni_ctx_t* c, uint64_t* n_mems, uint64_t* n_occs) {
@@ -889,7 +956,7 @@ struct GpuBackend : mh::Backend {
     moni_ctx* c;
     explicit GpuBackend(moni_ctx* c_) : c(c_) {}
     int seed(const moni_seed_params_t& p, std::vector<moni_mem_t>& mems, std::vector<uint64_t>& occs, std::vector<uint64_t>& rmo) override {
-        int rc = moni_seed_run(c, &p);
+        int rc = seed_run_align(c, &p);
         if (rc) return rc;
         mems.resize(c->n_mems); occs.resize(c->n_occs); rmo.resize(c->n_reads + 1);
         return moni_seed_fetch(c, mems.data(), occs.data(), rmo.data());
@@ -1208,7 +1275,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         {
             const double t0 = mh::now_s();
             if (!resident && (rc = reads_upload(c, b, false))) return rc;
-            if ((rc = moni_seed_run(c, &sp))) return rc;
+            if ((rc = seed_run_align(c, &sp))) return rc;
             st.t_seed += mh::now_s() - t0;
         }
         t_mark[0] = mh::now_s() - t_enter;
@@ -1721,7 +1788,7 @@ int moni_report_mems_batch(moni_ctx_t* c, const moni_read_batch_t* b, const uint
     if (rc) return rc;
     moni_seed_params_t sp;
     sp.min_len = prm->min_len; sp.filter_seeds = prm->filter_seeds; sp.n_seeds_thr = prm->n_seeds_thr; sp.report_mems = 1;
-    if ((rc = moni_seed_run(c, &sp))) return rc;
+    if ((rc = seed_run_align(c, &sp))) return rc;
     try {
         std::vector<moni_mem_t> mems(c->n_mems); std::vector<uint64_t> occs(c->n_occs), rmo(c->n_reads + 1);
         if ((rc = moni_seed_fetch(c, mems.data(), occs.data(), rmo.data()))) return rc;

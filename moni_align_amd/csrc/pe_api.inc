@@ -69,7 +69,7 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
         });
     }
     struct JoinGuard { std::thread& t; ~JoinGuard() { if (t.joinable()) t.join(); } } join_guard{uploader};
-    if ((!resident && (rc = reads_upload(c, b, false))) || (rc = moni_seed_run(c, &sp))) return rc;
+    if ((!resident && (rc = reads_upload(c, b, false))) || (rc = seed_run_align(c, &sp))) return rc;
     // (the names and qualities are the lines kernel's: their upload is waited for after the staged kernels have been queued)
     const double t1 = mh::now_s();
     std::vector<int32_t> msc(c->max_len + 2);
@@ -644,7 +644,7 @@ int moni_pe_report_mems_batch(moni_ctx_t* c, const moni_read_batch_t* b, const u
     if (rc) return rc;
     moni_seed_params_t sp;
     sp.min_len = prm->min_len; sp.filter_seeds = prm->filter_seeds; sp.n_seeds_thr = prm->n_seeds_thr; sp.report_mems = 1;
-    if ((rc = moni_seed_run(c, &sp))) return rc;
+    if ((rc = seed_run_align(c, &sp))) return rc;
     try {
         std::vector<moni_mem_t> mems(c->n_mems); std::vector<uint64_t> occs(c->n_occs), rmo(c->n_reads + 1);
         if ((rc = moni_seed_fetch(c, mems.data(), occs.data(), rmo.data()))) return rc;

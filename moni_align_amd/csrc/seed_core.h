@@ -346,16 +346,17 @@ template <int NCH>
 MONI_HD void ms_task(const moni_consts_t& K, const lds_tables_t& L, const moni_row_t* __restrict__ rows,
                      const moni_frow_t* __restrict__ frows, const uint32_t* __restrict__ cr, const moni_rec_t* __restrict__ recs,
                      const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t n_tasks, uint64_t task0,
-                     uint64_t* __restrict__ ptr_out, unsigned long long& n_steps, unsigned long long& n_jumps) {
+                     uint64_t* __restrict__ ptr_out, unsigned long long& n_steps, unsigned long long& n_jumps,
+                     const uint64_t* __restrict__ live = nullptr) {      // live: slot g works on task live[g] (n_tasks then counts the slots); null: the identity
     ms_state_t S[NCH];
     uint64_t pb[NCH], qb[NCH];
     uint32_t m_max = 0;
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
-        const uint64_t task = task0 + k;
+        const uint64_t slot = task0 + k;
         S[k].m = 0;
         pb[k] = qb[k] = 0;
-        if (task < n_tasks) { const uint64_t read = task >> 1; S[k].m = (uint32_t)(offs[read + 1] - offs[read]); pb[k] = ws_pat_base(blk, task); qb[k] = ws_ptr_base(blk, task); }
+        if (slot < n_tasks) { const uint64_t task = live ? live[slot] : slot; const uint64_t read = task >> 1; S[k].m = (uint32_t)(offs[read + 1] - offs[read]); pb[k] = ws_pat_base(blk, task); qb[k] = ws_ptr_base(blk, task); }
         m_max = S[k].m > m_max ? S[k].m : m_max;
         S[k].run = (uint32_t)K.r - 1; S[k].pos = K.n - 1; S[k].abs = true; S[k].off = 0;     // start with the empty string
         S[k].sample = K.last_run_sample; S[k].word = 0;

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "seed_core.h"
+#include "prefilter_core.h"
 
 #define MS_BLOCK 256
 #ifndef MS_CHAINS
@@ -52,12 +53,17 @@ __global__ void __launch_bounds__(MS_BLOCK, MINW)
 ms_lf_kernel(const moni_consts_t K, const moni_tables_t* __restrict__ T, const moni_row_t* __restrict__ rows,
              const moni_frow_t* __restrict__ frows, const uint32_t* __restrict__ cr, const moni_rec_t* __restrict__ recs,
              const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t n_tasks,
-             uint64_t* __restrict__ ptr_out, unsigned long long* __restrict__ counters) {
+             uint64_t* __restrict__ ptr_out, unsigned long long* __restrict__ counters,
+             const uint64_t* __restrict__ live, const uint64_t* __restrict__ n_live) {      // the live list of strand_filter_kernel and its length (null: every task)
+    if (live) {
+        n_tasks = *n_live;
+        if ((uint64_t)blockIdx.x * MS_BLOCK * NCH >= n_tasks) return;          // the grid is the full one: blocks past the live count leave
+    }
     __shared__ lds_tables_t L;
     load_tables(L, T, K);
     const uint64_t task0 = ((uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x) * NCH;
     unsigned long long n_steps = 0, n_jumps = 0;
-    if (task0 < n_tasks) ms_task<NCH>(K, L, rows, frows, cr, recs, pat, offs, blk, n_tasks, task0, ptr_out, n_steps, n_jumps);
+    if (task0 < n_tasks) ms_task<NCH>(K, L, rows, frows, cr, recs, pat, offs, blk, n_tasks, task0, ptr_out, n_steps, n_jumps, live);
     wave_add(n_steps, &counters[0]);
     wave_add(n_jumps, &counters[1]);
 }
@@ -70,17 +76,22 @@ mem_kernel(const moni_consts_t K, const uint8_t* __restrict__ text, const uint64
            const uint64_t* __restrict__ ptr, uint32_t min_len, uint32_t split_on,
            uint32_t* __restrict__ cnt_m, uint32_t* __restrict__ cnt_s,
            const uint64_t* __restrict__ read_mem_off, moni_mem_t* __restrict__ mems, uint32_t* __restrict__ aux,
-           moni_u64x2* __restrict__ slots, unsigned long long* __restrict__ counters) {
+           moni_u64x2* __restrict__ slots, unsigned long long* __restrict__ counters,
+           const uint64_t* __restrict__ live, const uint64_t* __restrict__ n_live) {      // as ms_lf_kernel's (the count pass; the emit pass takes every task)
+    if (live) {
+        n_tasks = *n_live;
+        if ((uint64_t)blockIdx.x * MS_BLOCK >= n_tasks) return;
+    }
     __shared__ uint64_t PW[W][MS_BLOCK];                 // [word][lane]: a lane's words lie in its own banks whatever word it reads
     __shared__ uint32_t EX[MONI_EXC_BITS / 32];
     for (uint32_t i = threadIdx.x; i < exc_words && i < MONI_EXC_BITS / 32; i += MS_BLOCK) EX[i] = exc[i];
     __syncthreads();
     mem_fast_t F;
     F.text2 = text2; F.exc = EX; F.exc_sh = exc_sh; F.pw = &PW[0][threadIdx.x]; F.pw_stride = MS_BLOCK; F.pw_words = W;
-    const uint64_t task = (uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
+    const uint64_t g = (uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
     unsigned long long n_cmp = 0;
-    if (task < n_tasks)
-        mem_task<EMIT>(K, F, text, pat, offs, blk, task, ptr, min_len, split_on, cnt_m, cnt_s, read_mem_off, mems, aux, slots, n_cmp);
+    if (g < n_tasks)
+        mem_task<EMIT>(K, F, text, pat, offs, blk, live ? live[g] : g, ptr, min_len, split_on, cnt_m, cnt_s, read_mem_off, mems, aux, slots, n_cmp);
     if (!EMIT) wave_add(n_cmp, &counters[3]);
 }
 
@@ -92,6 +103,46 @@ __global__ void __launch_bounds__(256) text2_build_kernel(const uint8_t* __restr
     bool bad;
     text2[w] = text2_word(text, n_text, w, bad);
     if (bad) { const uint64_t b = (32 * w) >> exc_sh; atomicOr(&exc[b >> 5], 1u << (b & 31u)); }
+}
+
+// The k-mer table of the strand prefilter (prefilter_core.h), one thread per 32 text positions; once per index, from the byte text
+__global__ void __launch_bounds__(256) kmer_build_kernel(const uint8_t* __restrict__ text, uint64_t n_text, uint64_t n_words, uint32_t k, uint32_t* __restrict__ tab) {
+    const uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w < n_words) pf_build_word(text, n_text, w, k, tab);
+}
+// ... and the number of k-mers it holds
+__global__ void __launch_bounds__(256) kmer_popcount_kernel(const uint32_t* __restrict__ tab, uint64_t n_words, unsigned long long* __restrict__ out) {
+    unsigned long long s = 0;
+    for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * 256) s += (unsigned)__popc(tab[w]);
+    wave_add(s, out);
+}
+
+// The strand prefilter, behind pack_kernel: one lane per task decides from the task's 2-bit code words whether it can hold a MEM (pf_task_keep).
+// flag[task] = 1 for a task that stays (flag[n_tasks] = 0: the scan's total), and a skipped task's counts are what mem_kernel would have found:
+// none.  stats[0] += skipped tasks, stats[1] += table lookups.
+__global__ void __launch_bounds__(MS_BLOCK)
+strand_filter_kernel(const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, const uint8_t* __restrict__ pflag, uint64_t n_tasks,
+                     uint32_t min_len, uint32_t k, const uint32_t* __restrict__ tab, uint64_t* __restrict__ flag, uint32_t* __restrict__ cnt_m, uint32_t* __restrict__ cnt_s,
+                     unsigned long long* __restrict__ stats) {
+    const uint64_t task = (uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
+    unsigned long long n_lookups = 0, skipped = 0;
+    if (task < n_tasks) {
+        const uint64_t read = task >> 1;
+        const uint32_t m = (uint32_t)(offs[read + 1] - offs[read]);
+        const uint64_t cb = ws_pat_base(blk, task) + 64u * ((ws_block_len(blk, task) + 7) / 8);      // the task's code words (pack_task)
+        pf_pat_t P;
+        pf_pat_init(P, pat + cb, 64u, m);
+        const bool keep = pf_task_keep(P, m, min_len, k, pflag[task] != 0, tab, n_lookups);
+        flag[task] = keep ? 1u : 0u;
+        if (!keep) { cnt_m[task] = 0; cnt_s[task] = 0; skipped = 1; }
+    } else if (task == n_tasks) flag[task] = 0;
+    wave_add(skipped, &stats[0]);
+    wave_add(n_lookups, &stats[1]);
+}
+// the live list in task order: pos = the exclusive scan of flag
+__global__ void __launch_bounds__(256) live_list_kernel(const uint64_t* __restrict__ flag, const uint64_t* __restrict__ pos, uint64_t n_tasks, uint64_t* __restrict__ live) {
+    const uint64_t task = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (task < n_tasks && flag[task]) live[pos[task]] = task;
 }
 
 // per-read final MEM count (orig + 2 * split)
