@@ -433,6 +433,43 @@ int  moni_seqcount_fetch(moni_ctx_t *ctx, moni_seqcount_res_t *res, uint64_t *co
 int  moni_seqcount_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const moni_seqcount_params_t *prm,
                          moni_seqcount_res_t *res, uint64_t *counts);
 
+/* ---- reference loci: where on the reference a pattern lies, and how many of its occurrences land there ---- */
+/* The search is moni_locate's (strand 0 the bytes as they are, strand 1 the reverse complement, task t = pattern * strands + strand).  The whole
+ * interval is enumerated, in the pieces the sequence counts use: one per BWT run the interval touches, max_walk bounds a task.  Every occurrence - the text
+ * position p of the pattern's first byte - gets a key: with lift = 1 liftidx::lift(p) (liftidx.hpp:89-95), the position on the contig the sequence
+ * of p was built from, the value the aligner's records carry; with lift = 0 p itself.  On an index with null lifts (FASTA-built) both are p.  A locus
+ * is a distinct key of a task, its support the number of the task's occurrences with that key.  Support can exceed the number of sequences: the
+ * bases of an insertion all lift to the reference base the insertion precedes. */
+typedef struct { uint32_t strands;      /* 1: forward only, 2: forward and reverse complement */
+                 uint32_t lift;         /* 1: keys are lifted positions; 0: text positions (the full locate, in text order) */
+                 uint64_t max_walk;     /* a task with count > max_walk is not enumerated; 0 = no limit */
+                 uint64_t max_total;    /* bound of the sum of count over the walked tasks of one run; 0 = no limit */
+                 uint64_t reserved[2];  /* 0 */
+               } moni_loci_params_t;
+/* count, sa_lo, matched: as in moni_locate_res_t, exact whether or not the task was walked.  walked, n_segs: as in moni_seqcount_res_t.  A walked
+ * task's n_loci loci lie at loci_off of lpos / lseq / lseq_off / support, in ascending lpos order (tasks in task order), and their supports sum to
+ * count; a task that was not walked has n_loci = 0. */
+typedef struct { uint64_t count, sa_lo, loci_off, n_loci; uint32_t matched, walked, n_segs, reserved; } moni_loci_res_t;
+void moni_loci_params_default(moni_loci_params_t *p);                /* strands 1, lift 1, max_walk 1 << 20, max_total 1 << 28 */
+/* Device-only run over the batch that moni_reads_upload made resident; the results stay in HBM, in buffers of their own (a locate, seqcount or
+ * approx result of the context stays fetchable).  MONI_EINVAL: strands outside {1, 2}, lift > 1, a non-zero reserved word, no resident batch;
+ * MONI_ERANGE: more than 2^24 tasks (the task index is sorted beside a 40-bit position in one 64-bit key); MONI_ENOMEM: the walked total exceeds
+ * max_total, or the buffers cannot be had - returned before anything is written, the context stays usable (and has no loci result).
+ * moni_last_kernel_ms(ctx, 0, ..) then gives count_kernel's time, (ctx, 3, ..) the walk's with its planning and scans, (ctx, 4, ..) the sort's and
+ * the fold's, (ctx, 6, ..) the whole run's; moni_last_counters: [0] search steps, [1] fast rows fetched, [2] phi steps = the sum of count - n_segs
+ * over the walked tasks, [3] steps that took the general path.  Works on an index without LCP samples. */
+int  moni_loci_run(moni_ctx_t *ctx, const moni_loci_params_t *prm);
+/* What moni_loci_fetch would write: the tasks and the loci of the last moni_loci_run (either pointer may be NULL); MONI_EINVAL before any run, after
+ * a run that failed, and after another batch was made resident (moni_reads_upload, moni_reads_swap, any *_batch call). */
+int  moni_loci_sizes(moni_ctx_t *ctx, uint64_t *n_tasks, uint64_t *n_loci);
+/* The results of the last moni_loci_run on this context: res holds *n_tasks records, lpos / lseq / lseq_off / support *n_loci values each (any
+ * pointer may be NULL).  lseq is the sequence lpos lies in and lseq_off the 0-based offset inside it (seqidx::index). */
+int  moni_loci_fetch(moni_ctx_t *ctx, moni_loci_res_t *res, uint64_t *lpos, uint32_t *lseq, uint64_t *lseq_off, uint64_t *support);
+/* Host-buffer form: upload, run, fetch.  res: batch->n_reads * strands records (the caller's); *lpos / *lseq / *lseq_off / *support are malloc'ed
+ * (moni_free; NULL when there is no locus), any of the four pointers may be NULL; *n_loci (may be NULL) their length.  An empty batch gives MONI_OK. */
+int  moni_loci_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const moni_loci_params_t *prm, moni_loci_res_t *res,
+                     uint64_t **lpos, uint32_t **lseq, uint64_t **lseq_off, uint64_t **support, uint64_t *n_loci);
+
 /* ---- k-mismatch count and locate: every string within Hamming distance k of a pattern that occurs in the index ---- */
 /* Tasks, strands and bytes are moni_locate's (task t = pattern * strands + strand; strand 1 is the reverse complement by the aligner's table).  Only
  * substitutions are searched.  A text window of the pattern's length occurs at distance e where it differs from the pattern at exactly e <= k

@@ -33,6 +33,7 @@ EXPORTS = [
     "moni_pml_batch", "moni_pml_run", "moni_pml_fetch", "moni_pml_sizes",
     "moni_locate_params_default", "moni_locate_run", "moni_locate_sizes", "moni_locate_fetch", "moni_locate_batch",
     "moni_seqcount_params_default", "moni_seqcount_run", "moni_seqcount_sizes", "moni_seqcount_fetch", "moni_seqcount_batch",
+    "moni_loci_params_default", "moni_loci_run", "moni_loci_sizes", "moni_loci_fetch", "moni_loci_batch",
     "moni_approx_params_default", "moni_approx_run", "moni_approx_sizes", "moni_approx_fetch", "moni_approx_batch",
     "moni_mslong_params_default", "moni_ms_long_batch",
 ]
@@ -105,6 +106,10 @@ class SeqcountParamsC(C.Structure):
     _fields_ = [("strands", C.c_uint32), ("reserved", C.c_uint32), ("max_walk", C.c_uint64)]
 
 
+class LociParamsC(C.Structure):
+    _fields_ = [("strands", C.c_uint32), ("lift", C.c_uint32), ("max_walk", C.c_uint64), ("max_total", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
 class ApproxParamsC(C.Structure):
     _fields_ = [("strands", C.c_uint32), ("k", C.c_uint32), ("max_hits", C.c_uint32), ("max_occ", C.c_uint32), ("chunk_len", C.c_uint32), ("reserved", C.c_uint32),
                 ("max_steps", C.c_uint64)]
@@ -135,11 +140,14 @@ DP_RESULT_DTYPE = np.dtype([("max", "<i4"), ("max_q", "<i4"), ("max_t", "<i4"), 
                             ("zdropped", "<i4"), ("n_cigar", "<u4"), ("cigar_off", "<u4")])
 LOCATE_RES_DTYPE = np.dtype([("count", "<u8"), ("sa_lo", "<u8"), ("occ_off", "<u8"), ("n_occ", "<u4"), ("matched", "<u4")])
 SEQCOUNT_RES_DTYPE = np.dtype([("count", "<u8"), ("sa_lo", "<u8"), ("matched", "<u4"), ("n_seqs", "<u4"), ("walked", "<u4"), ("n_segs", "<u4")])
+LOCI_RES_DTYPE = np.dtype([("count", "<u8"), ("sa_lo", "<u8"), ("loci_off", "<u8"), ("n_loci", "<u8"), ("matched", "<u4"), ("walked", "<u4"), ("n_segs", "<u4"),
+                           ("reserved", "<u4")])
 APPROX_RES_DTYPE = np.dtype([("cnt", "<u8", (4,)), ("n_hits", "<u8"), ("hit_off", "<u8"), ("n_kept", "<u4"), ("complete", "<u4"), ("matched", "<u4"), ("reserved", "<u4")])
 APPROX_HIT_DTYPE = np.dtype([("task", "<u8"), ("n_mis", "<u4"), ("n_occ", "<u4"), ("sa_lo", "<u8"), ("count", "<u8"), ("occ_off", "<u8")])
 APPROX_MAX_STEPS_DEFAULT = 1 << 20
 APPROX_CHUNK_LEN_DEFAULT = 1 << 30
 assert LOCATE_RES_DTYPE.itemsize == 32 and SEQCOUNT_RES_DTYPE.itemsize == 32 and APPROX_RES_DTYPE.itemsize == 64 and APPROX_HIT_DTYPE.itemsize == 40
+assert LOCI_RES_DTYPE.itemsize == 48
 assert MEM_DTYPE.itemsize == 48 and DP_TASK_DTYPE.itemsize == 32 and DP_RESULT_DTYPE.itemsize == 48
 
 DEFAULT_MAT = [2, -4, -4, -4, 0, -4, 2, -4, -4, 0, -4, -4, 2, -4, 0, -4, -4, -4, 2, 0, 0, 0, 0, 0, 0]
@@ -228,6 +236,13 @@ def lib():
         L.moni_seqcount_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.moni_seqcount_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.moni_seqcount_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.POINTER(SeqcountParamsC), C.c_void_p, C.c_void_p]
+        L.moni_loci_params_default.argtypes = [C.POINTER(LociParamsC)]
+        L.moni_loci_params_default.restype = None
+        L.moni_loci_run.argtypes = [C.c_void_p, C.POINTER(LociParamsC)]
+        L.moni_loci_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.moni_loci_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.moni_loci_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.POINTER(LociParamsC), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_approx_params_default.argtypes = [C.POINTER(ApproxParamsC)]
         L.moni_approx_params_default.restype = None
         L.moni_approx_run.argtypes = [C.c_void_p, C.POINTER(ApproxParamsC)]
@@ -719,6 +734,55 @@ class Ctx:
         counts = np.zeros((nt, ns), dtype=np.uint64) if want_counts else None
         _chk(self._L.moni_seqcount_fetch(self._h, res.ctypes.data, counts.ctypes.data if want_counts else None), "moni_seqcount_fetch")
         return res, counts
+
+    def _loci_params(self, strands: int, lift: int, max_walk: int, max_total: Optional[int]) -> "LociParamsC":
+        p = LociParamsC()
+        self._L.moni_loci_params_default(C.byref(p))
+        p.strands, p.lift, p.max_walk = strands, lift, max_walk
+        if max_total is not None:
+            p.max_total = max_total
+        return p
+
+    def loci_batch(self, seq: np.ndarray, offsets: np.ndarray, strands: int = 1, lift: int = 1, max_walk: int = 1 << 20, max_total: Optional[int] = None):
+        """reference loci (moni_loci_batch): (res, lpos, lseq, lseq_off, support) - res[i * strands + s] (LOCI_RES_DTYPE: count, sa_lo, loci_off, n_loci,
+        matched, walked, n_segs) of pattern i on strand s, and at res["loci_off"] its n_loci distinct lifted positions (lift=0: text positions) in
+        ascending order, the sequence each lies in, the offset inside it and the number of occurrences that land there"""
+        b, keep = self._batch(seq, offsets)
+        n = len(offsets) - 1
+        p = self._loci_params(strands, lift, max_walk, max_total)
+        res = np.zeros(n * strands, dtype=LOCI_RES_DTYPE)
+        hp, hs, ho, hu, nl = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _chk(self._L.moni_loci_batch(self._h, C.byref(b), C.byref(p), res.ctypes.data, C.byref(hp), C.byref(hs), C.byref(ho), C.byref(hu), C.byref(nl)), "moni_loci_batch")
+        self.n_reads = n
+        try:
+            k = nl.value
+            take = lambda h, dt: np.frombuffer(C.string_at(h, k * np.dtype(dt).itemsize), dtype=dt).copy() if k else np.zeros(0, dtype=dt)
+            return res, take(hp, np.uint64), take(hs, np.uint32), take(ho, np.uint64), take(hu, np.uint64)
+        finally:
+            for h in (hp, hs, ho, hu):
+                self._L.moni_free(h)
+
+    def loci_run(self, strands: int = 1, lift: int = 1, max_walk: int = 1 << 20, max_total: Optional[int] = None):
+        """moni_loci_run over the batch made resident by upload(): device only, the results wait for loci_fetch()"""
+        p = self._loci_params(strands, lift, max_walk, max_total)
+        _chk(self._L.moni_loci_run(self._h, C.byref(p)), "moni_loci_run")
+
+    def loci_sizes(self):
+        """(n_tasks, n_loci) of the last loci_run()"""
+        nt, nl = C.c_uint64(), C.c_uint64()
+        _chk(self._L.moni_loci_sizes(self._h, C.byref(nt), C.byref(nl)), "moni_loci_sizes")
+        return nt.value, nl.value
+
+    def loci_fetch(self, want_loci: bool = True):
+        """(res, lpos, lseq, lseq_off, support) of the last loci_run(), sized by moni_loci_sizes; want_loci=False fetches the records alone (the four
+        arrays come back empty)"""
+        nt, nl = self.loci_sizes()
+        k = nl if want_loci else 0
+        res = np.zeros(nt, dtype=LOCI_RES_DTYPE)
+        lp, ls, lo, su = np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.uint32), np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.uint64)
+        ptr = lambda a: a.ctypes.data if k else None
+        _chk(self._L.moni_loci_fetch(self._h, res.ctypes.data, ptr(lp), ptr(ls), ptr(lo), ptr(su)), "moni_loci_fetch")
+        return res, lp, ls, lo, su
 
     def _approx_params(self, strands, k, max_hits, max_occ, chunk_len, max_steps) -> "ApproxParamsC":
         p = ApproxParamsC()

@@ -43,6 +43,7 @@
 #include "pml_kernels.hip"
 #include "locate_kernels.hip"
 #include "seqcount_kernels.hip"
+#include "loci_kernels.hip"
 #include "approx_kernels.hip"
 #include "mslong_kernels.hip"
 
@@ -218,6 +219,11 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
         DBuf<moni_locate_res_t> lres; DBuf<moni_seqcount_res_t> res; DBuf<uint64_t> toe, cnt, off, counts; DBuf<uint32_t> k_lo;
         uint64_t n_tasks = 0, n_segs = 0; uint32_t n_seq = 0; bool valid = false;
     } sc;
+    struct LociBufs {       // reference loci (loci_api.inc): the last run's records and loci, on the device until moni_loci_fetch; grow-only
+        DBuf<moni_locate_res_t> lres; DBuf<moni_seqcount_res_t> sres; DBuf<moni_loci_res_t> res; DBuf<uint64_t> toe, cnt, off, occ_off, keys, sorted, idx, lpos, lseq_off, support;
+        DBuf<uint32_t> k_lo, lseq; DBuf<uint8_t> sort_tmp;
+        uint64_t n_tasks = 0, n_loci = 0, n_segs = 0; bool valid = false;
+    } loci;
     struct ApxBufs {        // k-mismatch queries (approx_api.inc): the last run's records, hits and positions, on the device until moni_approx_fetch; grow-only
         DBuf<moni_approx_res_t> res; DBuf<moni_approx_hit_t> slots, hits; DBuf<apx_ckpt_t> ckpt; DBuf<uint64_t> cnt, ck_off, hit_off, occ_cnt, occ_off, pos, seq_off; DBuf<uint32_t> seq;
         uint64_t n_tasks = 0, n_hits = 0, n_occ = 0; bool valid = false;
@@ -548,7 +554,7 @@ void moni_ctx_destroy(moni_ctx_t* c) {
 
 // A new batch is resident (uploaded, or swapped in): what the last runs left in the context describes another batch
 static void results_invalidate(moni_ctx* c) {
-    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false; c->apx.valid = false;
+    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false; c->apx.valid = false; c->loci.valid = false;
 }
 
 static int reads_upload(moni_ctx* c, const moni_read_batch_t* b, bool keep_host_copy);
@@ -1986,6 +1992,7 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "pml_api.inc"
 #include "locate_api.inc"
 #include "seqcount_api.inc"
+#include "loci_api.inc"
 #include "approx_api.inc"
 #include "mslong_api.inc"
 

@@ -30,7 +30,7 @@ int moni_ms_long_batch(moni_ctx_t* c, const moni_read_batch_t* b, const moni_msl
     st.patterns = nr; st.bases = total;
     // the resident batch is replaced by bytes and offsets alone: nothing of the other entry points can run on it
     c->n_reads = 0; c->total_len = 0; c->max_len = 0; c->h_blk.clear(); c->h_seq.clear(); c->h_offs.clear();
-    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false;
+    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false; c->loci.valid = false;
     for (int e = 0; e < EV_N; ++e) c->ev_valid[e] = false;
     if (!total) { if (stats) *stats = st; return MONI_OK; }
     auto& B = c->msl;

@@ -29,6 +29,10 @@
 // --seq-count [--both-strands] [--max-walk N] writes <out>.seqcount (moni_seqcount_batch: per pattern and strand, the occurrences that start in each
 // sequence of the index): name <+|-> count matched n_seqs seqname:count,... - the sequences with a count, in index order; * for none, ? where the
 // pattern has more than --max-walk occurrences and was not enumerated.
+// --loci [--both-strands] [--max-walk N] [--no-lift] writes <out>.loci (moni_loci_batch: per pattern and strand, the distinct reference positions its
+// occurrences lift to): name <+|-> count matched n_loci seqname:pos:support,... - tab-separated, pos 1-based, the loci in reference order, support the
+// occurrences that land on each; * for none, ? where the pattern has more than --max-walk occurrences and was not enumerated.  --no-lift keeps text
+// positions: every occurrence, in text order, each with support 1.
 // --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N] writes <out>.approx (moni_approx_batch: every string within K <= 3
 // substitutions of the pattern that occurs in the index): per pattern and strand one line `name <+|-> complete cnt0,..,cntK n_hits hits`, tab-separated -
 // complete is 0 where --max-steps stopped a part of the search (the figures are lower bounds then), cnt the text positions at each distance, n_hits the
@@ -57,6 +61,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -204,6 +209,7 @@ struct Args {
     bool locate = false, both_strands = false;        // --locate [--both-strands]: exact-match count and locate of every pattern
     uint32_t max_occ = 0;                             // --max-occ: positions listed per pattern and strand (0: counts alone)
     bool seq_count = false;                           // --seq-count [--both-strands] [--max-walk N]: per-sequence occurrence counts of every pattern
+    bool loci = false, no_lift = false;               // --loci [--both-strands] [--max-walk N] [--no-lift]: the reference loci of every pattern
     uint64_t max_walk = 1ull << 20; bool max_walk_set = false;      // --max-walk: patterns with more occurrences are counted, not enumerated (0: no limit)
     bool approx = false; uint32_t approx_k = 0;      // --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]: count and locate within K substitutions
     uint32_t max_hits = 16; bool max_hits_set = false;      // --max-hits: matching strings listed per pattern and strand
@@ -237,6 +243,8 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--pseudo-ms")) { a.pseudo_ms = true; continue; }
         if (!strcmp(argv[i], "--locate")) { a.locate = true; continue; }
         if (!strcmp(argv[i], "--seq-count")) { a.seq_count = true; continue; }
+        if (!strcmp(argv[i], "--loci")) { a.loci = true; continue; }
+        if (!strcmp(argv[i], "--no-lift")) { a.no_lift = true; continue; }
         if (!strcmp(argv[i], "--max-walk") && i + 1 < argc) { a.max_walk = strtoull(argv[++i], nullptr, 10); a.max_walk_set = true; continue; }
         if (!strcmp(argv[i], "--approx") && i + 1 < argc) { a.approx = true; a.approx_k = (uint32_t)strtoul(argv[++i], nullptr, 10); continue; }
         if (!strcmp(argv[i], "--max-hits") && i + 1 < argc) { a.max_hits = (uint32_t)strtoul(argv[++i], nullptr, 10); a.max_hits_set = true; continue; }
@@ -247,7 +255,7 @@ static void parse(int argc, char** argv, Args& a) {
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
                               "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n";
     int c;
     char* s;
@@ -779,7 +787,7 @@ int main(int argc, char** argv) {
         if (a.legacy_mems) die("--locate cannot be combined with --mems");
         if (a.extend) die("--locate cannot be combined with --extend");
         if (a.pseudo_ms) die("--locate cannot be combined with --pseudo-ms");
-    } else if (!a.approx && ((a.both_strands && !a.seq_count) || a.max_occ)) die("--max-occ / --both-strands belong to --locate");
+    } else if (!a.approx && ((a.both_strands && !a.seq_count && !a.loci) || a.max_occ)) die("--max-occ / --both-strands belong to --locate");
     if (a.seq_count) {       // per-sequence occurrence counts: single-end patterns, one mode at a time
         if (paired) die("--seq-count takes single-end input (-p), not -1 / -2");
         if (a.report_mems) die("--seq-count cannot be combined with -m");
@@ -789,7 +797,19 @@ int main(int argc, char** argv) {
         if (a.extend) die("--seq-count cannot be combined with --extend");
         if (a.pseudo_ms) die("--seq-count cannot be combined with --pseudo-ms");
         if (a.locate) die("--seq-count cannot be combined with --locate");
-    } else if (a.max_walk_set) die("--max-walk belongs to --seq-count");
+    } else if (a.max_walk_set && !a.loci) die("--max-walk belongs to --seq-count / --loci");
+    if (a.loci) {            // reference loci: single-end patterns, one mode at a time
+        if (paired) die("--loci takes single-end input (-p), not -1 / -2");
+        if (a.report_mems) die("--loci cannot be combined with -m");
+        if (a.csv) die("--loci cannot be combined with -c");
+        if (a.legacy_ms) die("--loci cannot be combined with --ms");
+        if (a.legacy_mems) die("--loci cannot be combined with --mems");
+        if (a.extend) die("--loci cannot be combined with --extend");
+        if (a.pseudo_ms) die("--loci cannot be combined with --pseudo-ms");
+        if (a.locate) die("--loci cannot be combined with --locate");
+        if (a.seq_count) die("--loci cannot be combined with --seq-count");
+        if (a.approx) die("--loci cannot be combined with --approx");
+    } else if (a.no_lift) die("--no-lift belongs to --loci");
     if (a.approx) {          // k-mismatch count and locate: single-end patterns, one mode at a time
         if (a.approx_k > MONI_APPROX_MAX_K) die("--approx takes 0 to " + std::to_string(MONI_APPROX_MAX_K) + " mismatches");
         if (paired) die("--approx takes single-end input (-p), not -1 / -2");
@@ -818,7 +838,7 @@ int main(int argc, char** argv) {
     if (!a.output.empty()) sam_filename = a.output;
     if (paired) return run_paired(a, sam_filename);
     const bool legacy = a.legacy_ms || a.legacy_mems;
-    if ((legacy || a.pseudo_ms || a.locate || a.seq_count || a.approx) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate / .seqcount)
+    if ((legacy || a.pseudo_ms || a.locate || a.seq_count || a.loci || a.approx) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate / .seqcount)
     info("Output file: " + sam_filename);
     MappedReader mrd;
     const bool mapped = mrd.open(a.patterns);
@@ -830,11 +850,11 @@ int main(int argc, char** argv) {
         bases = b.seq.size();
         printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : (a.locate ? (a.both_strands ? " mode=locate strands=2" : " mode=locate strands=1") : (a.seq_count ? (a.both_strands ? " mode=seq-count strands=2" : " mode=seq-count strands=1") : (a.approx ? (" mode=approx k=" + std::to_string(a.approx_k) + (a.both_strands ? " strands=2" : " strands=1")).c_str() : "")))));
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : (a.locate ? (a.both_strands ? " mode=locate strands=2" : " mode=locate strands=1") : (a.seq_count ? (a.both_strands ? " mode=seq-count strands=2" : " mode=seq-count strands=1") : (a.loci ? (a.both_strands ? " mode=loci strands=2" : " mode=loci strands=1") : (a.approx ? (" mode=approx k=" + std::to_string(a.approx_k) + (a.both_strands ? " strands=2" : " strands=1")).c_str() : ""))))));
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
-    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && !a.pseudo_ms && !a.locate && !a.seq_count && !a.approx && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
+    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && !a.pseudo_ms && !a.locate && !a.seq_count && !a.loci && !a.approx && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
     const int per_gpu = legacy ? 1 : (fast ? a.ctx_per_gpu : 2);                      // contexts (batches in flight) per GPU
     std::vector<moni_index_t*> idx(a.gpus, nullptr);
     std::vector<moni_ctx_t*> ctx((size_t)a.gpus * per_gpu, nullptr);
@@ -946,6 +966,7 @@ int main(int argc, char** argv) {
     else if (a.pseudo_ms) { out = fopen((sam_filename + ".pseudo_lengths").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".pseudo_lengths failed"); }
     else if (a.locate) { out = fopen((sam_filename + ".locate").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".locate failed"); }
     else if (a.seq_count) { out = fopen((sam_filename + ".seqcount").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".seqcount failed"); }
+    else if (a.loci) { out = fopen((sam_filename + ".loci").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".loci failed"); }
     else if (a.approx) { out = fopen((sam_filename + ".approx").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".approx failed"); }
     else {
         out = fopen(sam_filename.c_str(), "w");
@@ -959,7 +980,7 @@ int main(int argc, char** argv) {
         }
     }
     std::vector<std::string> seq_names;          // --locate / --seq-count: the sequences' names, from the header's @SQ lines (one per sequence of the concatenation, in order)
-    if (a.locate || a.seq_count || a.approx) {
+    if (a.locate || a.seq_count || a.loci || a.approx) {
         char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
         const std::string hs(h, hl); moni_free(h);
         for (size_t at = 0; (at = hs.find("@SQ\tSN:", at)) != std::string::npos;) { at += 7; seq_names.push_back(hs.substr(at, hs.find('\t', at) - at)); }
@@ -1148,6 +1169,45 @@ int main(int argc, char** argv) {
                     if (occurs) ++n_al;
                 }
                 d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
+            } else if (a.loci) {            // one line per pattern and strand: name, strand, count, bytes matched, loci, each locus with its support
+                moni_loci_params_t lp; moni_loci_params_default(&lp);
+                lp.strands = a.both_strands ? 2 : 1; lp.max_walk = a.max_walk; lp.lift = a.no_lift ? 0 : 1;
+                std::string sa;
+                std::vector<moni_loci_res_t> res;
+                // a batch whose occurrences do not fit the library's bound (MONI_ENOMEM) is run in halves, in order
+                std::function<void(size_t, size_t)> part = [&](size_t lo, size_t hi) {
+                    const size_t n = hi - lo;
+                    moni_read_batch_t sub{b.seq.data(), b.off.data() + lo, n};
+                    res.assign(n * lp.strands + 1, moni_loci_res_t());
+                    uint32_t* sq = nullptr; uint64_t* so = nullptr; uint64_t* su = nullptr; uint64_t n_loci = 0;
+                    const int lr = moni_loci_batch(C, &sub, &lp, res.data(), nullptr, &sq, &so, &su, &n_loci);
+                    if (lr == MONI_ENOMEM && n > 1) { part(lo, lo + n / 2); part(lo + n / 2, hi); return; }
+                    if (lr == MONI_ENOMEM) die("--loci: the occurrences of one pattern do not fit in memory; lower --max-walk");
+                    if (lr) die("moni_loci_batch failed (" + std::to_string(lr) + ")");
+                    for (size_t r = lo; r < hi; ++r) {
+                        bool occurs = false;
+                        for (uint32_t s = 0; s < lp.strands; ++s) {
+                            const moni_loci_res_t& R = res[(r - lo) * lp.strands + s];
+                            sa.append((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r]));
+                            sa += s ? "\t-\t" : "\t+\t";
+                            sa += std::to_string(R.count); sa.push_back('\t'); sa += std::to_string(R.matched); sa.push_back('\t'); sa += std::to_string(R.n_loci); sa.push_back('\t');
+                            if (!R.walked) sa.push_back('?');
+                            else if (!R.n_loci) sa.push_back('*');
+                            for (uint64_t k = 0; k < R.n_loci; ++k) {
+                                const uint64_t o = R.loci_off + k;
+                                if (o >= n_loci || sq[o] >= seq_names.size()) die("moni_loci_batch returned a position outside the index");
+                                if (k) sa.push_back(',');
+                                sa += seq_names[sq[o]]; sa.push_back(':'); sa += std::to_string(so[o] + 1); sa.push_back(':'); sa += std::to_string(su[o]);
+                            }
+                            sa.push_back('\n');
+                            occurs = occurs || R.count;
+                        }
+                        if (occurs) ++n_al;
+                    }
+                    moni_free(sq); moni_free(so); moni_free(su);
+                };
+                if (b.n()) part(0, b.n());
+                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
             } else if (a.approx) {          // one line per pattern and strand: name, strand, complete, the counts per distance, the matching strings, those kept
                 moni_approx_params_t ap; moni_approx_params_default(&ap);
                 ap.strands = a.both_strands ? 2 : 1; ap.k = a.approx_k; ap.max_hits = a.max_hits; ap.max_occ = a.max_occ; ap.max_steps = a.max_steps;
@@ -1227,7 +1287,7 @@ int main(int argc, char** argv) {
     close_out(out2);
     delete zrd;
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    info(std::string(a.extend ? "Number of extended reads: " : a.pseudo_ms ? "Number of reads with a pseudo-matching length >= -l: " : (a.locate || a.seq_count || a.approx) ? "Number of patterns that occur: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
+    info(std::string(a.extend ? "Number of extended reads: " : a.pseudo_ms ? "Number of reads with a pseudo-matching length >= -l: " : (a.locate || a.seq_count || a.loci || a.approx) ? "Number of patterns that occur: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
     info("Elapsed time (s): " + std::to_string(el));
     info("Reads per second: " + std::to_string(processed / (el > 0 ? el : 1)));
     info("Stage busy seconds: reader (parse) " + std::to_string(t_reader) + ", library calls summed over " + std::to_string(ctx.size()) + " workers " + std::to_string(t_align) +
