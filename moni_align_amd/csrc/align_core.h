@@ -10,6 +10,7 @@
 #include "../../include/moni_hip.h"
 #include "sort_emul.h"
 #include "lift_core.h"
+#include "chain_core.h"
 
 #if defined(__HIPCC__)
 #define AC_HD __host__ __device__ __forceinline__
@@ -227,27 +228,16 @@ AC_HD_BIG bool ac_chain(ac_ws_t& W, const ac_params_t& P, ac_sec_t* sec) {
             const uint32_t mate_j = nj.mate;
             if (mate_i != mate_j && ((mate_i ^ mate_j) != 3)) continue;
             if (x_i > x_j + P.max_dist_x) { lb = j; continue; }
-            const long long x_d = x_i - x_j, y_d = y_i - y_j;
-            const int32_t l = (int32_t)(y_d > x_d ? (y_d - x_d) : (x_d - y_d));
-            const uint32_t ilog_l = l > 0 ? (uint32_t)ac_ilog2((uint32_t)l) : 0;
-            if (mate_i == mate_j && (y_j >= y_i || y_d > P.max_dist_y)) continue;
-            const long long mn = y_d < x_d ? y_d : x_d;
-            const long long alpha = mn < w_i ? mn : w_i;
-            long long beta = 0;
-            if (mate_i != mate_j) {
-                if (x_d == 0) ++beta;
-                else { const int c_lin = (int)(l * .01 * avg_mem_length); beta = c_lin < (long long)ilog_l ? c_lin : (long long)ilog_l; }
-            } else {
-                beta = l > 0 ? ((long long)(.01 * l * avg_mem_length) + ilog_l) >> 1 : 0;
-            }
-            const long long score = nj.f + (alpha - beta);
+            long long gain;                                                              // alpha - beta: the wide form of chain_core.h
+            if (!cc_gain<long long>(x_i - x_j, y_i, y_j, w_i, mate_i == mate_j, P.max_dist_y, avg_mem_length, gain)) continue;
+            const long long score = nj.f + gain;
             if (score > max_f) { max_f = score; max_j = j; if (n_pred > 0) --n_pred; }
-            else if (sec && (long long)sec[j].f + (alpha - beta) > max_sec_f) {          // chain.hpp:586-612
+            else if (sec && (long long)sec[j].f + gain > max_sec_f) {          // chain.hpp:586-612
                 if (max_j >= 0) {
                     const uint64_t pos_j = nj.x - nj.len + 1;                            // the occurrence the anchor stands for
                     bool uniq = true;
                     for (long long tmp = max_j; tmp >= 0; tmp = W.node[tmp].p) if (W.node[tmp].x - W.node[tmp].len + 1 == pos_j) { uniq = false; break; }
-                    if (uniq) { max_sec_f = (long long)sec[j].f + (alpha - beta); max_sec_j = j; }
+                    if (uniq) { max_sec_f = (long long)sec[j].f + gain; max_sec_j = j; }
                 }
             }
             else if ((size_t)(long long)nj.t == i && (++n_pred > (size_t)P.max_pred)) break;

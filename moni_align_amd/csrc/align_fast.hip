@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "align_core.h"
+#include "chain_core.h"
 #include "render_core.h"
 
 #define AF_MAX_MEMS 64
@@ -154,6 +155,7 @@ struct af_args_t {
     uint32_t l0_mm, l0_ma;                   // capacities (seeds, anchors) of the instance the launch uses for LEVEL 0 (classify_kernel)
     uint32_t wave_max;                       // a group of the WILD / GLOBAL / GWILD queues with at most this many chunks is computed by dp_wave_kernel (af_chunk_kernel decides; MONI_AF_WAVE_MAX)
     uint32_t dbg;                            // AF_PROFILE builds: 1 = no direction stores, 2 = no DP rows (timing experiments; results are wrong)
+    uint32_t chain_narrow;                   // cc_narrow_ok(A.P) (chain_core.h), once per launch: the chaining DP runs in 32-bit integers; 0: the reference's 64-bit form
 };
 #ifdef AF_PROFILE
 #define AF_STAMP(var) const long long var = clock64()
@@ -303,6 +305,9 @@ struct af_grp_t {
     __device__ __forceinline__ unsigned long long lt_mask() const { return (1ull << lane) - 1ull; }
     template <class T> __device__ __forceinline__ T shfl(T v, int src) const { return __shfl(v, base + src); }
     __device__ __forceinline__ int id() const { return base / GW; }
+    // a value that is the same in every lane of the group: with the whole wavefront as the group the compiler is told so (an SGPR: scalar compares and
+    // branches, no VGPR held across the phases); narrower groups of one wavefront differ from each other and keep it per lane
+    __device__ __forceinline__ uint32_t uni(uint32_t v) const { return GW == 64 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)v) : v; }
 };
 
 // std::sort of n <= 16 elements is one insertion sort, i.e. a stable sort: every lane places one element by its stable rank
@@ -334,6 +339,7 @@ __device__ __forceinline__ void af_wave_sort(const GT& g, T* a, uint32_t n, lsor
     const int lane = g.lane;
     auto less = [&](const T& x, const T& y) { return key(x) < key(y); };
     const unsigned long long lt_mask = g.lt_mask();
+    n = g.uni(n);
     if (n > 16) {
         int lg = 0;
         for (uint32_t v = n; v > 1; v >>= 1) ++lg;
@@ -344,9 +350,9 @@ __device__ __forceinline__ void af_wave_sort(const GT& g, T* a, uint32_t n, lsor
         while (sp > 0) {
             const lsort::frame f = st[--sp];
             __syncthreads();
-            long first = f.first, last = f.last, depth = f.depth;
+            long first = (long)g.uni((uint32_t)f.first), last = (long)g.uni((uint32_t)f.last), depth = (long)g.uni((uint32_t)f.depth);
             while (last - first > 16) {
-                if (depth == 0) { if (lane == 0) lsort::heap_sort(a, first, last, less); __syncthreads(); break; }
+                if (depth == 0) { if (lane == 0) lsort::heap_sort_inline(a, first, last, less); __syncthreads(); break; }      // (inlined: a call needs a stack)
                 --depth;
                 const long mid = first + (last - first) / 2;
                 if (lane == 0) lsort::move_median_to_first(a, first, first + 1, mid, last - 1, less);
@@ -356,6 +362,7 @@ __device__ __forceinline__ void af_wave_sort(const GT& g, T* a, uint32_t n, lsor
                 const uint32_t lo = (uint32_t)first + 1, hi = (uint32_t)last;
                 T v[NC]; bool fa[NC], fb[NC]; uint32_t ra[NC], rb[NC];
                 uint32_t nA = 0, nB = 0;
+                // (Measured and not kept, profiles/chain_diet: a wave-uniform skip of the passes c that hold no element - most ranges are shorter than NC * GW.)
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {          // ranks from the left among the elements not below the pivot
                     const uint32_t i = lo + (uint32_t)lane + GW * c;
@@ -387,7 +394,7 @@ __device__ __forceinline__ void af_wave_sort(const GT& g, T* a, uint32_t n, lsor
                     K += (uint32_t)__popcll(g.ballot(sw));
                 }
                 const uint32_t iK = K < nA ? (uint32_t)ipos[K] : 0xFFFFFFFFu, jK1 = K > 0 ? (uint32_t)jpos[K - 1] : 0xFFFFFFFFu;
-                const long cut = (long)(iK < jK1 ? iK : jK1);
+                const long cut = (long)g.uni(iK < jK1 ? iK : jK1);
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
                     if (fa[c] && ra[c] < K) a[jpos[ra[c]]] = v[c];
@@ -427,22 +434,75 @@ __device__ __forceinline__ void af_wave_sort(const GT& g, T* a, uint32_t n, lsor
     __syncthreads();
 }
 
+// The chaining DP (chain.hpp:278-362) of ONE run of the sorted anchors, [fb, fe), by one lane.  I / U: the integers of the differences, scores and indices /
+// of the counts: long long / size_t is the reference's arithmetic for any parameters, int32_t / uint32_t the same values where cc_narrow_ok(P) holds
+// (chain_core.h: no intermediate leaves 32 bits; an index is below MA <= 2048).  The reference ends stay 64 bits up to the distance test.
+template <class I, class U, class WT>
+__device__ __forceinline__ void af_chain_run(WT& L, const ac_params_t& P, uint32_t fb, uint32_t fe, float avg_mem_length, const bool sec) {
+    const I max_iter = (I)P.max_iter, max_dist_y = (I)P.max_dist_y;
+    const U max_pred = (U)P.max_pred;
+    const long long max_dist_x = P.max_dist_x;
+    I lb = (I)fb;
+    for (uint32_t i = fb; i < fe; ++i) {
+        const uint64_t aw = L.anch[i];
+        const af_mem_t mi = L.mem[aw >> 40];
+        const long long x_i = (long long)AF_X(aw);
+        const I y_i = mi.rpos, w_i = mi.len;
+        const uint32_t mate_i = mi.mate;
+        I max_f = w_i, max_j = -1, max_sec_f = w_i, max_sec_j = -1;
+        U n_pred = 0;
+        if ((U)i - (U)lb > (U)max_iter) lb = (I)i - max_iter;
+        for (I j = (I)i - 1; j >= lb; --j) {
+            // (Measured and not kept, profiles/chain_diet: mate and rpos packed into the anchor word, so that the loop does not read mem[].)
+            const uint64_t awj = L.anch[j];
+            const af_mem_t mj = L.mem[awj >> 40];
+            const long long x_j = (long long)AF_X(awj);
+            const I y_j = mj.rpos;
+            const uint32_t mate_j = mj.mate;
+            if (mate_i != mate_j && ((mate_i ^ mate_j) != 3)) continue;
+            if (x_i > x_j + max_dist_x) { lb = j; continue; }
+            I gain;
+            if (!cc_gain<I>((I)(x_i - x_j), y_i, y_j, w_i, mate_i == mate_j, max_dist_y, avg_mem_length, gain)) continue;
+            const I score = (I)L.f[j] + gain;
+            if (score > max_f) { max_f = score; max_j = j; if (n_pred > 0) --n_pred; }
+            else if (WT::SEC && sec && (I)L.f2[j] + gain > max_sec_f) {          // chain.hpp:586-612: the best predecessor that is not on the primary chain of the best one
+                if (max_j >= 0) {
+                    const uint64_t pos_j = (uint64_t)x_j - mj.len + 1;                                // the occurrence the anchor stands for
+                    bool uniq = true;
+                    for (I tmp = max_j; tmp >= 0; tmp = L.p[tmp]) { const uint64_t at = L.anch[tmp]; if (AF_X(at) - L.mem[at >> 40].len + 1 == pos_j) { uniq = false; break; } }
+                    if (uniq) { max_sec_f = (I)L.f2[j] + gain; max_sec_j = j; }
+                }
+            }
+            else if ((U)(I)L.t[j] == (U)i && (++n_pred > max_pred)) break;
+            if (L.p[j] > 0) L.t[L.p[j]] = (int16_t)i;
+            if (WT::SEC && sec && L.p2[j] > 0) L.t2[L.p2[j]] = (int16_t)i;
+        }
+        L.f[i] = (int32_t)max_f; L.p[i] = (int16_t)max_j;
+        L.msc[i] = (max_j >= 0 && L.msc[max_j] > max_f) ? L.msc[max_j] : (int32_t)max_f;
+        if (WT::SEC && sec) { L.f2[i] = (int32_t)max_sec_f; L.p2[i] = (int16_t)max_sec_j; L.msc2[i] = (max_sec_j >= 0 && L.msc2[max_sec_j] > max_sec_f) ? L.msc2[max_sec_j] : (int32_t)max_sec_f; }
+    }
+}
+
 // The whole wave: anchors -> chains (chain.hpp:221-438) over the wave's LDS arrays.  The sorts are the libstdc++ emulation where
 // ties exist (one lane; short arrays by stable rank); the chaining DP and the backtracking run one lane per RUN of anchors: a run
 // is a maximal stretch of the sorted anchors whose consecutive reference ends are at most max_dist_x apart, pairs from different
 // runs never pass the distance test of chain.hpp:300 (or are skipped for their mates before it), so runs share nothing but the
 // lower bound `lb`, which only ever excludes anchors that are too far anyway.  Returns the plan status (uniform).
-template <class WT, class GT = af_grp_t<64>>
+// GEN: the general instance, with both switches at run time - the serial sorts that MONI_AF_DBG=64 selects (out-of-line calls: a stack, and registers
+// spilled around them) and the 64-bit chaining DP, for parameters that cc_narrow_ok does not admit (G.chain_narrow == 0) and for the cross-check.  Without GEN the instance holds
+// neither: the wave's sorts and the 32-bit DP.  chain_plan_kernel is built both ways and launched by the two conditions; the paired kernels are general.
+template <class WT, class GT = af_grp_t<64>, bool GEN = true>
 __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t na, float avg_mem_length, const GT g = GT(), const bool sec_on = false) {
     const ac_params_t& P = G.A.P;
     constexpr uint32_t GW = GT::W;
     const int lane = g.lane;
+    na = g.uni(na);
     // ---- std::sort of the anchors by reference end (chain.hpp:246) ----
     AF_STAMP(s0);
 #if defined(AF_PROFILE) || defined(AF_CUTS)
     if (G.dbg & 32) { /* timing experiment: the anchors stay unsorted */ } else
 #endif
-    if (G.dbg & 64) {          // MONI_AF_DBG=64 (any build): the serial form, for cross-checking the wave's
+    if (GEN && (G.dbg & 64)) {          // MONI_AF_DBG=64 (any build): the serial form, for cross-checking the wave's
         if (na <= 16) af_small_sort(L.anch, na, [](const uint64_t& a, const uint64_t& b) { return AF_X(a) < AF_X(b); }, lane);
         else { if (lane == 0) lsort::sort(L.anch, (long)na, [](const uint64_t& a, const uint64_t& b) { return AF_X(a) < AF_X(b); }, L.stack); __syncthreads(); }
     } else {
@@ -466,55 +526,12 @@ __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t
     if (G.dbg & 128) return AF_ST_UNALIGNED;          // timing experiment: stop after the sort
 #endif
     // ---- chaining DP (chain.hpp:278-362), one lane per run ----
+    // (G.chain_narrow: the host's cc_narrow_ok(P), the same for every lane and every launch of a context's parameters)
     for (uint32_t k = lane; k < n_runs; k += GW) {
         const uint32_t fb = L.run_start[k], fe = L.run_start[k + 1];
-        long long lb = fb;
-        for (uint32_t i = fb; i < fe; ++i) {
-            const uint64_t aw = L.anch[i];
-            const af_mem_t mi = L.mem[aw >> 40];
-            const long long x_i = (long long)AF_X(aw), y_i = mi.rpos, w_i = mi.len;
-            const uint32_t mate_i = mi.mate;
-            long long max_f = w_i, max_j = -1, max_sec_f = w_i, max_sec_j = -1;
-            size_t n_pred = 0;
-            if ((size_t)i - (size_t)lb > (size_t)P.max_iter) lb = (long long)i - P.max_iter;
-            for (long long j = (long long)i - 1; j >= lb; --j) {
-                const uint64_t awj = L.anch[j];
-                const af_mem_t mj = L.mem[awj >> 40];
-                const long long x_j = (long long)AF_X(awj), y_j = mj.rpos;
-                const uint32_t mate_j = mj.mate;
-                if (mate_i != mate_j && ((mate_i ^ mate_j) != 3)) continue;
-                if (x_i > x_j + P.max_dist_x) { lb = j; continue; }
-                const long long x_d = x_i - x_j, y_d = y_i - y_j;
-                const int32_t l = (int32_t)(y_d > x_d ? (y_d - x_d) : (x_d - y_d));
-                const uint32_t ilog_l = l > 0 ? (uint32_t)(31 - __clz(l)) : 0;
-                if (mate_i == mate_j && (y_j >= y_i || y_d > P.max_dist_y)) continue;
-                const long long mn = y_d < x_d ? y_d : x_d;
-                const long long alpha = mn < w_i ? mn : w_i;
-                long long beta = 0;
-                if (mate_i != mate_j) {
-                    if (x_d == 0) ++beta;
-                    else { const int c_lin = (int)(l * .01 * avg_mem_length); beta = c_lin < (long long)ilog_l ? c_lin : (long long)ilog_l; }
-                } else {
-                    beta = l > 0 ? ((long long)(.01 * l * avg_mem_length) + ilog_l) >> 1 : 0;
-                }
-                const long long score = L.f[j] + (alpha - beta);
-                if (score > max_f) { max_f = score; max_j = j; if (n_pred > 0) --n_pred; }
-                else if (WT::SEC && sec_on && (long long)L.f2[j] + (alpha - beta) > max_sec_f) {          // chain.hpp:586-612: the best predecessor that is not on the primary chain of the best one
-                    if (max_j >= 0) {
-                        const uint64_t pos_j = (uint64_t)x_j - mj.len + 1;                                 // the occurrence the anchor stands for
-                        bool uniq = true;
-                        for (long long tmp = max_j; tmp >= 0; tmp = L.p[tmp]) { const uint64_t at = L.anch[tmp]; if (AF_X(at) - L.mem[at >> 40].len + 1 == pos_j) { uniq = false; break; } }
-                        if (uniq) { max_sec_f = (long long)L.f2[j] + (alpha - beta); max_sec_j = j; }
-                    }
-                }
-                else if ((size_t)(long long)L.t[j] == (size_t)i && (++n_pred > (size_t)P.max_pred)) break;
-                if (L.p[j] > 0) L.t[L.p[j]] = (int16_t)i;
-                if (WT::SEC && sec_on && L.p2[j] > 0) L.t2[L.p2[j]] = (int16_t)i;
-            }
-            L.f[i] = (int32_t)max_f; L.p[i] = (int16_t)max_j;
-            L.msc[i] = (max_j >= 0 && L.msc[max_j] > max_f) ? L.msc[max_j] : (int32_t)max_f;
-            if (WT::SEC && sec_on) { L.f2[i] = (int32_t)max_sec_f; L.p2[i] = (int16_t)max_sec_j; L.msc2[i] = (max_sec_j >= 0 && L.msc2[max_sec_j] > max_sec_f) ? L.msc2[max_sec_j] : (int32_t)max_sec_f; }
-        }
+        if (!GEN || (G.chain_narrow && !(G.dbg & 64))) af_chain_run<int32_t, uint32_t>(L, P, fb, fe, avg_mem_length, WT::SEC && sec_on);
+        // (the cross-check runs the reference's arithmetic as well)
+        else af_chain_run<long long, size_t>(L, P, fb, fe, avg_mem_length, WT::SEC && sec_on);
     }
     __syncthreads();
     AF_STAMP(s2); AF_PROF(G, 6, s1, s2);
@@ -616,7 +633,7 @@ __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t
     if (WT::SEC && sec_on) { if (!track(L.f2, L.msc2, L.p2, L.t2, (uint32_t)(WT::MA + WT::MC), true, ns2)) return 0xFFu; }
     __syncthreads();
     // std::sort of the chains by score (chain.hpp:402): ties
-    if (G.dbg & 64) {
+    if (GEN && (G.dbg & 64)) {
         if (n_chains <= 16) af_small_sort(L.chains, n_chains, [](const af_chain_t& x, const af_chain_t& y) { return x.score > y.score; }, lane);
         else { if (lane == 0) lsort::sort(L.chains, (long)n_chains, [](const af_chain_t& x, const af_chain_t& y) { return x.score > y.score; }, L.stack); __syncthreads(); }
     } else          // by the whole wave (run_start and p are free again: scratch)
@@ -891,7 +908,7 @@ __global__ void __launch_bounds__(256) classify_kernel(const af_args_t G) {
 
 // One read of chain_plan_kernel once its seeds and anchors are in LDS: chains (af_chain), check_left_MEM's lifts, the selection loop and the plan
 // (af_plan_cands), the hand-over lists, the plan and the tasks to HBM.  All lanes of the read's group call it.
-template <class WT, int LEVEL, class GT>
+template <class WT, int LEVEL, bool GEN, class GT>
 __device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT g, uint32_t r_in, uint64_t off, uint32_t m, uint32_t na, float avg, bool fallback, bool too_big) {
     constexpr uint32_t GW = GT::W;
     const int lane = g.lane;
@@ -902,7 +919,7 @@ __device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT
     if (G.dbg & 4) na = 0;                                   // timing experiments (results are wrong): stop after the anchors ...
 #endif
     if (!fallback && !too_big && na > 0) {
-        status = af_chain(G, L, na, avg, g);
+        status = af_chain<WT, GT, GEN>(G, L, na, avg, g);
         status = (uint32_t)g.shfl((int)status, 0);
         __syncthreads();
 #if defined(AF_PROFILE) || defined(AF_CUTS)
@@ -1005,7 +1022,9 @@ __device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT
 // wavefront side by side, each in its own copy of WT.
 // (Measured and not kept, profiles/r04f: classify_kernel gathering a read's seeds and anchors into a slot that the LEVEL-0 instance asks for one read ahead - the
 // kernel is bound by VALU issue, not by those loads: 9.36 against 9.2 ms per 1 M reads, and 1.5 ms more in classify_kernel.)
-template <class WT, int LEVEL, int OCC = (LEVEL == 0 ? 6 : LEVEL == 1 ? 3 : 1), int GW = 64>
+// GEN: the general instance (af_chain), launched for MONI_AF_DBG=64 and for chaining parameters beyond cc_narrow_ok: it alone holds the serial sorts of the
+// cross-check and the 64-bit chaining DP.
+template <class WT, int LEVEL, int OCC = (LEVEL == 0 ? 6 : LEVEL == 1 ? 3 : 1), int GW = 64, bool GEN = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) chain_plan_kernel(const af_args_t G) {
     constexpr uint32_t NG = 64 / GW;          // reads per wavefront
     __shared__ WT Ls[NG];                     // one wavefront per workgroup: __syncthreads() orders the wave's own LDS traffic
@@ -1022,14 +1041,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OC
     while (true) {
         if (w_k >= GRAB) {
             if (threadIdx.x == 0) w_base = atomicAdd(&G.ctr[LEVEL == 0 ? AFC_READ_CUR : LEVEL == 1 ? AFC_BIG_CUR : AFC_HUGE_CUR], GRAB * NG);
-            w_base = (uint32_t)__shfl((int)w_base, 0);
+            w_base = GW == 64 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)w_base) : (uint32_t)__shfl((int)w_base, 0);
             w_k = 0;
         }
         if (w_base + w_k * NG >= n_work) break;          // (wave-uniform: the groups leave together)
         const uint32_t w_in = w_base + w_k * NG + (NG > 1 ? (uint32_t)g.id() : 0u);
         ++w_k;
         if (w_in >= n_work) continue;                    // the list's last reads: fewer than the wavefront has groups
-        const uint32_t r_in = work_list[w_in];
+        const uint32_t r_in = g.uni(work_list[w_in]);
         const uint64_t r = A.read_lo + r_in;
         const uint64_t off = A.offs[r];
         const uint32_t m = (uint32_t)(A.offs[r + 1] - off);
@@ -1065,31 +1084,24 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OC
             }
             for (int o = GW / 2; o > 0; o >>= 1) { tot_len += __shfl_xor(tot_len, o); n_anch += __shfl_xor(n_anch, o); }
             if (n_mems > (uint32_t)WT::MM || n_anch > (unsigned long long)WT::MA) too_big = true;
-            na = (uint32_t)n_anch;
+            na = g.uni((uint32_t)n_anch);
             if (!too_big && na > 0) {
                 avg = (float)(size_t)tot_len / (size_t)n_anch;
                 __syncthreads();
-                // ---- populate_anchors (chain.hpp:83-95): mem by mem, occurrence by occurrence ----
-                if (NG > 1) {          // few lanes: every lane finds the seed of its anchors (a seed has about as many occurrences as the index has sequences)
-                    for (uint32_t x = lane; x < na; x += GW) {
-                        uint32_t i = 0, base = 0;
-                        while (base + L.mem[i].nocc <= x) { base += L.mem[i].nocc; ++i; }
-                        const af_mem_t mi = L.mem[i];
-                        L.anch[x] = (A.occs[mi.occ_off + (x - base)] + mi.len - 1) | ((uint64_t)i << 40);
-                    }
-                } else {
-                    uint32_t base = 0;
-                    for (uint32_t i = 0; i < n_mems; ++i) {
-                        const af_mem_t mi = L.mem[i];
-                        for (uint32_t j = lane; j < mi.nocc; j += GW) L.anch[base + j] = (A.occs[mi.occ_off + j] + mi.len - 1) | ((uint64_t)i << 40);
-                        base += mi.nocc;
-                    }
+                // ---- populate_anchors (chain.hpp:83-95): mem by mem, occurrence by occurrence.  Every lane finds the seed of its anchors (a seed has about as
+                // many occurrences as the index has sequences), so all of a read's occurrences are asked for at once: seed by seed they were as many dependent
+                // round trips to HBM as the read has seeds, with a fifth of the lanes at work ----
+                for (uint32_t x = lane; x < na; x += GW) {
+                    uint32_t i = 0, base = 0;
+                    while (base + L.mem[i].nocc <= x) { base += L.mem[i].nocc; ++i; }
+                    const af_mem_t mi = L.mem[i];
+                    L.anch[x] = (A.occs[mi.occ_off + (x - base)] + mi.len - 1) | ((uint64_t)i << 40);
                 }
                 for (uint32_t i = lane; i < na; i += GW) { L.f[i] = 0; L.msc[i] = 0; L.p[i] = 0; L.t[i] = 0; }
             }
         }
         __syncthreads();
-        af_plan_read<WT, LEVEL>(G, L, g, r_in, off, m, na, avg, fallback, too_big);
+        af_plan_read<WT, LEVEL, GEN>(G, L, g, r_in, off, m, na, avg, fallback, too_big);
     }
 }
 

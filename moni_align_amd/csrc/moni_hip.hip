@@ -1533,6 +1533,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                 G.bnd = S.bnd.p;
                 G.pat = c->pat.p; G.blk = c->blk.p; G.text2 = I->d_text2.p; G.exc = I->d_exc.p; G.exc_sh = I->exc_sh; G.pflag = c->pflag.p; G.wave_max = af_wave_max();
                 G.txt_cur = S.txt_cur.p; G.txt_shard_words = txt_per / (AF_TXT_SHARDS + 1);
+                G.chain_narrow = cc_narrow_ok(A.P) ? 1u : 0u;
                 HIPCHK(hipMemsetAsync(S.txt_cur.p, 0, AF_TXT_SHARDS * 8 * sizeof(unsigned long long), sx));
 #ifdef AF_PROFILE
                 if ((rc = S.prof.ensure(32))) return rc;
@@ -1558,24 +1559,30 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                 const bool no_k2 = getenv("MONI_AF_NOPLANK") != nullptr;          // (measurement: the LEVEL-0 instance runs the selection loop and builds the plan itself, as the others do)
                 G.ctab = (no_k2 || l0_mid) ? nullptr : S.ctab.p;
                 hipLaunchKernelGGL(classify_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, sx, G);
+                // MONI_AF_DBG=64, or chaining parameters beyond cc_narrow_ok, launch the general instances, which hold the serial sorts and the 64-bit chaining DP;
+                // the others have no call and no stack in them
+#define AF_LAUNCH_CP(WT, LEVEL, OCC, GW, grid) do { \
+                    if ((G.dbg & 64) || !G.chain_narrow) hipLaunchKernelGGL((chain_plan_kernel<WT, LEVEL, OCC, GW, true>), grid, dim3(64), 0, sx, G); \
+                    else hipLaunchKernelGGL((chain_plan_kernel<WT, LEVEL, OCC, GW, false>), grid, dim3(64), 0, sx, G); } while (0)
                 if (l0_mid) {
                     const dim3 g1((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * 4 * 4));
-                    hipLaunchKernelGGL((chain_plan_kernel<af_wave_mid_t, 0, 4>), g1, dim3(64), 0, sx, G);
+                    AF_LAUNCH_CP(af_wave_mid_t, 0, 4, 64, g1);
                 } else {
                     // four reads per wavefront (16 lanes each, 4 x 4.6 KB of LDS): 8 wavefronts = 32 reads in flight per CU, as with one read per wavefront at
                     // 8 waves/SIMD, but the one-lane sections issue a quarter of the instructions.  MONI_AF_GW=64: one read per wavefront (MONI_AF_K1OCC waves/SIMD)
                     static const int l0_gw = getenv("MONI_AF_GW") ? atoi(getenv("MONI_AF_GW")) : 64;
                     static const int k1occ = getenv("MONI_AF_K1OCC") ? atoi(getenv("MONI_AF_K1OCC")) : (l0_gw == 16 ? 2 : 8);      // one read per wavefront: measured 5, 6, 8 waves/SIMD
                     const dim3 g1((unsigned)std::min<uint64_t>(l0_gw == 16 ? (nr + 3) / 4 : nr, (uint64_t)n_cu * 4 * k1occ));
-                    if (l0_gw == 16) hipLaunchKernelGGL((chain_plan_kernel<af_wave_small_t, 0, 2, 16>), g1, dim3(64), 0, sx, G);
-                    else if (k1occ == 4) hipLaunchKernelGGL((chain_plan_kernel<af_wave_small_t, 0, 4>), g1, dim3(64), 0, sx, G);
-                    else if (k1occ == 5) hipLaunchKernelGGL((chain_plan_kernel<af_wave_small_t, 0, 5>), g1, dim3(64), 0, sx, G);
-                    else if (k1occ == 8) hipLaunchKernelGGL((chain_plan_kernel<af_wave_small_t, 0, 8>), g1, dim3(64), 0, sx, G);
-                    else hipLaunchKernelGGL((chain_plan_kernel<af_wave_small_t, 0, 6>), g1, dim3(64), 0, sx, G);
+                    if (l0_gw == 16) AF_LAUNCH_CP(af_wave_small_t, 0, 2, 16, g1);
+                    else if (k1occ == 4) AF_LAUNCH_CP(af_wave_small_t, 0, 4, 64, g1);
+                    else if (k1occ == 5) AF_LAUNCH_CP(af_wave_small_t, 0, 5, 64, g1);
+                    else if (k1occ == 8) AF_LAUNCH_CP(af_wave_small_t, 0, 8, 64, g1);
+                    else AF_LAUNCH_CP(af_wave_small_t, 0, 6, 64, g1);
                 }
-                hipLaunchKernelGGL((chain_plan_kernel<af_wave_t, 1>), dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * 10)), dim3(64), 0, sx, G);
+                AF_LAUNCH_CP(af_wave_t, 1, 3, 64, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * 10)));
                 static const bool no_huge = getenv("MONI_AF_NOHUGE") != nullptr;          // (debugging aid: reads beyond the large instance then go straight to align_kernel)
-                if (!no_huge) hipLaunchKernelGGL((chain_plan_kernel<af_wave_huge_t, 2>), dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu)), dim3(64), 0, sx, G);      // ~90 KB of LDS per wave: one per CU
+                if (!no_huge) AF_LAUNCH_CP(af_wave_huge_t, 2, 1, 64, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu)));      // ~90 KB of LDS per wave: one per CU
+#undef AF_LAUNCH_CP
                 HIPCHK(hipGetLastError());
                 if (G.ctab) hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, sx, G);
                 hipLaunchKernelGGL(bin_tasks_kernel, dim3((unsigned)((nr + AF_BT_READS - 1) / AF_BT_READS)), dim3(256), 0, sx, G);

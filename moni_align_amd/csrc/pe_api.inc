@@ -223,7 +223,7 @@ static int pe_run(moni_ctx* c, const moni_read_batch_t* b, const moni_align_para
             af_args_t& G = X.G;
             G.A.P = A.PP.P; G.A.D = A.D; G.A.mems = A.mems; G.A.occs = A.occs; G.A.read_mem_off = A.read_mem_off; G.A.offs = A.offs;
             G.A.min_score_of_len = A.min_score_of_len; G.A.max_len = A.max_len; G.A.read_lo = A.pair_lo; G.A.n_reads = A.n_pairs;
-            G.pe = 1; G.pe_sel = c->pe.sel[set].p;
+            G.pe = 1; G.pe_sel = c->pe.sel[set].p; G.chain_narrow = cc_narrow_ok(G.A.P) ? 1u : 0u;
             G.plans = S.plans.p; G.tasks = S.tasks.p; G.task_cap = pf_slot_cap; G.ntasks = S.ntasks.p; G.res = S.res.p; G.bin_q = S.bin_q.p; G.bin_cap = pf_task_cap; G.task_pos = S.task_pos.p;
             G.chunks = S.chunks.p; G.chunk_cap = pf_chunk_cap; G.dirs = S.dirs.p; G.dirs_cap = pf_dirs_cap; G.tb_task = S.tb_task.p; G.tb = S.tb.p; G.tb_cap = pf_tb_cap;
             uint32_t* const fbk = c->pe.fb[0].p + (size_t)k * (CH + 16);

@@ -9,6 +9,7 @@
 #include "../../include/moni_hip.h"
 #include "sort_emul.h"
 #include "lift_core.h"
+#include "chain_core.h"
 #include "pe_big.h"
 
 #define AC_MAX_MEMS 4096

@@ -72,8 +72,9 @@ SORT_HD void adjust_heap(T* a, long first, long hole, long len, T value, Less le
 }
 
 // std::__partial_sort(first, last, last): __heap_select with middle == last is just make_heap, then __sort_heap
+// (heap_sort_inline: for a kernel that is to have no call, and so no stack, in it)
 template <class T, class Less>
-SORT_HD_BIG void heap_sort(T* a, long first, long last, Less less) {
+SORT_HD void heap_sort_inline(T* a, long first, long last, Less less) {
     const long len = last - first;
     if (len >= 2) {
         long parent = (len - 2) / 2;
@@ -92,6 +93,8 @@ SORT_HD_BIG void heap_sort(T* a, long first, long last, Less less) {
         adjust_heap(a, first, 0, l - first, value, less);
     }
 }
+template <class T, class Less>
+SORT_HD_BIG void heap_sort(T* a, long first, long last, Less less) { heap_sort_inline(a, first, last, less); }
 
 template <class T, class Less>
 SORT_HD void unguarded_linear_insert(T* a, long last, Less less) {
