@@ -95,7 +95,7 @@ struct moni_index {
     DBuf<uint32_t> d_phi_dir, d_phi_inv_dir;
     DBuf<uint8_t> d_text;
     DBuf<uint64_t> d_text2; DBuf<uint32_t> d_exc; uint32_t exc_sh = 10, exc_words = 0;      // 2-bit text and its exception bitmap (seed_core.h: mem_fast_t)
-    DBuf<uint32_t> d_kmers; uint32_t pf_k = 0; double pf_density = 0; bool pf_on = false; float pf_build_ms = 0;      // the text's k-mers, one bit each (prefilter_core.h); pf_on: sparse enough to filter with
+    DBuf<uint32_t> d_kmers; uint32_t pf_k = 0; double pf_density = 0; bool pf_on = false; float pf_build_ms = 0; bool compl_acgt = false;      // the text's k-mers, one bit each (prefilter_core.h); pf_on: sparse enough to filter with
     DBuf<uint64_t> d_seq_starts;
     DBuf<uint32_t> d_name_id;
     DBuf<uint8_t> d_snames; DBuf<uint32_t> d_sname_off;      // sequence names, ragged (SAM text in align_kernel)
@@ -132,6 +132,7 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
     DBuf<uint32_t> cnt_m, cnt_s;
     DBuf<uint64_t> pf_flag, pf_pos, pf_live; DBuf<unsigned long long> pf_stats;      // strand prefilter: per task kept or not, the scan, the live tasks in order; skipped tasks and lookups
     int seed_prefilter = 1;                    // moni_seed_prefilter: 0 off, 1 in the align and paired paths, 2 in moni_seed_run too
+    bool seed_fuse = true;                     // the filtered stage runs pack_filter_kernel (MONI_SEED_FUSE=0: pack_kernel + strand_filter_kernel)
     bool pf_active = false;                    // the last ms_launch filtered: pf_live / pf_pos[n_tasks] are the live list and its length
     uint64_t pf_tasks = 0;                     // tasks of the last seeding run
     DBuf<moni_u64x2> mem_slots;
@@ -359,6 +360,7 @@ int moni_index_create(const moni_flat_index_t* f, int device, moni_index_t** out
     I->K = img.K;
     I->lifts_null = lt.all_null;
     std::vector<moni_tables_t> tv(1, img.T);
+    I->compl_acgt = pk_compl_ok(img.T.compl_tab);          // pack_filter_kernel complements codes, not bytes (packfilter_core.h)
     std::vector<uint8_t> text;
     if (f->text) text.assign(f->text, f->text + (f->n - 1));
     else {
@@ -535,6 +537,7 @@ int moni_ctx_create(moni_index_t* I, moni_ctx_t** out) {
     c->idx = I;
     if (const char* v = getenv("MONI_MS_VARIANT")) c->ms_variant = atoi(v);
     if (const char* v = getenv("MONI_EXTZ_LDS")) c->extz_lds = atoi(v);
+    if (const char* v = getenv("MONI_SEED_FUSE")) c->seed_fuse = atoi(v) != 0;
     if (const char* v = getenv("MONI_SEED_PREFILTER")) { const int x = atoi(v); if (x >= 0 && x <= 2) c->seed_prefilter = x; }
     bool ok = hipStreamCreate(&c->stream.h) == hipSuccess;
     for (int i = 0; ok && i < EV_N; ++i) ok = hipEventCreate(&c->ev[i].h) == hipSuccess;
@@ -614,7 +617,7 @@ int moni_reads_swap(moni_ctx_t* c, uint32_t slot) {
 
 // tabs: the byte tables pack_kernel derives strand 1 with (default: the index's own, kpbseq.h:120-137; extend mode brings its complement)
 // filter_min_len > 0 (seed_all alone; it has made cnt_m / cnt_s): the strand prefilter runs behind pack_kernel, and the walk takes the live tasks only -
-// the pointers of a skipped task are not written.  Every other caller gets all of them.
+// the pointers of a skipped task are not written, nor (with pack_filter_kernel in place of the two kernels) its byte words.  Every other caller gets all of them.
 static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr, uint32_t filter_min_len = 0) {
     moni_index* I = c->idx;
     if (!tabs) tabs = I->d_tables.p;
@@ -623,15 +626,26 @@ static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr, uint32_t 
     if (c->h_blk.empty()) return MONI_EINVAL;
     if ((rc = c->ptr.ensure(c->h_blk.back().x + 1)) || (rc = c->pat.ensure(c->h_blk.back().y + 1)) || (rc = c->pflag.ensure(n_tasks + 8))) return rc;
     const unsigned grid = (unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK);
-    if (n_tasks)
+    // the filtered stage packs and filters in one kernel (pack_filter_kernel: no byte words for a skipped task) where the tables are the index's own and
+    // their complement is the one its arithmetic assumes; MONI_SEED_FUSE=0 keeps the two kernels
+    const bool fuse = n_tasks && filter_min_len && tabs == I->d_tables.p && I->compl_acgt && c->seed_fuse;
+    if (fuse && ((rc = c->pf_flag.ensure(n_tasks + 2)) || (rc = c->pf_pos.ensure(n_tasks + 2)) || (rc = c->pf_live.ensure(n_tasks + 2)))) return rc;
+    if (fuse) {
+        const unsigned grid_r = (unsigned)((c->n_reads + 1 + MS_BLOCK - 1) / MS_BLOCK);
+#define PF_LAUNCH(W) hipLaunchKernelGGL((pack_filter_kernel<W>), dim3(grid_r), dim3(MS_BLOCK), 0, c->stream, I->K, tabs, c->seq.p, c->offs.p, c->blk.p, c->n_reads, c->pat.p, c->pflag.p, \
+                                        filter_min_len, I->pf_k, I->d_kmers.p, c->pf_flag.p, c->cnt_m.p, c->cnt_s.p, c->pf_stats.p)
+        if (c->max_len <= 160) PF_LAUNCH(5); else PF_LAUNCH(8);
+#undef PF_LAUNCH
+    } else if (n_tasks)
         hipLaunchKernelGGL(pack_kernel, dim3(grid), dim3(MS_BLOCK), 0, c->stream, I->K, tabs, c->seq.p, c->offs.p, c->blk.p, n_tasks, c->pat.p, c->pflag.p);
     rec(c, EV_MS0);
     c->pf_active = false;
     const uint64_t* live = nullptr; const uint64_t* n_live = nullptr;
     if (n_tasks && filter_min_len) {          // flags, their scan (the live count stays on the device: no synchronisation), the list
         if ((rc = c->pf_flag.ensure(n_tasks + 2)) || (rc = c->pf_pos.ensure(n_tasks + 2)) || (rc = c->pf_live.ensure(n_tasks + 2))) return rc;
-        hipLaunchKernelGGL(strand_filter_kernel, dim3((unsigned)((n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, c->pat.p, c->offs.p, c->blk.p, c->pflag.p, n_tasks,
-                           filter_min_len, I->pf_k, I->d_kmers.p, c->pf_flag.p, c->cnt_m.p, c->cnt_s.p, c->pf_stats.p);
+        if (!fuse)
+            hipLaunchKernelGGL(strand_filter_kernel, dim3((unsigned)((n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, c->pat.p, c->offs.p, c->blk.p, c->pflag.p, n_tasks,
+                               filter_min_len, I->pf_k, I->d_kmers.p, c->pf_flag.p, c->cnt_m.p, c->cnt_s.p, c->pf_stats.p);
         if ((rc = exclusive_scan_u64(c, c->pf_flag.p, c->pf_pos.p, n_tasks + 1))) return rc;
         hipLaunchKernelGGL(live_list_kernel, dim3((unsigned)((n_tasks + 255) / 256)), dim3(256), 0, c->stream, c->pf_flag.p, c->pf_pos.p, n_tasks, c->pf_live.p);
         live = c->pf_live.p; n_live = c->pf_pos.p + n_tasks;

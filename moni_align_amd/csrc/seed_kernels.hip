@@ -11,6 +11,7 @@
 
 #include "seed_core.h"
 #include "prefilter_core.h"
+#include "packfilter_core.h"
 
 #define MS_BLOCK 256
 #ifndef MS_CHAINS
@@ -136,6 +137,27 @@ strand_filter_kernel(const uint64_t* __restrict__ pat, const uint64_t* __restric
         flag[task] = keep ? 1u : 0u;
         if (!keep) { cnt_m[task] = 0; cnt_s[task] = 0; skipped = 1; }
     } else if (task == n_tasks) flag[task] = 0;
+    wave_add(skipped, &stats[0]);
+    wave_add(n_lookups, &stats[1]);
+}
+// pack_kernel and strand_filter_kernel in one, for the filtered seeding stage (packfilter_core.h): one lane per READ packs both tasks and decides them
+// on code words held in its LDS column, and writes byte words only for a task that stays.  W: code words per strand and lane (reads of up to 32 W
+// bases take the arithmetic form; longer ones in the same launch take pack_task and the filter as they are).  Same outputs and statistics as the two.
+template <int W>
+__global__ void __launch_bounds__(MS_BLOCK)
+pack_filter_kernel(const moni_consts_t K, const moni_tables_t* __restrict__ T, const uint8_t* __restrict__ seq, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk,
+                   uint64_t n_reads, uint64_t* __restrict__ pat, uint8_t* __restrict__ pflag, uint32_t min_len, uint32_t k, const uint32_t* __restrict__ tab,
+                   uint64_t* __restrict__ flag, uint32_t* __restrict__ cnt_m, uint32_t* __restrict__ cnt_s, unsigned long long* __restrict__ stats) {
+    __shared__ lds_tables_t L;
+    __shared__ uint64_t CW[2 * W][MS_BLOCK];             // [strand * W + word][lane]
+    load_tables(L, T, K);
+    const uint64_t read = (uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
+    unsigned long long n_lookups = 0, skipped = 0;
+    if (read < n_reads) {
+        pk_args_t A;
+        A.min_len = min_len; A.k = k; A.tab = tab; A.cw = &CW[0][threadIdx.x]; A.cw_stride = MS_BLOCK; A.cw_words = W;
+        pack_filter_read(L, A, seq, offs, blk, read, pat, pflag, flag, cnt_m, cnt_s, n_lookups, skipped);
+    } else if (read == n_reads) flag[2 * n_reads] = 0;
     wave_add(skipped, &stats[0]);
     wave_add(n_lookups, &stats[1]);
 }
