@@ -371,6 +371,38 @@ int moni_pml_fetch(moni_ctx_t *ctx, uint32_t *lengths, uint32_t *read_max, uint3
  * MONI_EINVAL where moni_pml_fetch gives it. */
 int moni_pml_sizes(moni_ctx_t *ctx, uint64_t *n_reads, uint64_t *total_len);
 
+/* ---- read screening: present / absent calls from pseudo-matching lengths against the read's own null ---- */
+/* Every read is walked as four strings: P0 its bytes as they are (the string of moni_pml_batch), P1 its reverse complement by the index's
+ * complement table, and the reverse - not complemented - of each, N0 and N1: the same composition, no homology.  Offsets are cut into windows of
+ * `window`; a window is scored if it holds at least min_win offsets.  The score of a window is the one-sided Kolmogorov-Smirnov numerator
+ * D = max over v in 0 .. MONI_SCREEN_BINS - 2 of #{null lengths <= v} - #{pattern lengths <= v}, lengths clipped to MONI_SCREEN_BINS - 1; a scored
+ * window of len offsets is positive when D * ks_den >= ks_num * len.  All arithmetic is integer. */
+#define MONI_SCREEN_BINS 32
+#define MONI_SCREEN_PRESENT 1u      /* 2 * n_pos[s] > n_win on either strand */
+#define MONI_SCREEN_STRAND1 2u      /* n_pos[1] > n_pos[0] */
+#define MONI_SCREEN_SHORT 4u        /* n_win == 0: never present */
+typedef struct { uint32_t window;    /* 8 .. 65535 */
+                 uint32_t min_win;   /* 1 .. window */
+                 uint32_t ks_num, ks_den;   /* 1 <= ks_num <= ks_den <= 65535 */
+                 uint32_t strands;   /* 1: P0 / N0 alone (the fields of strand 1 are 0), 2: both */
+                 uint32_t reserved[3]; } moni_screen_params_t;
+/* n_win: scored windows (the same on both strands); per strand s: n_pos[s] positive windows, d_max[s] the largest D of a scored window,
+ * max_pml[s] the largest unclipped pseudo-matching length of Ps. */
+typedef struct { uint32_t n_win, n_pos[2], d_max[2], max_pml[2], flags; } moni_screen_res_t;
+void moni_screen_params_default(moni_screen_params_t *p);            /* window 50, min_win 25, ks 1/4, strands 2 */
+/* Device-only run over the batch that moni_reads_upload made resident; one record per read stays in HBM, nothing per base or per window is
+ * written.  MONI_EINVAL: a parameter outside its range, a non-zero reserved word, no resident batch.  moni_last_kernel_ms(ctx, 0, ..) then gives
+ * screen_kernel's time, (ctx, 6, ..) the whole run's (pack_kernel included); moni_last_counters: [0] steps = 2 * strands * bases, [1] threshold
+ * jumps of all strings, [2] those of the P0 strings alone. */
+int moni_screen_run(moni_ctx_t *ctx, const moni_screen_params_t *prm);
+/* What moni_screen_fetch would write: the reads of the batch of the last moni_screen_run (the pointer may be NULL); MONI_EINVAL before any run,
+ * and after another batch was made resident (moni_reads_upload, moni_reads_swap, any *_batch call). */
+int moni_screen_sizes(moni_ctx_t *ctx, uint64_t *n_reads);
+/* The records of the last moni_screen_run on this context: res holds *n_reads of them. */
+int moni_screen_fetch(moni_ctx_t *ctx, moni_screen_res_t *res);
+/* Host-buffer form: upload, run, fetch.  res: batch->n_reads records (the caller's).  An empty batch gives MONI_OK and writes nothing. */
+int moni_screen_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const moni_screen_params_t *prm, moni_screen_res_t *res);
+
 /* ---- exact-match count and locate: what ri::r_index::count / locate_all give the users of ms_pointers (include/ms/moni.hpp: ms_pointers derives
  * from ri::r_index) ---- */
 /* A backward search of every pattern of the batch over the BWT the matching-statistics walk reads.  Strand 0 takes the pattern's bytes as they are

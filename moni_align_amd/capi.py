@@ -31,6 +31,7 @@ EXPORTS = [
     "moni_pe_params_default", "moni_pe_learn_batch", "moni_pe_align_batch", "moni_pe_align_stream", "moni_pe_align_run", "moni_pe_align_csv_batch", "moni_pe_report_mems_batch",
     "moni_extend_params_default", "moni_extend_batch", "moni_extend_run",
     "moni_pml_batch", "moni_pml_run", "moni_pml_fetch", "moni_pml_sizes",
+    "moni_screen_params_default", "moni_screen_run", "moni_screen_sizes", "moni_screen_fetch", "moni_screen_batch",
     "moni_locate_params_default", "moni_locate_run", "moni_locate_sizes", "moni_locate_fetch", "moni_locate_batch",
     "moni_seqcount_params_default", "moni_seqcount_run", "moni_seqcount_sizes", "moni_seqcount_fetch", "moni_seqcount_batch",
     "moni_loci_params_default", "moni_loci_run", "moni_loci_sizes", "moni_loci_fetch", "moni_loci_batch",
@@ -98,6 +99,11 @@ class ExtendStatsC(C.Structure):
                 ("t_kernel", C.c_double)]
 
 
+class ScreenParamsC(C.Structure):
+    _fields_ = [("window", C.c_uint32), ("min_win", C.c_uint32), ("ks_num", C.c_uint32), ("ks_den", C.c_uint32), ("strands", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
 class LocateParamsC(C.Structure):
     _fields_ = [("strands", C.c_uint32), ("max_occ", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
@@ -148,6 +154,9 @@ APPROX_MAX_STEPS_DEFAULT = 1 << 20
 APPROX_CHUNK_LEN_DEFAULT = 1 << 30
 assert LOCATE_RES_DTYPE.itemsize == 32 and SEQCOUNT_RES_DTYPE.itemsize == 32 and APPROX_RES_DTYPE.itemsize == 64 and APPROX_HIT_DTYPE.itemsize == 40
 assert LOCI_RES_DTYPE.itemsize == 48
+SCREEN_RES_DTYPE = np.dtype([("n_win", "<u4"), ("n_pos", "<u4", (2,)), ("d_max", "<u4", (2,)), ("max_pml", "<u4", (2,)), ("flags", "<u4")])
+SCREEN_BINS, SCREEN_PRESENT, SCREEN_STRAND1, SCREEN_SHORT = 32, 1, 2, 4
+assert SCREEN_RES_DTYPE.itemsize == 32 and C.sizeof(ScreenParamsC) == 32
 assert MEM_DTYPE.itemsize == 48 and DP_TASK_DTYPE.itemsize == 32 and DP_RESULT_DTYPE.itemsize == 48
 
 DEFAULT_MAT = [2, -4, -4, -4, 0, -4, 2, -4, -4, 0, -4, -4, 2, -4, 0, -4, -4, -4, 2, 0, 0, 0, 0, 0, 0]
@@ -225,6 +234,12 @@ def lib():
         L.moni_pml_run.argtypes = [C.c_void_p, C.c_uint32]
         L.moni_pml_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.moni_pml_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.moni_screen_params_default.argtypes = [C.POINTER(ScreenParamsC)]
+        L.moni_screen_params_default.restype = None
+        L.moni_screen_run.argtypes = [C.c_void_p, C.POINTER(ScreenParamsC)]
+        L.moni_screen_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.moni_screen_fetch.argtypes = [C.c_void_p, C.c_void_p]
+        L.moni_screen_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.POINTER(ScreenParamsC), C.c_void_p]
         L.moni_locate_params_default.argtypes = [C.POINTER(LocateParamsC)]
         L.moni_locate_params_default.restype = None
         L.moni_locate_run.argtypes = [C.c_void_p, C.POINTER(LocateParamsC)]
@@ -651,6 +666,38 @@ class Ctx:
         hits = np.zeros(nr.value, dtype=np.uint32)
         _chk(self._L.moni_pml_fetch(self._h, ln.ctypes.data if want_lengths else None, mx.ctypes.data, hits.ctypes.data), "moni_pml_fetch")
         return ln, mx, hits
+
+    def _screen_params(self, overrides) -> "ScreenParamsC":
+        p = ScreenParamsC()
+        self._L.moni_screen_params_default(C.byref(p))
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        return p
+
+    def screen_batch(self, seq: np.ndarray, offsets: np.ndarray, **overrides):
+        """read screening (moni_screen_batch): one record per read (SCREEN_RES_DTYPE: n_win, n_pos[2], d_max[2], max_pml[2], flags) - the windows
+        of pseudo-matching lengths of either strand against those of the read reversed.  overrides: fields of moni_screen_params_t (window,
+        min_win, ks_num, ks_den, strands)."""
+        b, keep = self._batch(seq, offsets)
+        n = len(offsets) - 1
+        p = self._screen_params(overrides)
+        res = np.zeros(n, dtype=SCREEN_RES_DTYPE)
+        _chk(self._L.moni_screen_batch(self._h, C.byref(b), C.byref(p), res.ctypes.data if n else None), "moni_screen_batch")
+        self.n_reads = n
+        return res
+
+    def screen_run(self, **overrides):
+        """moni_screen_run over the batch made resident by upload(): device only, the records wait for screen_fetch()"""
+        p = self._screen_params(overrides)
+        _chk(self._L.moni_screen_run(self._h, C.byref(p)), "moni_screen_run")
+
+    def screen_fetch(self) -> np.ndarray:
+        """the records of the last screen_run(), as many as the library says that run covered (moni_screen_sizes)"""
+        nr = C.c_uint64()
+        _chk(self._L.moni_screen_sizes(self._h, C.byref(nr)), "moni_screen_sizes")
+        res = np.zeros(nr.value, dtype=SCREEN_RES_DTYPE)
+        _chk(self._L.moni_screen_fetch(self._h, res.ctypes.data if nr.value else None), "moni_screen_fetch")
+        return res
 
     def _locate_params(self, strands: int, max_occ: int) -> "LocateParamsC":
         p = LocateParamsC()

@@ -41,6 +41,7 @@
 #include "pe_lines.hip"
 #include "extend_kernels.hip"
 #include "pml_kernels.hip"
+#include "screen_kernels.hip"
 #include "locate_kernels.hip"
 #include "seqcount_kernels.hip"
 #include "loci_kernels.hip"
@@ -213,6 +214,9 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
     struct PmlBufs {        // pseudo-matching lengths (pml_api.inc): the last run's results, on the device until moni_pml_fetch
         DBuf<uint32_t> lens, mx, hits; uint64_t n_reads = 0, total = 0; bool valid = false;
     } pml;
+    struct ScreenBufs {     // read screening (screen_api.inc): the last run's records, on the device until moni_screen_fetch
+        DBuf<moni_screen_res_t> res; uint64_t n_reads = 0; bool valid = false;
+    } scr;
     struct LocBufs {        // exact-match count / locate (locate_api.inc): the last run's results, on the device until moni_locate_fetch; grow-only
         DBuf<moni_locate_res_t> res; DBuf<uint64_t> toe, cnt, off, pos, seq_off; DBuf<uint32_t> seq; uint64_t n_tasks = 0, n_occ = 0; bool valid = false;
     } loc;
@@ -557,7 +561,7 @@ void moni_ctx_destroy(moni_ctx_t* c) {
 
 // A new batch is resident (uploaded, or swapped in): what the last runs left in the context describes another batch
 static void results_invalidate(moni_ctx* c) {
-    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->loc.valid = false; c->sc.valid = false; c->apx.valid = false; c->loci.valid = false;
+    c->n_mems = c->n_occs = 0; c->occs_valid = false; c->pml.valid = false; c->scr.valid = false; c->loc.valid = false; c->sc.valid = false; c->apx.valid = false; c->loci.valid = false;
 }
 
 static int reads_upload(moni_ctx* c, const moni_read_batch_t* b, bool keep_host_copy);
@@ -2011,6 +2015,7 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "pe_api.inc"
 #include "extend_api.inc"
 #include "pml_api.inc"
+#include "screen_api.inc"
 #include "locate_api.inc"
 #include "seqcount_api.inc"
 #include "loci_api.inc"

@@ -26,6 +26,10 @@
 // reads, the same path as -m; its @HD line has the tabs of moni_sam_header where the reference's extender writes blanks.
 // --pseudo-ms writes <out>.pseudo_lengths, the text of the legacy `moni pseudo-ms` (src/spumoni/run_spumoni.cpp:466-501; moni_pml_batch): per read a
 // line ">" + the read's running number in the input, then its pseudo-matching lengths, each followed by a blank.  Single-end reads, the same path as -m.
+// --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] writes <out>.screen (moni_screen_batch: every read called present or absent from its
+// pseudo-matching lengths on both strands against those of the read reversed): per read, in input order, one line
+// `name length P|A|S +|-|. n_win n_pos0 n_pos1 d_max0 d_max1 max_pml0 max_pml1`, tab-separated - P present, A absent, S too short for a scored window; the strand
+// column is . unless the read is present.  Single-end reads, the same path as -m.
 // --seq-count [--both-strands] [--max-walk N] writes <out>.seqcount (moni_seqcount_batch: per pattern and strand, the occurrences that start in each
 // sequence of the index): name <+|-> count matched n_seqs seqname:count,... - the sequences with a count, in index order; * for none, ? where the
 // pattern has more than --max-walk occurrences and was not enumerated.
@@ -206,6 +210,7 @@ struct Args {
     bool split = false; uint32_t seg_len = 0, overlap = 0; bool seg_len_set = false, overlap_set = false;      // --ms / --mems --split [--seg-len N] [--overlap N]: long patterns, moni_ms_long_batch
     bool extend = false;                              // --extend: the legacy `moni extend` (longest MEM of each strand, extended to both sides)
     bool pseudo_ms = false;                           // --pseudo-ms: the legacy `moni pseudo-ms` (pseudo-matching lengths of every read)
+    bool screen = false, one_strand = false, screen_opt = false; moni_screen_params_t SP;      // --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand]: present / absent calls (screen_opt: one of its options was given)
     bool locate = false, both_strands = false;        // --locate [--both-strands]: exact-match count and locate of every pattern
     uint32_t max_occ = 0;                             // --max-occ: positions listed per pattern and strand (0: counts alone)
     bool seq_count = false;                           // --seq-count [--both-strands] [--max-walk N]: per-sequence occurrence counts of every pattern
@@ -226,6 +231,7 @@ struct Args {
 static void parse(int argc, char** argv, Args& a) {
     moni_align_params_default(&a.P);
     moni_pe_params_default(&a.PE);
+    moni_screen_params_default(&a.SP);
     a.P.n_seeds_thr = 5000; a.P.freq_thr = 0.30;          // struct defaults of align_full_ksw2.cpp:70,73 (the wrapper always passes -S/-F)
     std::vector<char*> av;
     for (int i = 0; i < argc; ++i) {
@@ -241,6 +247,16 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--overlap") && i + 1 < argc) { a.overlap = (uint32_t)strtoul(argv[++i], nullptr, 10); a.overlap_set = true; continue; }
         if (!strcmp(argv[i], "--extend")) { a.extend = true; continue; }
         if (!strcmp(argv[i], "--pseudo-ms")) { a.pseudo_ms = true; continue; }
+        if (!strcmp(argv[i], "--screen")) { a.screen = true; continue; }
+        if (!strcmp(argv[i], "--window") && i + 1 < argc) { a.SP.window = (uint32_t)strtoul(argv[++i], nullptr, 10); a.screen_opt = true; continue; }
+        if (!strcmp(argv[i], "--min-win") && i + 1 < argc) { a.SP.min_win = (uint32_t)strtoul(argv[++i], nullptr, 10); a.screen_opt = true; continue; }
+        if (!strcmp(argv[i], "--ks") && i + 1 < argc) {          // NUM/DEN
+            char* e = nullptr;
+            a.SP.ks_num = (uint32_t)strtoul(argv[++i], &e, 10);
+            a.SP.ks_den = *e == '/' ? (uint32_t)strtoul(e + 1, nullptr, 10) : 0;
+            a.screen_opt = true; continue;
+        }
+        if (!strcmp(argv[i], "--one-strand")) { a.one_strand = true; a.screen_opt = true; continue; }
         if (!strcmp(argv[i], "--locate")) { a.locate = true; continue; }
         if (!strcmp(argv[i], "--seq-count")) { a.seq_count = true; continue; }
         if (!strcmp(argv[i], "--loci")) { a.loci = true; continue; }
@@ -255,7 +271,7 @@ static void parse(int argc, char** argv, Args& a) {
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
                               "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n";
     int c;
     char* s;
@@ -779,6 +795,23 @@ int main(int argc, char** argv) {
         if (a.legacy_mems) die("--pseudo-ms cannot be combined with --mems");
         if (a.extend) die("--pseudo-ms cannot be combined with --extend");
     }
+    if (a.screen) {          // read screening: single-end reads, one mode at a time
+        if (paired) die("--screen takes single-end input (-p), not -1 / -2");
+        if (a.report_mems) die("--screen cannot be combined with -m");
+        if (a.csv) die("--screen cannot be combined with -c");
+        if (a.legacy_ms) die("--screen cannot be combined with --ms");
+        if (a.legacy_mems) die("--screen cannot be combined with --mems");
+        if (a.extend) die("--screen cannot be combined with --extend");
+        if (a.pseudo_ms) die("--screen cannot be combined with --pseudo-ms");
+        if (a.locate) die("--screen cannot be combined with --locate");
+        if (a.seq_count) die("--screen cannot be combined with --seq-count");
+        if (a.loci) die("--screen cannot be combined with --loci");
+        if (a.approx) die("--screen cannot be combined with --approx");
+        a.SP.strands = a.one_strand ? 1 : 2;
+        if (a.SP.window < 8 || a.SP.window > 65535) die("--window takes 8 to 65535");
+        if (a.SP.min_win < 1 || a.SP.min_win > a.SP.window) die("--min-win takes 1 to --window");
+        if (a.SP.ks_num < 1 || a.SP.ks_num > a.SP.ks_den || a.SP.ks_den > 65535) die("--ks takes NUM/DEN with 1 <= NUM <= DEN <= 65535");
+    } else if (a.screen_opt) die("--window / --min-win / --ks / --one-strand belong to --screen");
     if (a.locate) {          // exact-match count and locate: single-end patterns, one mode at a time
         if (paired) die("--locate takes single-end input (-p), not -1 / -2");
         if (a.report_mems) die("--locate cannot be combined with -m");
@@ -838,7 +871,7 @@ int main(int argc, char** argv) {
     if (!a.output.empty()) sam_filename = a.output;
     if (paired) return run_paired(a, sam_filename);
     const bool legacy = a.legacy_ms || a.legacy_mems;
-    if ((legacy || a.pseudo_ms || a.locate || a.seq_count || a.loci || a.approx) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate / .seqcount)
+    if ((legacy || a.pseudo_ms || a.screen || a.locate || a.seq_count || a.loci || a.approx) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate / .seqcount)
     info("Output file: " + sam_filename);
     MappedReader mrd;
     const bool mapped = mrd.open(a.patterns);
@@ -850,11 +883,11 @@ int main(int argc, char** argv) {
         bases = b.seq.size();
         printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : (a.locate ? (a.both_strands ? " mode=locate strands=2" : " mode=locate strands=1") : (a.seq_count ? (a.both_strands ? " mode=seq-count strands=2" : " mode=seq-count strands=1") : (a.loci ? (a.both_strands ? " mode=loci strands=2" : " mode=loci strands=1") : (a.approx ? (" mode=approx k=" + std::to_string(a.approx_k) + (a.both_strands ? " strands=2" : " strands=1")).c_str() : ""))))));
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : a.screen ? (a.one_strand ? " mode=screen strands=1" : " mode=screen strands=2") : (a.locate ? (a.both_strands ? " mode=locate strands=2" : " mode=locate strands=1") : (a.seq_count ? (a.both_strands ? " mode=seq-count strands=2" : " mode=seq-count strands=1") : (a.loci ? (a.both_strands ? " mode=loci strands=2" : " mode=loci strands=1") : (a.approx ? (" mode=approx k=" + std::to_string(a.approx_k) + (a.both_strands ? " strands=2" : " strands=1")).c_str() : ""))))));
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
-    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && !a.pseudo_ms && !a.locate && !a.seq_count && !a.loci && !a.approx && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
+    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && !a.pseudo_ms && !a.screen && !a.locate && !a.seq_count && !a.loci && !a.approx && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
     const int per_gpu = legacy ? 1 : (fast ? a.ctx_per_gpu : 2);                      // contexts (batches in flight) per GPU
     std::vector<moni_index_t*> idx(a.gpus, nullptr);
     std::vector<moni_ctx_t*> ctx((size_t)a.gpus * per_gpu, nullptr);
@@ -964,6 +997,7 @@ int main(int argc, char** argv) {
     if (a.legacy_ms) { out = fopen((sam_filename + ".pointers").c_str(), "w"); out2 = fopen((sam_filename + ".lengths").c_str(), "w"); if (!out || !out2) die("open() file " + sam_filename + ".pointers/.lengths failed"); }
     else if (a.legacy_mems) { out = fopen((sam_filename + ".mems").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".mems failed"); }
     else if (a.pseudo_ms) { out = fopen((sam_filename + ".pseudo_lengths").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".pseudo_lengths failed"); }
+    else if (a.screen) { out = fopen((sam_filename + ".screen").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".screen failed"); }
     else if (a.locate) { out = fopen((sam_filename + ".locate").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".locate failed"); }
     else if (a.seq_count) { out = fopen((sam_filename + ".seqcount").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".seqcount failed"); }
     else if (a.loci) { out = fopen((sam_filename + ".loci").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".loci failed"); }
@@ -1103,6 +1137,24 @@ int main(int argc, char** argv) {
                     for (size_t k = 0; k < m; ++k) { const int nc = snprintf(num, sizeof num, "%u ", len[o + k]); sa.append(num, (size_t)nc); }
                     sa.push_back('\n');
                     if (hits[r]) ++n_al;          // reads with a length >= -l somewhere
+                }
+                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
+            } else if (a.screen) {          // one line per read: name, length, call, strand, scored windows, then per strand positive windows, largest D, largest length
+                std::vector<moni_screen_res_t> res(b.n() + 1);
+                const int sr = moni_screen_batch(C, &rb, &a.SP, res.data());
+                if (sr) die("moni_screen_batch failed (" + std::to_string(sr) + ")");
+                std::string sa;
+                sa.reserve(b.n() * 64 + b.names.size());
+                char num[128];
+                for (size_t r = 0; r < b.n(); ++r) {
+                    const moni_screen_res_t& R = res[r];
+                    const bool present = (R.flags & MONI_SCREEN_PRESENT) != 0;
+                    sa.append((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r]));
+                    const int nc = snprintf(num, sizeof num, "\t%llu\t%c\t%c\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", (unsigned long long)(b.off[r + 1] - b.off[r]),
+                                            (R.flags & MONI_SCREEN_SHORT) ? 'S' : present ? 'P' : 'A', !present ? '.' : (R.flags & MONI_SCREEN_STRAND1) ? '-' : '+', R.n_win, R.n_pos[0],
+                                            R.n_pos[1], R.d_max[0], R.d_max[1], R.max_pml[0], R.max_pml[1]);
+                    sa.append(num, (size_t)nc);
+                    if (present) ++n_al;
                 }
                 d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
             } else if (a.locate) {          // one line per pattern and strand: name, strand, count, bytes matched, the occurrences kept
@@ -1287,7 +1339,7 @@ int main(int argc, char** argv) {
     close_out(out2);
     delete zrd;
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    info(std::string(a.extend ? "Number of extended reads: " : a.pseudo_ms ? "Number of reads with a pseudo-matching length >= -l: " : (a.locate || a.seq_count || a.loci || a.approx) ? "Number of patterns that occur: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
+    info(std::string(a.extend ? "Number of extended reads: " : a.pseudo_ms ? "Number of reads with a pseudo-matching length >= -l: " : a.screen ? "Number of reads called present: " : (a.locate || a.seq_count || a.loci || a.approx) ? "Number of patterns that occur: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
     info("Elapsed time (s): " + std::to_string(el));
     info("Reads per second: " + std::to_string(processed / (el > 0 ? el : 1)));
     info("Stage busy seconds: reader (parse) " + std::to_string(t_reader) + ", library calls summed over " + std::to_string(ctx.size()) + " workers " + std::to_string(t_align) +
