@@ -342,25 +342,44 @@ MONI_HD void ms_step(const moni_consts_t& K, const lds_tables_t& L, const moni_r
 }
 
 // One lane runs NCH tasks (task0 .. task0+NCH-1; with NCH = 2 the two strands of one read).
+// The pointer stores of a filtered run (live != null): the list mostly holds one strand of a read, so the lanes of a wave hold every other task of
+// a workspace block and their stores at a step fill half of every line they touch.  A task whose sister strand (task ^ 1) is not in the list writes
+// its sample over both tasks' words as one aligned 16-byte store: the wave then writes whole lines, which the memory system takes at a higher rate
+// than half-written ones (profiles/ms_stage).  The sister is a task the filter has skipped: nothing reads its pointers (its MEM counts are zero; a run
+// without the filter writes every task's own).  Two strands that are both in the list store 8 bytes each, side by side.
+// -DMONI_MS_NOSTORE (profiles/ms_stage; never in the product build): the walk without its pointer stores - the samples are folded into one word that
+// is stored once per task, at step 0's place, so that the walk stays alive: the floor the stores are measured against
 template <int NCH>
 MONI_HD void ms_task(const moni_consts_t& K, const lds_tables_t& L, const moni_row_t* __restrict__ rows,
                      const moni_frow_t* __restrict__ frows, const uint32_t* __restrict__ cr, const moni_rec_t* __restrict__ recs,
                      const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t n_tasks, uint64_t task0,
                      uint64_t* __restrict__ ptr_out, unsigned long long& n_steps, unsigned long long& n_jumps,
-                     const uint64_t* __restrict__ live = nullptr) {      // live: slot g works on task live[g] (n_tasks then counts the slots); null: the identity
+                     const uint64_t* __restrict__ live = nullptr) {      // live: slot g works on task live[g], in task order (n_tasks then counts the slots); null: the identity
     ms_state_t S[NCH];
     uint64_t pb[NCH], qb[NCH];
+    bool lone[NCH];                                          // in the list without its sister strand
+#ifdef MONI_MS_NOSTORE
+    uint64_t fold[NCH];
+#endif
     uint32_t m_max = 0;
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
         const uint64_t slot = task0 + k;
         S[k].m = 0;
         pb[k] = qb[k] = 0;
-        if (slot < n_tasks) { const uint64_t task = live ? live[slot] : slot; const uint64_t read = task >> 1; S[k].m = (uint32_t)(offs[read + 1] - offs[read]); pb[k] = ws_pat_base(blk, task); qb[k] = ws_ptr_base(blk, task); }
+        lone[k] = false;
+        if (slot < n_tasks) {
+            const uint64_t task = live ? live[slot] : slot; const uint64_t read = task >> 1;
+            S[k].m = (uint32_t)(offs[read + 1] - offs[read]); pb[k] = ws_pat_base(blk, task); qb[k] = ws_ptr_base(blk, task);
+            if (live) lone[k] = (task & 1u) ? !(slot > 0 && live[slot - 1] == task - 1) : !(slot + 1 < n_tasks && live[slot + 1] == task + 1);
+        }
         m_max = S[k].m > m_max ? S[k].m : m_max;
         S[k].run = (uint32_t)K.r - 1; S[k].pos = K.n - 1; S[k].abs = true; S[k].off = 0;     // start with the empty string
         S[k].sample = K.last_run_sample; S[k].word = 0;
         n_steps += S[k].m;
+#ifdef MONI_MS_NOSTORE
+        fold[k] = 0;
+#endif
     }
     for (uint32_t s = 0; s < m_max; ++s) {
 #pragma unroll
@@ -379,7 +398,15 @@ MONI_HD void ms_task(const moni_consts_t& K, const lds_tables_t& L, const moni_r
             } else {
                 ms_step(K, L, rows, frows, cr, recs, c, S[k], n_jumps);
             }
-            ptr_out[qb[k] + (uint64_t)s * 64u] = S[k].sample;
+#ifdef MONI_MS_NOSTORE
+            fold[k] ^= S[k].sample + s;
+            if (s + 1u == S[k].m) ptr_out[qb[k]] = fold[k];
+#else
+            if (lone[k]) {                                   // (a block's first word is a multiple of 64 words: the pair is 16-byte aligned)
+                moni_u64x2 two; two.x = two.y = S[k].sample;
+                *reinterpret_cast<moni_u64x2*>(ptr_out + (qb[k] & ~1ull) + (uint64_t)s * 64u) = two;
+            } else ptr_out[qb[k] + (uint64_t)s * 64u] = S[k].sample;
+#endif
         }
     }
 }
@@ -628,7 +655,13 @@ struct walk_t {
     uint64_t* out;                  // destination for kept occurrences or nullptr
     uint64_t out_cap;
     unsigned long long phi_steps;
+    uint64_t* stage = nullptr;      // OCC_STAGE_N words that only this lane touches (word j at stage[j * stage_stride]; occ_kernel: LDS), or nullptr
+    uint32_t stage_stride = 0;
 };
+// With a stage the kept occurrences of a walk go to `out` OCC_STAGE_N at a time (walk_push) and the rest behind the walk (walk_flush): the lanes of a
+// wave write to lists 128 bytes apart, so every store is a request per lane, and eight of them issued back to back to one 64-byte line cost the memory
+// system less than eight with a phi step between them (profiles/ms_stage).  The same words reach the same places of the list.
+#define OCC_STAGE_N 8u
 
 MONI_HD uint32_t seq_of(const uint64_t* __restrict__ seq_starts, uint32_t n_seq, uint64_t pos) {
     // rank1(pos + 1) - 1  (seqidx.hpp:136-139): number of onsets <= pos, minus one
@@ -648,10 +681,31 @@ MONI_HD void walk_push(walk_t& W, const occ_args_t& A, const moni_consts_t& K, u
     }
     W.total++;
     if (keep) {
-        if (W.out && W.kept < W.out_cap) W.out[W.kept] = pos;
+#ifndef MONI_OCC_NOSTORE      // (profiles/ms_stage; never in the product build: the walk without its per-occurrence stores)
+        if (W.out && W.kept < W.out_cap) {
+            if (W.stage) {
+                const uint32_t j = (uint32_t)W.kept & (OCC_STAGE_N - 1u);
+                W.stage[(uint64_t)j * W.stage_stride] = pos;
+                if (j == OCC_STAGE_N - 1u) {
+#pragma unroll
+                    for (uint32_t i = 0; i < OCC_STAGE_N; ++i) W.out[W.kept - j + i] = W.stage[(uint64_t)i * W.stage_stride];
+                }
+            } else W.out[W.kept] = pos;
+        }
+#endif
         W.kept++;
         W.last_kept = pos;
     } else W.filtered++;
+}
+
+// the staged occurrences of a finished walk that walk_push has not written: those behind the last full group, below out_cap
+MONI_HD void walk_flush(const walk_t& W) {
+#ifndef MONI_OCC_NOSTORE
+    if (!W.stage || !W.out) return;
+    const uint64_t n = W.kept < W.out_cap ? W.kept : W.out_cap;
+    const uint32_t rem = (uint32_t)n & (OCC_STAGE_N - 1u);
+    for (uint32_t i = 0; i < rem; ++i) W.out[n - rem + i] = W.stage[(uint64_t)i * W.stage_stride];
+#endif
 }
 
 // find_MEM_above / find_MEM_below (seed_finder.hpp:169-239 with the guards of 377-393)
@@ -704,6 +758,7 @@ MONI_HD void run_seed(const occ_args_t& A, const moni_consts_t& K, uint64_t firs
         walk_seed(W, A, K, first_pos, above_from, below_from, len, upper, lower);
         W.phi_steps = ps;                                  // count the reference's walk once
     }
+    walk_flush(W);
 }
 
 // occ_task<FILL>: one lane per final MEM slot.  A full MEM's lane also walks its left half (which starts
@@ -714,13 +769,15 @@ MONI_HD void run_seed(const occ_args_t& A, const moni_consts_t& K, uint64_t firs
 //                 second pass over a compact array.  The product leaves the lists in place (seed_kernels.hip: occ_kernel takes
 //                 `kept` from the count pass and places them) and walks only the long ones again (occ_long_task).
 template <bool FILL>
-MONI_HD void occ_task(const moni_consts_t& K, const occ_args_t& A, uint64_t g, unsigned long long& phi_steps, occ_kept_t* kept = nullptr) {
+MONI_HD void occ_task(const moni_consts_t& K, const occ_args_t& A, uint64_t g, unsigned long long& phi_steps, occ_kept_t* kept = nullptr,
+                      uint64_t* stage = nullptr, uint32_t stage_stride = 0) {      // the count pass's stage (walk_t), used by one walk after the other; null: a store per occurrence
     const uint32_t ax = A.aux[g];
     if (ax == 0xFFFFFFFEu) return;                         // left halves ride with their parent
     const moni_mem_t M = A.mems[g];
     walk_t W; W.phi_steps = 0;
     uint64_t upper = 0, lower = 0;
     if (!FILL) {
+        W.stage = stage; W.stage_stride = stage_stride;
         run_seed(A, K, M.pos, M.pos, M.pos, M.len, A.tmp + g * A.tmp_cap, A.tmp_cap, W, upper, lower);
         A.mems[g].total_occ = (uint32_t)W.total; A.mems[g].num_filtered = (uint32_t)W.filtered; A.mems[g].occ_cnt = (uint32_t)W.kept;
         if (kept) { kept->slot[0] = g; kept->kept[0] = (uint32_t)W.kept; kept->n = 1; }
@@ -735,6 +792,7 @@ MONI_HD void occ_task(const moni_consts_t& K, const occ_args_t& A, uint64_t g, u
         walk_t WB; WB.phi_steps = 0;
         uint64_t u2, l2;
         if (!FILL) {
+            WB.stage = stage; WB.stage_stride = stage_stride;
             run_seed(A, K, upper, upper, lower, Bm.len, A.tmp + hb * A.tmp_cap, A.tmp_cap, WB, u2, l2);
             A.mems[hb].pos = upper;
             A.mems[hb].total_occ = (uint32_t)WB.total; A.mems[hb].num_filtered = (uint32_t)WB.filtered; A.mems[hb].occ_cnt = (uint32_t)WB.kept;

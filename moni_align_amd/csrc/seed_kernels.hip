@@ -17,6 +17,9 @@
 #ifndef MS_CHAINS
 #define MS_CHAINS 2          // independent tasks interleaved per lane in ms_lf_kernel (both strands of one read)
 #endif
+#ifndef OCC_STAGE
+#define OCC_STAGE 1          // 0 (profiles/ms_stage): occ_kernel with a store per kept occurrence
+#endif
 
 __device__ __forceinline__ void load_tables(lds_tables_t& L, const moni_tables_t* __restrict__ T, const moni_consts_t& K) {
     if (threadIdx.x < MONI_MAX_SIGMA) {
@@ -190,11 +193,18 @@ occ_kernel(const moni_consts_t K, occ_args_t A) {
     const uint64_t g = (uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
     unsigned long long phi_steps = 0;
     occ_kept_t kp; kp.n = 0;
+#if OCC_STAGE
+    __shared__ uint64_t ST[OCC_STAGE_N][MS_BLOCK];           // [entry of the group][lane]
+    if (g < A.n_mems) occ_task<false>(K, A, g, phi_steps, &kp, &ST[0][threadIdx.x], MS_BLOCK);
+#else
     if (g < A.n_mems) occ_task<false>(K, A, g, phi_steps, &kp);
+#endif
     wave_add(phi_steps, &A.counters[2]);
     unsigned long long want = 0, kept = 0;          // overflow entries this lane's long lists need; occurrences its seeds keep
     uint32_t n_long = 0;
-    for (uint32_t i = 0; i < kp.n; ++i) {
+#pragma unroll                                       // (both entries by constant index: kp stays in registers)
+    for (uint32_t i = 0; i < 2; ++i) {
+        if (i >= kp.n) break;
         kept += kp.kept[i];
         if (kp.kept[i] > A.tmp_cap) { want += kp.kept[i]; ++n_long; }
         else A.mems[kp.slot[i]].occ_off = kp.slot[i] * A.tmp_cap;
@@ -211,8 +221,9 @@ occ_kernel(const moni_consts_t K, occ_args_t A) {
     if (lane == 63) { base_w = atomicAdd(&A.small->ovf, w_incl); base_n = atomicAdd(&A.small->n_long, n_incl); }
     base_w = __shfl(base_w, 63); base_n = __shfl(base_n, 63);
     unsigned long long at = base_w + (w_incl - want); uint32_t li = base_n + (n_incl - n_long);
-    for (uint32_t i = 0; i < kp.n; ++i)
-        if (kp.kept[i] > A.tmp_cap) {
+#pragma unroll
+    for (uint32_t i = 0; i < 2; ++i)
+        if (i < kp.n && kp.kept[i] > A.tmp_cap) {
             A.mems[kp.slot[i]].occ_off = A.n_mems * A.tmp_cap + at;
             A.long_list[li++] = kp.slot[i];               // every slot is appended at most once: the list holds n_mems entries
             at += kp.kept[i];
