@@ -134,6 +134,8 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
     DBuf<uint64_t> pf_flag, pf_pos, pf_live; DBuf<unsigned long long> pf_stats;      // strand prefilter: per task kept or not, the scan, the live tasks in order; skipped tasks and lookups
     int seed_prefilter = 1;                    // moni_seed_prefilter: 0 off, 1 in the align and paired paths, 2 in moni_seed_run too
     bool seed_fuse = true;                     // the filtered stage runs pack_filter_kernel (MONI_SEED_FUSE=0: pack_kernel + strand_filter_kernel)
+    DBuf<uint64_t> evl; DBuf<uint32_t> evl_cnt;  // the seeding stage's walk as event lists (seed_core.h: ms_task_events) and their lengths per task, in place of ptr
+    bool ms_events = true;                     // seed_all takes the event lists (MONI_MS_EVENTS=0: the dense pointers, as every other caller of ms_launch does)
     bool pf_active = false;                    // the last ms_launch filtered: pf_live / pf_pos[n_tasks] are the live list and its length
     uint64_t pf_tasks = 0;                     // tasks of the last seeding run
     DBuf<moni_u64x2> mem_slots;
@@ -542,6 +544,7 @@ int moni_ctx_create(moni_index_t* I, moni_ctx_t** out) {
     if (const char* v = getenv("MONI_MS_VARIANT")) c->ms_variant = atoi(v);
     if (const char* v = getenv("MONI_EXTZ_LDS")) c->extz_lds = atoi(v);
     if (const char* v = getenv("MONI_SEED_FUSE")) c->seed_fuse = atoi(v) != 0;
+    if (const char* v = getenv("MONI_MS_EVENTS")) c->ms_events = atoi(v) != 0;
     if (const char* v = getenv("MONI_SEED_PREFILTER")) { const int x = atoi(v); if (x >= 0 && x <= 2) c->seed_prefilter = x; }
     bool ok = hipStreamCreate(&c->stream.h) == hipSuccess;
     for (int i = 0; ok && i < EV_N; ++i) ok = hipEventCreate(&c->ev[i].h) == hipSuccess;
@@ -622,13 +625,20 @@ int moni_reads_swap(moni_ctx_t* c, uint32_t slot) {
 // tabs: the byte tables pack_kernel derives strand 1 with (default: the index's own, kpbseq.h:120-137; extend mode brings its complement)
 // filter_min_len > 0 (seed_all alone; it has made cnt_m / cnt_s): the strand prefilter runs behind pack_kernel, and the walk takes the live tasks only -
 // the pointers of a skipped task are not written, nor (with pack_filter_kernel in place of the two kernels) its byte words.  Every other caller gets all of them.
-static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr, uint32_t filter_min_len = 0) {
+// events (seed_all alone): the walk writes its event lists (c->evl, c->evl_cnt) and no dense pointers; c->ptr is then neither needed nor allocated.
+// MONI_MS_EV_STAGE=0 (profiles/ms_events; never in the product build): a store per event where the default stages eight in LDS
+#ifndef MONI_MS_EV_STAGE
+#define MONI_MS_EV_STAGE 1
+#endif
+static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr, uint32_t filter_min_len = 0, bool events = false) {
     moni_index* I = c->idx;
     if (!tabs) tabs = I->d_tables.p;
     const uint64_t n_tasks = 2 * c->n_reads;
     int rc;
     if (c->h_blk.empty()) return MONI_EINVAL;
-    if ((rc = c->ptr.ensure(c->h_blk.back().x + 1)) || (rc = c->pat.ensure(c->h_blk.back().y + 1)) || (rc = c->pflag.ensure(n_tasks + 8))) return rc;
+    if ((rc = c->pat.ensure(c->h_blk.back().y + 1)) || (rc = c->pflag.ensure(n_tasks + 8))) return rc;
+    if (events) { if ((rc = c->evl.ensure(ws_ev_words(c->h_blk.back().x, c->h_blk.size() - 1) + 8)) || (rc = c->evl_cnt.ensure(n_tasks + 2))) return rc; }
+    else if ((rc = c->ptr.ensure(c->h_blk.back().x + 1))) return rc;
     const unsigned grid = (unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK);
     // the filtered stage packs and filters in one kernel (pack_filter_kernel: no byte words for a skipped task) where the tables are the index's own and
     // their complement is the one its arithmetic assumes; MONI_SEED_FUSE=0 keeps the two kernels
@@ -655,7 +665,20 @@ static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr, uint32_t 
         live = c->pf_live.p; n_live = c->pf_pos.p + n_tasks;
         c->pf_active = true;
     }
-    if (n_tasks) {
+    if (n_tasks && events) {          // one task per lane stages its events; the interleaved variants store each
+#define MS_LAUNCH(NCH, MINW, STAGED) do { const uint64_t nl = (n_tasks + (NCH) - 1) / (NCH); \
+        hipLaunchKernelGGL((ms_lf_events_kernel<NCH, MINW, STAGED>), dim3((unsigned)((nl + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, \
+                           I->K, tabs, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p, n_tasks, c->evl.p, c->evl_cnt.p, c->d_counters.p, live, n_live); } while (0)
+        switch (c->ms_variant) {
+            case 1: MS_LAUNCH(1, 8, MONI_MS_EV_STAGE != 0); break;
+            case 2: MS_LAUNCH(2, 8, false); break;
+            case 3: MS_LAUNCH(2, 6, false); break;
+            case 4: MS_LAUNCH(1, 6, MONI_MS_EV_STAGE != 0); break;
+            case 5: MS_LAUNCH(4, 4, false); break;
+            default: MS_LAUNCH(1, 6, MONI_MS_EV_STAGE != 0); break;
+        }
+#undef MS_LAUNCH
+    } else if (n_tasks) {
 #define MS_LAUNCH(NCH, MINW) do { const uint64_t nl = (n_tasks + (NCH) - 1) / (NCH); \
         hipLaunchKernelGGL((ms_lf_kernel<NCH, MINW>), dim3((unsigned)((nl + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, \
                            I->K, tabs, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p, n_tasks, c->ptr.p, c->d_counters.p, live, n_live); } while (0)
@@ -757,16 +780,23 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm, bool align_path)
     // the strand prefilter: where the mode asks for it, the index's table is sparse enough and min_len leaves a window of k-mers (prefilter_core.h)
     const bool filter = (c->seed_prefilter == 2 || (c->seed_prefilter == 1 && align_path)) && I->pf_on && prm->min_len >= I->pf_k;
     rec(c, EV_ALL0);
-    if ((rc = ms_launch(c, nullptr, filter ? prm->min_len : 0))) return rc;                              // (allocates pat / ptr)
+    // the walk's assignments as event lists, which is all mem_kernel asks of the pointers; a read too long for the event word's step field: dense pointers
+    const bool events = c->ms_events && c->max_len < MONI_EV_MAX_LEN;
+    if ((rc = ms_launch(c, nullptr, filter ? prm->min_len : 0, events))) return rc;                      // (allocates pat and ptr or ev)
     const uint64_t* live = c->pf_active ? c->pf_live.p : nullptr; const uint64_t* n_live = c->pf_active ? c->pf_pos.p + n_tasks : nullptr;
-    const uint64_t* pat = c->pat.p; const uint64_t* ptr = c->ptr.p;
+    const uint64_t* pat = c->pat.p; const uint64_t* ptr = events ? nullptr : c->ptr.p;
+    const uint64_t* ev = c->evl.p; const uint32_t* ev_cnt = c->evl_cnt.p;
     const unsigned grid_t = (unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK);
     const uint32_t split_on = prm->report_mems ? 0u : 1u;
     // the 2-bit comparison holds a lane's pattern in LDS: 5 words (160 bases) or 8 (256); reads beyond that compare bytes (MONI_MEM_BYTES=1: all do)
     static const bool mem_bytes = getenv("MONI_MEM_BYTES") != nullptr;
     const uint64_t* text2 = mem_bytes ? nullptr : I->d_text2.p;
 #define MEM_LAUNCH(EMIT, RMO, MEMS, AUX, LIVE, NLIVE) do { \
-        if (c->max_len <= 160) hipLaunchKernelGGL((mem_kernel<EMIT, 5>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, text2, I->d_exc.p, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
+        if (events && c->max_len <= 160) hipLaunchKernelGGL((mem_events_kernel<EMIT, 5>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, text2, I->d_exc.p, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
+                                                  n_tasks, ev, ev_cnt, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters.p, LIVE, NLIVE); \
+        else if (events) hipLaunchKernelGGL((mem_events_kernel<EMIT, 8>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, text2, I->d_exc.p, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
+                                n_tasks, ev, ev_cnt, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters.p, LIVE, NLIVE); \
+        else if (c->max_len <= 160) hipLaunchKernelGGL((mem_kernel<EMIT, 5>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, text2, I->d_exc.p, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
                                                   n_tasks, ptr, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters.p, LIVE, NLIVE); \
         else hipLaunchKernelGGL((mem_kernel<EMIT, 8>), dim3(grid_t), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_text.p, text2, I->d_exc.p, I->exc_sh, I->exc_words, pat, offs, c->blk.p, \
                                 n_tasks, ptr, prm->min_len, split_on, cnt_m, cnt_s, RMO, MEMS, AUX, slots, c->d_counters.p, LIVE, NLIVE); } while (0)

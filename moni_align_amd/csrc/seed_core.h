@@ -412,6 +412,159 @@ MONI_HD void ms_task(const moni_consts_t& K, const lds_tables_t& L, const moni_r
 }
 
 // ------------------------------------------------------------------------------------------------
+// The walk's jumps as an event list (the seeding stage; every other reader of MS pointers takes the dense workspace above).
+// ms_step changes the sample in two ways only: a match decrements it, a threshold jump or an absent byte assigns it.  mem_task asks of a pointer
+// whether it is its neighbour's plus one, so the decremented values say nothing there: the list holds the assignments alone, and the reader
+// rebuilds every step's word from the last assignment at or before it.
+//   event word  the assigned sample in the low 40 bits (every assigned value fits: image.hpp refuses an index whose thr / ssa / esa / lfpos
+//               exceed 40 bits, the fast row's halves are 32 + 8 bits, an absent byte assigns 0, last_run_sample < n < 2^40), and in the upper
+//               24 bits the step of the assignment PLUS ONE.  Field 0 is the start state, last_run_sample assigned in front of step 0: a walk
+//               whose step 0 is a match records that, one whose step 0 assigns records field 1 - either way the first event covers step 0 and
+//               no list is empty.  (The sample after a matched step 0 is last_run_sample - 1, which wraps when last_run_sample is 0 and would
+//               not fit the 40 bits; the value in front of it always does.)
+//   word of step s = sample - (s + 1 - field) in 64-bit arithmetic, from the last event with field <= s + 1: the wrap of 0 - 1 behind an absent
+//               byte comes out as the dense word does
+//   list        of task t at ev[ws_ev_base(blk, t)], 64-byte aligned, room for its block's depth rounded up to 8 events (a walk can jump at
+//               every step), events in step order, their number in ev_cnt[t] once the walk has ended (a task of length 0 has none and no count)
+// A block of 64 tasks takes 64 * depth + 512 words: the dense block and the rounding, so that the block table serves both layouts.
+// Reads of 2^24 bases or more do not fit the field: such a batch takes the dense form (moni_hip.hip: seed_all).
+// ------------------------------------------------------------------------------------------------
+#define MONI_EV_SHIFT 40
+#define MONI_EV_MAX_LEN (1ull << 24)
+#define MONI_EV_STAGE_N 8u
+MONI_HD uint64_t ws_ev_cap(const moni_u64x2* __restrict__ blk, uint64_t task) { return (ws_block_len(blk, task) + 7u) & ~7ull; }
+MONI_HD uint64_t ws_ev_base(const moni_u64x2* __restrict__ blk, uint64_t task) { return blk[task >> 6].x + 512u * (task >> 6) + (task & 63u) * ws_ev_cap(blk, task); }
+MONI_HD uint64_t ws_ev_words(uint64_t ptr_words, uint64_t n_blocks) { return ptr_words + 512u * n_blocks; }
+
+// ms_task with the event list in place of the pointer stores: the same steps, the same counts.  Whether a step assigned is read off the jump counter
+// (ms_step bumps it on exactly the paths that assign) and not off the sample, because a jump can assign the old value minus one.
+// STAGED (one task per lane): a lane collects eight events in `stage` (word j at stage[j * stage_stride]; ms_lf_events_kernel: LDS) and writes them
+// as one 64-byte line in back-to-back stores, the rest behind the walk - the form of walk_push / walk_flush.  Otherwise a store per event.
+template <int NCH, bool STAGED>
+MONI_HD void ms_task_events(const moni_consts_t& K, const lds_tables_t& L, const moni_row_t* __restrict__ rows,
+                            const moni_frow_t* __restrict__ frows, const uint32_t* __restrict__ cr, const moni_rec_t* __restrict__ recs,
+                            const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t n_tasks, uint64_t task0,
+                            uint64_t* __restrict__ ev, uint32_t* __restrict__ ev_cnt, unsigned long long& n_steps, unsigned long long& n_jumps,
+                            const uint64_t* __restrict__ live = nullptr, uint64_t* stage = nullptr, uint32_t stage_stride = 0) {
+    static_assert(!STAGED || NCH == 1, "the stage holds one task's events");
+    ms_state_t S[NCH];
+    uint64_t pb[NCH], eb[NCH], tk[NCH];
+    uint32_t ne[NCH];
+    uint32_t m_max = 0;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        const uint64_t slot = task0 + k;
+        S[k].m = 0;
+        pb[k] = eb[k] = tk[k] = 0; ne[k] = 0;
+        if (slot < n_tasks) {
+            const uint64_t task = live ? live[slot] : slot; const uint64_t read = task >> 1;
+            S[k].m = (uint32_t)(offs[read + 1] - offs[read]); pb[k] = ws_pat_base(blk, task); eb[k] = ws_ev_base(blk, task); tk[k] = task;
+        }
+        m_max = S[k].m > m_max ? S[k].m : m_max;
+        S[k].run = (uint32_t)K.r - 1; S[k].pos = K.n - 1; S[k].abs = true; S[k].off = 0;     // start with the empty string
+        S[k].sample = K.last_run_sample; S[k].word = 0;
+        n_steps += S[k].m;
+    }
+    for (uint32_t s = 0; s < m_max; ++s) {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (s >= S[k].m) continue;
+            if ((s & 7u) == 0) S[k].word = pat[pb[k] + (uint64_t)(s >> 3) * 64u];
+            const uint32_t raw = (uint32_t)S[k].word & 0xFFu;
+            S[k].word >>= 8;
+            const uint32_t c = L.code[raw];
+            bool assigned = true;
+            if (c == MONI_CODE_ABSENT) {                      // n_c == 0   (moni.hpp:583-588)
+                S[k].sample = 0;
+                S[k].pos = L.abs_pos[raw];
+                S[k].run = L.abs_run[raw];
+                S[k].abs = true;
+            } else {
+                const uint32_t j0 = (uint32_t)n_jumps;
+                ms_step(K, L, rows, frows, cr, recs, c, S[k], n_jumps);
+                assigned = ((((uint32_t)n_jumps) ^ j0) & 0x0FFFFFFFu) != 0;          // (bits 28.. are MONI_MS_ATTR's)
+            }
+            if (assigned || s == 0) {
+                const uint64_t w = assigned ? (S[k].sample | ((uint64_t)(s + 1u) << MONI_EV_SHIFT)) : K.last_run_sample;
+                if (STAGED) {
+                    const uint32_t j = ne[k] & (MONI_EV_STAGE_N - 1u);
+                    stage[(uint64_t)j * stage_stride] = w;
+                    if (j == MONI_EV_STAGE_N - 1u) {          // (a list starts on a 64-byte boundary: the eight words are one line)
+#pragma unroll
+                        for (uint32_t i = 0; i < MONI_EV_STAGE_N; i += 2) {
+                            moni_u64x2 two; two.x = stage[(uint64_t)i * stage_stride]; two.y = stage[(uint64_t)(i + 1u) * stage_stride];
+                            *reinterpret_cast<moni_u64x2*>(ev + eb[k] + (ne[k] - j) + i) = two;
+                        }
+                    }
+                } else ev[eb[k] + ne[k]] = w;
+                ++ne[k];
+            }
+            if (s + 1u == S[k].m) {                           // the walk has ended: the staged events behind the last full line, and the count
+                if (STAGED) {
+                    const uint32_t rem = ne[k] & (MONI_EV_STAGE_N - 1u);
+                    for (uint32_t i = 0; i < rem; ++i) ev[eb[k] + (ne[k] - rem) + i] = stage[(uint64_t)i * stage_stride];
+                }
+                ev_cnt[tk[k]] = ne[k];
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Where mem_task takes the pointer of a step from.  take(s) is called once per read offset, with s = m - 1 - i falling by one (or, behind
+// silent(), by more); silent(s) > 0 says that this many offsets from this one on hold no assignment in the step above them (see mem_task).
+// ------------------------------------------------------------------------------------------------
+// the dense workspace: the word of step s - 1 is asked for while step s is worked on
+struct mem_src_dense_t {
+    static constexpr bool skips = false;
+    const uint64_t* p = nullptr; uint64_t nxt = 0;
+    MONI_HD void open(const uint64_t* __restrict__ ptr, const moni_u64x2* __restrict__ blk, uint64_t task, uint32_t m) {
+        p = ptr + ws_ptr_base(blk, task);
+        nxt = m ? p[(uint64_t)(m - 1) * 64u] : 0;
+    }
+    MONI_HD uint64_t take(uint32_t s) { const uint64_t pos = nxt; if (s) nxt = p[(uint64_t)(s - 1u) * 64u]; return pos; }
+    MONI_HD uint32_t silent(uint32_t) const { return 0; }
+};
+// the event list, walked from its last event towards the first: a lane reads its own contiguous list 16 bytes at a time and asks for the pair in front
+// while it works through the current one
+template <bool SKIP>
+struct mem_src_events_t {
+    static constexpr bool skips = SKIP;
+    const uint64_t* ev = nullptr; const uint32_t* ev_cnt = nullptr;      // the buffers (set by the caller)
+    const uint64_t* lst = nullptr;
+    uint64_t p0 = 0, p1 = 0, a0 = 0, a1 = 0;      // the pair that holds the current event and the pair in front of it (scalars: the object stays in registers)
+    uint64_t v = 0;                  // the current event: its sample,
+    uint32_t f = 0, k = 0;           // its field (step + 1) and its index in the list
+    bool moved = false;              // the last take() went to an earlier event: the step above it holds an assignment
+    MONI_HD void set(uint64_t w) { v = w & MONI_POS_MASK; f = (uint32_t)(w >> MONI_EV_SHIFT); }
+    MONI_HD void open(const uint64_t* __restrict__, const moni_u64x2* __restrict__ blk, uint64_t task, uint32_t m) {
+        if (!m) return;
+        lst = ev + ws_ev_base(blk, task);
+        k = ev_cnt[task] - 1u;                                       // (no list of a task with a base is empty)
+        const uint32_t a = k & ~1u;
+        const moni_u64x2 q = *reinterpret_cast<const moni_u64x2*>(lst + a);        // (an odd count reads one word behind the list, inside its room: not used)
+        p0 = q.x; p1 = q.y; a0 = q.x; a1 = q.y;
+        if (a >= 2) { const moni_u64x2 r = *reinterpret_cast<const moni_u64x2*>(lst + a - 2); a0 = r.x; a1 = r.y; }
+        set((k & 1u) ? p1 : p0);
+    }
+    MONI_HD uint64_t take(uint32_t s) {
+        moved = false;
+        if (s + 1u < f && k) {                                       // step s lies in front of the current assignment (the first event has field 0 or 1: k > 0 here)
+            if (!(k & 1u)) {
+                p0 = a0; p1 = a1;
+                if (k >= 4) { const moni_u64x2 r = *reinterpret_cast<const moni_u64x2*>(lst + (k - 4u)); a0 = r.x; a1 = r.y; }
+            }
+            --k;
+            set((k & 1u) ? p1 : p0);
+            moved = true;
+        }
+        return v - (uint64_t)(s + 1u - f);
+    }
+    // steps s, s - 1, .. down to the current event's own step (or step 0) are all decrements of one another
+    MONI_HD uint32_t silent(uint32_t s) const { return moved ? 0u : s + 1u - (f ? f - 1u : 0u); }
+};
+
+// ------------------------------------------------------------------------------------------------
 // mem_task<EMIT>: the forward text-comparison loop of find_mems.
 //   EMIT = false: cnt_m[task] = number of MEMs, cnt_s[task] = number of MEMs that will be split in halves
 //   EMIT = true : writes the MEM (and the fixed fields of its two halves) to its final slot.
@@ -429,12 +582,13 @@ struct mem_fast_t {
     uint32_t pw_stride, pw_words;     // tasks of up to 32 * pw_words bases take the 2-bit comparison
 };
 
-template <bool EMIT>
+// src: where the pointers come from (above); the default is the dense workspace `ptr`, which the event source does not read
+template <bool EMIT, class SRC = mem_src_dense_t>
 MONI_HD void mem_task(const moni_consts_t& K, const mem_fast_t& F, const uint8_t* __restrict__ text,
                       const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t task,
                       const uint64_t* __restrict__ ptr, uint32_t min_len, uint32_t split_on, uint32_t* __restrict__ cnt_m,
                       uint32_t* __restrict__ cnt_s, const uint64_t* __restrict__ read_mem_off, moni_mem_t* __restrict__ mems,
-                      uint32_t* __restrict__ aux, moni_u64x2* __restrict__ slots, unsigned long long& n_cmp) {
+                      uint32_t* __restrict__ aux, moni_u64x2* __restrict__ slots, unsigned long long& n_cmp, SRC src = SRC()) {
     const uint64_t read = task >> 1;
     const uint32_t strand = (uint32_t)task & 1u;
     const uint64_t off = offs[read];
@@ -490,7 +644,7 @@ MONI_HD void mem_task(const moni_consts_t& K, const mem_fast_t& F, const uint8_t
     }
     pat_cache_t pc; pc.w = 0xFFFFFFFFu; pc.word = 0;
     text_cache_t tc; tc.w = ~0ull; tc.word = 0;
-    const uint64_t pb = ws_pat_base(blk, task), qb = ws_ptr_base(blk, task);
+    const uint64_t pb = ws_pat_base(blk, task);
     // the pattern's code words into the lane's LDS column; has_inv: the pattern holds a byte that is not A / C / G / T (its mask words are then read
     // where they lie in the workspace)
     const bool fast = F.text2 != nullptr && m <= 32u * F.pw_words;
@@ -507,12 +661,27 @@ MONI_HD void mem_task(const moni_consts_t& K, const mem_fast_t& F, const uint8_t
     // extensions (with the nest, every offset costs the wavefront its longest extension).
     uint32_t i = 0;
     bool ext = false;
-    uint64_t pos = 0, nxt = m ? ptr[qb + (uint64_t)(m - 1) * 64u] : 0;      // the pointer of offset i + 1 is asked for while offset i is worked on
+    uint64_t pos = 0;
+    src.open(ptr, blk, task, m);                 // (the dense source asks for the pointer of offset i + 1 while offset i is worked on)
     while (i < m) {
         if (!ext) {
-            pos = nxt;
-            if (i + 1 < m) nxt = ptr[qb + (uint64_t)(m - 2 - i) * 64u];
+            pos = src.take(m - 1u - i);
             ext = pos != prev_pos_plus_one;
+            if (SRC::skips && !ext && i) {
+                // A run of silent offsets closed in one move.  An offset is silent when the step above its own holds no assignment: its pointer is then
+                // its neighbour's plus one and nothing is compared.  All the loop does there is pl = l; l = l ? l - 1 : 0; prev = pos + 1, and it can find
+                // no MEM: on entry l is the neighbour's final l minus one (or both are 0), so l >= pl holds only at l == 0, where n_Ns < l fails.
+                // k such offsets in a row leave l and pl k steps further down that ramp, pos k - 1 further on, and n_cmp as it was.
+                const uint64_t k = src.silent(m - 1u - i);
+                if (k) {
+                    pl = l >= k ? l - (k - 1) : 0;
+                    l = l >= k ? l - k : 0;
+                    pos += k - 1;
+                    prev_pos_plus_one = pos + 1;
+                    i += (uint32_t)k;
+                    continue;
+                }
+            }
         }
         if (ext) {
             bool more = false;

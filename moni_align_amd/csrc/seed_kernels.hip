@@ -72,16 +72,41 @@ ms_lf_kernel(const moni_consts_t K, const moni_tables_t* __restrict__ T, const m
     wave_add(n_jumps, &counters[1]);
 }
 
+// The walk of the seeding stage (moni_hip.hip: seed_all): ms_task_events in place of ms_task - the assignments of a walk as a list per task, no dense pointers.
+// STAGED (NCH = 1): eight events per lane wait in LDS, [word][lane], 16 KB beside the 4 KB of tables: 20 416 B per block, eight blocks in the 160 KB of a CU.
+template <int NCH, int MINW, bool STAGED>
+__global__ void __launch_bounds__(MS_BLOCK, MINW)
+ms_lf_events_kernel(const moni_consts_t K, const moni_tables_t* __restrict__ T, const moni_row_t* __restrict__ rows,
+                    const moni_frow_t* __restrict__ frows, const uint32_t* __restrict__ cr, const moni_rec_t* __restrict__ recs,
+                    const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t n_tasks,
+                    uint64_t* __restrict__ ev, uint32_t* __restrict__ ev_cnt, unsigned long long* __restrict__ counters,
+                    const uint64_t* __restrict__ live, const uint64_t* __restrict__ n_live) {      // as ms_lf_kernel's
+    if (live) {
+        n_tasks = *n_live;
+        if ((uint64_t)blockIdx.x * MS_BLOCK * NCH >= n_tasks) return;
+    }
+    __shared__ lds_tables_t L;
+    __shared__ uint64_t ST[STAGED ? MONI_EV_STAGE_N : 1][STAGED ? MS_BLOCK : 1];      // [event of the group][lane]
+    load_tables(L, T, K);
+    const uint64_t task0 = ((uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x) * NCH;
+    unsigned long long n_steps = 0, n_jumps = 0;
+    if (task0 < n_tasks)
+        ms_task_events<NCH, STAGED>(K, L, rows, frows, cr, recs, pat, offs, blk, n_tasks, task0, ev, ev_cnt, n_steps, n_jumps, live,
+                                    STAGED ? &ST[0][threadIdx.x] : nullptr, MS_BLOCK);
+    wave_add(n_steps, &counters[0]);
+    wave_add(n_jumps, &counters[1]);
+}
+
 // W: 64-bit pattern code words per lane in LDS (reads of up to 32 W bases take the 2-bit comparison; longer ones in the same launch compare bytes)
-template <bool EMIT, int W>
-__global__ void __launch_bounds__(MS_BLOCK)
-mem_kernel(const moni_consts_t K, const uint8_t* __restrict__ text, const uint64_t* __restrict__ text2, const uint32_t* __restrict__ exc, uint32_t exc_sh, uint32_t exc_words,
+template <bool EMIT, int W, class SRC>
+__device__ __forceinline__ void
+mem_body(const moni_consts_t& K, const uint8_t* __restrict__ text, const uint64_t* __restrict__ text2, const uint32_t* __restrict__ exc, uint32_t exc_sh, uint32_t exc_words,
            const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t n_tasks,
            const uint64_t* __restrict__ ptr, uint32_t min_len, uint32_t split_on,
            uint32_t* __restrict__ cnt_m, uint32_t* __restrict__ cnt_s,
            const uint64_t* __restrict__ read_mem_off, moni_mem_t* __restrict__ mems, uint32_t* __restrict__ aux,
            moni_u64x2* __restrict__ slots, unsigned long long* __restrict__ counters,
-           const uint64_t* __restrict__ live, const uint64_t* __restrict__ n_live) {      // as ms_lf_kernel's (the count pass; the emit pass takes every task)
+           const uint64_t* __restrict__ live, const uint64_t* __restrict__ n_live, const SRC& src) {
     if (live) {
         n_tasks = *n_live;
         if ((uint64_t)blockIdx.x * MS_BLOCK >= n_tasks) return;
@@ -95,8 +120,39 @@ mem_kernel(const moni_consts_t K, const uint8_t* __restrict__ text, const uint64
     const uint64_t g = (uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
     unsigned long long n_cmp = 0;
     if (g < n_tasks)
-        mem_task<EMIT>(K, F, text, pat, offs, blk, live ? live[g] : g, ptr, min_len, split_on, cnt_m, cnt_s, read_mem_off, mems, aux, slots, n_cmp);
+        mem_task<EMIT>(K, F, text, pat, offs, blk, live ? live[g] : g, ptr, min_len, split_on, cnt_m, cnt_s, read_mem_off, mems, aux, slots, n_cmp, src);
     if (!EMIT) wave_add(n_cmp, &counters[3]);
+}
+template <bool EMIT, int W>
+__global__ void __launch_bounds__(MS_BLOCK)
+mem_kernel(const moni_consts_t K, const uint8_t* __restrict__ text, const uint64_t* __restrict__ text2, const uint32_t* __restrict__ exc, uint32_t exc_sh, uint32_t exc_words,
+           const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t n_tasks,
+           const uint64_t* __restrict__ ptr, uint32_t min_len, uint32_t split_on,
+           uint32_t* __restrict__ cnt_m, uint32_t* __restrict__ cnt_s,
+           const uint64_t* __restrict__ read_mem_off, moni_mem_t* __restrict__ mems, uint32_t* __restrict__ aux,
+           moni_u64x2* __restrict__ slots, unsigned long long* __restrict__ counters,
+           const uint64_t* __restrict__ live, const uint64_t* __restrict__ n_live) {      // as ms_lf_kernel's (the count pass; the emit pass takes every task)
+    mem_body<EMIT, W>(K, text, text2, exc, exc_sh, exc_words, pat, offs, blk, n_tasks, ptr, min_len, split_on, cnt_m, cnt_s, read_mem_off, mems, aux, slots, counters, live, n_live,
+                      mem_src_dense_t());
+}
+// ... with the pointers rebuilt from the event lists of ms_lf_events_kernel (both passes: the emit pass walks a task with more than MONI_MEM_SLOTS MEMs again).
+// MONI_MEM_EV_SKIP=0 (profiles/ms_events; never in the product build): every read offset takes a turn of the loop, as with the dense workspace
+#ifndef MONI_MEM_EV_SKIP
+#define MONI_MEM_EV_SKIP 1
+#endif
+template <bool EMIT, int W>
+__global__ void __launch_bounds__(MS_BLOCK)
+mem_events_kernel(const moni_consts_t K, const uint8_t* __restrict__ text, const uint64_t* __restrict__ text2, const uint32_t* __restrict__ exc, uint32_t exc_sh, uint32_t exc_words,
+                  const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t n_tasks,
+                  const uint64_t* __restrict__ ev, const uint32_t* __restrict__ ev_cnt, uint32_t min_len, uint32_t split_on,
+                  uint32_t* __restrict__ cnt_m, uint32_t* __restrict__ cnt_s,
+                  const uint64_t* __restrict__ read_mem_off, moni_mem_t* __restrict__ mems, uint32_t* __restrict__ aux,
+                  moni_u64x2* __restrict__ slots, unsigned long long* __restrict__ counters,
+                  const uint64_t* __restrict__ live, const uint64_t* __restrict__ n_live) {
+    mem_src_events_t<MONI_MEM_EV_SKIP != 0> src;
+    src.ev = ev; src.ev_cnt = ev_cnt;
+    mem_body<EMIT, W>(K, text, text2, exc, exc_sh, exc_words, pat, offs, blk, n_tasks, nullptr, min_len, split_on, cnt_m, cnt_s, read_mem_off, mems, aux, slots, counters, live, n_live,
+                      src);
 }
 
 // the 2-bit text and the bitmap of its blocks that hold a byte outside A / C / G / T (seed_core.h: text2_word), one thread per word; once per index
