@@ -236,6 +236,7 @@ typedef struct {
     uint64_t dp_cells_cut;                                /* staged DP kernels: cells of the problems after an extension's target rows that cannot hold its result are
                                                              cut (dp_cells counts the problems as the reference poses them: qlen x tlen of every ksw_extz2_sse call) */
     uint64_t dp_slots;                                    /* ... and the cell slots those kernels ran (128 problems x the chunk's longest query x the target rows of its passes) */
+    uint64_t runs_routed;                                 /* reads whose runs of anchors were chained with one lane per run (chain_runs_kernel), not in chain_plan_kernel */
 } moni_align_stats_t;
 
 void moni_align_params_default(moni_align_params_t *p);

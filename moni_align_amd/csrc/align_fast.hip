@@ -66,7 +66,8 @@ static_assert(AF_NBIN + 1 <= (1 << (32 - AF_POS_BITS)), "task_pos");
 #define AF_NEG_INF (-0x40000000)
 
 enum { AF_GAP_NONE = 0, AF_GAP_INS, AF_GAP_DEL0, AF_GAP_TASK, AF_GAP_1X1 };
-enum { AF_ST_UNALIGNED = 0, AF_ST_CAND = 1, AF_ST_FALLBACK = 2, AF_ST_FINAL = 3, AF_ST_CHAINS = 4 /* chain_plan_kernel has left the read's chains for plan_kernel */ };
+enum { AF_ST_UNALIGNED = 0, AF_ST_CAND = 1, AF_ST_FALLBACK = 2, AF_ST_FINAL = 3, AF_ST_CHAINS = 4 /* chain_plan_kernel has left the read's chains for plan_kernel */,
+       AF_ST_RUNS = 5 /* (never in a plan) af_chain has left the read's runs of anchors for chain_runs_kernel */ };
 
 struct af_anchor_t {             // one anchor of a chain to score, and the gap between it and the next one (16 bytes)
     uint64_t occ;
@@ -118,6 +119,18 @@ struct af_plan_lds_t {
 struct af_ctab_t { int32_t score; uint16_t an0; uint8_t cnt, strand; uint64_t left_ref; };      // one chain of a read, in the order of chain.hpp:402's sort: its anchors are an[an0 .. an0 + cnt) of the read's plan
 static_assert(sizeof(af_ctab_t) == 16, "af_ctab_t");
 #define AF_CTAB 48               // chains per read in the table (the small LDS instance's capacity)
+// What the LEVEL-0 instance of chain_plan_kernel leaves for chain_runs_kernel (lane = run): the read's sorted anchors as 8-byte nodes, the runs' boundaries
+// in fixed slots of the read, and a header.  A read takes this route when it has at most AF_RUN_SLOTS runs of at most AF_RUN_LEN anchors each.
+// node: x - xbase[run] | rpos << 32 | len << 42 | idx << 52 | mate << 62.  The first field holds 32 bits because a run's consecutive ends are at most
+// max_dist_x <= 2^28 apart (cc_narrow_ok) and a run has at most AF_RUN_LEN <= 16 anchors; the next three are positions in a read of fewer than AF_MAX_READ bases.
+// Which reads took the route says rflag, a byte per read of the launch that the host clears ahead of every launch and the route sets to the number of runs:
+// a read chained in place writes nothing, and nothing of an earlier launch is ever read.
+#define AF_RUN_LEN 8             // anchors of a run (profiles/chain_runs: 150-base reads at 1 % substitutions have runs of up to 7)
+#define AF_RUN_SLOTS 16          // runs of a read
+#define AF_RUN_CHAINS 48         // kept chains and chain starts of a read: the small instance's capacity, the chain table's AF_CTAB
+#define AF_RUN_NODES 96          // anchors of a read: the small instance's capacity
+struct af_rstage_t { uint64_t node[AF_RUN_NODES]; uint64_t xbase[AF_RUN_SLOTS]; float avg; uint8_t na, n_runs, rs[AF_RUN_SLOTS + 1] /* first anchor of run k; rs[n_runs] = na */, pad; };
+static_assert(sizeof(af_rstage_t) == 920 && AF_MAX_READ <= 1024 && AF_RUN_LEN <= 16 && AF_RUN_NODES <= 127 && AF_RUN_CHAINS <= 255, "af_rstage_t: field widths");
 struct af_res_t { int32_t mqe, mqe_t, score, flags; };      // flags: 1 = a wildcard base in an operand (not computed)
 struct af_chunk_t { uint32_t bin, start, n, qhi; uint64_t dir_off; };
 struct af_tb_t { uint32_t n_ops; uint32_t ops[AF_TB_CIG]; };      // raw backtrack order (end -> start); n_ops = ~0u: did not fit
@@ -144,6 +157,7 @@ struct af_args_t {
     const uint64_t* text2; const uint32_t* exc; uint32_t exc_sh;      // the 2-bit text and its exception bitmap (seed_core.h: mem_fast_t)
     const uint8_t* pflag;                    // per seeding task (2 read + strand): the pattern holds a byte outside A / C / G / T
     af_ctab_t* ctab;                         // AF_CTAB per read of the launch: LEVEL 0's chains, for plan_kernel (nullptr: the LEVEL-0 instance plans by itself)
+    af_rstage_t* rstage; uint8_t* rflag;     // one per read of the launch: LEVEL 0's runs of anchors, for chain_runs_kernel (nullptr: every read is chained in place; MONI_AF_RUNS=0)
     uint32_t* list0; uint32_t* big_list; uint32_t* huge_list; // reads (indices in the launch) of the small / the large / the largest instance of chain_plan_kernel (classify_kernel)
     unsigned long long* txt_cur;             // AF_TXT_SHARDS cursors (one per 64 bytes) of the text pool's shard regions: a device-scope atomic on ONE address
     uint64_t txt_shard_words;                // sustains only ~50 M/s; region s + 1 of the pool (txt_shard_words each) belongs to shard s, region 0 to cursors[15]
@@ -178,6 +192,7 @@ enum { AFC_TASKS = 0, AFC_FALLBACK = 1, AFC_TRACED = 2, AFC_READ_CUR = 3, AFC_DI
        AFC_SLOTS = 48 /* 64 bit: cell slots the DP kernels computed (query positions of the chunk's longest problem x target rows of its passes (or diagonals of its band) x 128 problems) */,
        AFC_CUTCELLS = 50 /* 64 bit: cells of the problems after an extension's target rows are cut (af_build_cand) and a problem is banded (af_tile_band2, af_global_band); AFC_CELLS counts them as the reference poses them */,
        AFC_BANDH = 52 /* + min(W / 4, 13): global problems by the width of the band of diagonals their optimal paths can touch (af_global_band) */,
+       AFC_RUNS = 66 /* reads whose runs of anchors chain_runs_kernel has chained */,
        AFC_BINS = 68 /* + bin */, AFC_WMODE = 172 /* + group (7): dp_wave_kernel computes the group, not dp_lane_kernel */, AF_NCTR = 192 };
 static_assert(AFC_BINS + AF_NBIN + 1 <= AFC_WMODE && AFC_WMODE + 7 <= AF_NCTR && AFC_WHY + 12 <= AFC_RBYTES && AFC_BANDH + 14 <= AFC_BINS && AFC_NCHUNKS + 7 <= AFC_CURSOR && AFC_CURSOR + 7 <= AFC_BIG, "counter layout");
 enum { AF_GRP_LARGE = 0, AF_GRP_SMALL = 1, AF_GRP_BAND = 2, AF_GRP_WILD = 3, AF_GRP_GLOBAL = 4, AF_GRP_GBAND = 5, AF_GRP_GWILD = 6 };
@@ -491,8 +506,11 @@ __device__ __forceinline__ void af_chain_run(WT& L, const ac_params_t& P, uint32
 // GEN: the general instance, with both switches at run time - the serial sorts that MONI_AF_DBG=64 selects (out-of-line calls: a stack, and registers
 // spilled around them) and the 64-bit chaining DP, for parameters that cc_narrow_ok does not admit (G.chain_narrow == 0) and for the cross-check.  Without GEN the instance holds
 // neither: the wave's sorts and the 32-bit DP.  chain_plan_kernel is built both ways and launched by the two conditions; the paired kernels are general.
-template <class WT, class GT = af_grp_t<64>, bool GEN = true>
-__device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t na, float avg_mem_length, const GT g = GT(), const bool sec_on = false) {
+// ROUTE (the small plain LEVEL-0 instance alone, and only with G.rstage): a read of at most AF_RUN_SLOTS runs of at most AF_RUN_LEN anchors each stops behind
+// the runs.  Its sorted anchors, the runs' boundaries and a header go to the staging slot of read r_in, chain_runs_kernel does everything below with one lane
+// per run, and AF_ST_RUNS is returned.  The test is the same for every lane of the wavefront.
+template <class WT, class GT = af_grp_t<64>, bool GEN = true, bool ROUTE = false>
+__device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t na, float avg_mem_length, const GT g = GT(), const bool sec_on = false, const uint32_t r_in = 0) {
     const ac_params_t& P = G.A.P;
     constexpr uint32_t GW = GT::W;
     const int lane = g.lane;
@@ -522,6 +540,23 @@ __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t
     }
     if (lane == 0) L.run_start[n_runs] = (uint16_t)na;
     __syncthreads();
+    if (ROUTE && G.rstage != nullptr && n_runs <= AF_RUN_SLOTS) {
+        const bool lng = (uint32_t)lane < n_runs && (uint32_t)L.run_start[lane + 1] - (uint32_t)L.run_start[lane] > AF_RUN_LEN;
+        if (g.ballot(lng) == 0) {
+            af_rstage_t& R = G.rstage[r_in];
+            for (uint32_t i = lane; i < na; i += GW) {
+                const uint64_t aw = L.anch[i];
+                const af_mem_t mi = L.mem[aw >> 40];
+                uint32_t fb = 0;                                   // the first anchor of the anchor's run
+                for (uint32_t k = 1; k < n_runs; ++k) { const uint32_t s = L.run_start[k]; fb = s <= i ? s : fb; }
+                R.node[i] = (AF_X(aw) - AF_X(L.anch[fb])) | ((uint64_t)mi.rpos << 32) | ((uint64_t)mi.len << 42) | ((uint64_t)mi.idx << 52) | ((uint64_t)mi.mate << 62);
+            }
+            if ((uint32_t)lane < n_runs) R.xbase[lane] = AF_X(L.anch[L.run_start[lane]]);
+            if ((uint32_t)lane <= n_runs) R.rs[lane] = (uint8_t)L.run_start[lane];
+            if (lane == 0) { R.avg = avg_mem_length; R.na = (uint8_t)na; R.n_runs = (uint8_t)n_runs; G.rflag[r_in] = (uint8_t)n_runs; }
+            return AF_ST_RUNS;
+        }
+    }
 #if defined(AF_PROFILE) || defined(AF_CUTS)
     if (G.dbg & 128) return AF_ST_UNALIGNED;          // timing experiment: stop after the sort
 #endif
@@ -918,10 +953,13 @@ __device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT
 #if defined(AF_PROFILE) || defined(AF_CUTS)
     if (G.dbg & 4) na = 0;                                   // timing experiments (results are wrong): stop after the anchors ...
 #endif
+    // (the runs' route: the small plain instance alone, and only where plan_kernel takes the chain table)
+    constexpr bool ROUTE = LEVEL == 0 && !GEN && GW == 64 && !WT::SEC && (uint32_t)WT::MA <= AF_RUN_NODES && (uint32_t)WT::MC <= AF_CTAB && (uint32_t)WT::MA <= AF_PLAN_AN;
     if (!fallback && !too_big && na > 0) {
-        status = af_chain<WT, GT, GEN>(G, L, na, avg, g);
+        status = af_chain<WT, GT, GEN, ROUTE>(G, L, na, avg, g, false, r_in);
         status = (uint32_t)g.shfl((int)status, 0);
         __syncthreads();
+        if (ROUTE && status == AF_ST_RUNS) return;              // chain_runs_kernel goes on from here
 #if defined(AF_PROFILE) || defined(AF_CUTS)
         if ((G.dbg & 8) && status == AF_ST_CAND) status = AF_ST_UNALIGNED;      // ... after the chains ...
 #endif
@@ -1103,6 +1141,162 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OC
         __syncthreads();
         af_plan_read<WT, LEVEL, GEN>(G, L, g, r_in, off, m, na, avg, fallback, too_big);
     }
+}
+
+// chain_runs_kernel: one LANE per run of anchors of the reads that af_chain's ROUTE has left in the staging slots - 16 run slots per read, four reads per
+// wavefront.  Everything chain_plan_kernel does behind the runs with one lane per run at 13 active lanes of 64 - the chaining DP, chain ends and starts,
+// backtracking and keep test (chain_core.h), check_left_MEM's lift - runs here 4 x 13 lanes wide, over the lane's own LDS columns [k][lane].  The kept chains
+// of a read are put in the order of the sorted starts by rank (cc_chain_pos) through a few words of LDS per read; std::sort by score keeps that order for up
+// to 16 chains and is the introsort for more (two chains per run are common: a MEM, and its two halves chained), which the read's 16 lanes emulate
+// (af_wave_sort).  The read then gets what af_plan_read's LEVEL-0 branch gives it: the chains' anchors left to right in the plan's anchor array, the chain
+// table, the plan's header and ntasks - plan_kernel finds the same table whoever wrote it.  A read of more chain starts than the small instance holds
+// (AF_RUN_CHAINS) or of more chain anchors than the plan's array goes to the large instance's list; LEVEL 1 is launched behind this kernel.
+// p and t hold GLOBAL anchor indices (< 96: a byte), f and msc 16 bits (a chain's score is below the read's length).
+struct af_runcol_t {
+    uint64_t (*node)[64]; int16_t (*fa)[64]; int16_t (*ma)[64]; int8_t (*pa)[64]; uint8_t (*ta)[64]; uint8_t (*sa)[64]; int lane;
+    __device__ __forceinline__ long long x(uint32_t k) const { return (long long)(uint32_t)node[k][lane]; }
+    __device__ __forceinline__ int32_t y(uint32_t k) const { return (int32_t)((node[k][lane] >> 32) & 1023u); }
+    __device__ __forceinline__ int32_t w(uint32_t k) const { return (int32_t)((node[k][lane] >> 42) & 1023u); }
+    __device__ __forceinline__ uint32_t mate(uint32_t k) const { return (uint32_t)(node[k][lane] >> 62); }
+    __device__ __forceinline__ int32_t f(uint32_t k) const { return fa[k][lane]; }
+    __device__ __forceinline__ int32_t msc(uint32_t k) const { return ma[k][lane]; }
+    __device__ __forceinline__ int32_t p(uint32_t k) const { return pa[k][lane]; }
+    __device__ __forceinline__ int32_t t(uint32_t k) const { return ta[k][lane]; }
+    __device__ __forceinline__ void set_f(uint32_t k, int32_t v) { fa[k][lane] = (int16_t)v; }
+    __device__ __forceinline__ void set_msc(uint32_t k, int32_t v) { ma[k][lane] = (int16_t)v; }
+    __device__ __forceinline__ void set_p(uint32_t k, int32_t v) { pa[k][lane] = (int8_t)v; }
+    __device__ __forceinline__ void set_t(uint32_t k, int32_t v) { ta[k][lane] = (uint8_t)v; }
+    __device__ __forceinline__ uint32_t start(uint32_t q) const { return sa[q][lane]; }
+    __device__ __forceinline__ void set_start(uint32_t q, uint32_t v) { sa[q][lane] = (uint8_t)v; }
+};
+static_assert(AF_RUN_NODES == af_wave_small_t::MA && AF_RUN_CHAINS == af_wave_small_t::MC && AF_RUN_CHAINS <= AF_CTAB && AF_RUN_NODES <= AF_PLAN_AN, "chain_runs_kernel holds what the small instance holds");
+__global__ void __launch_bounds__(64) chain_runs_kernel(const af_args_t G) {
+    __shared__ uint64_t s_node[AF_RUN_LEN][64];
+    __shared__ int16_t s_f[AF_RUN_LEN][64], s_msc[AF_RUN_LEN][64];      // (s_msc: once the starts are known, the lane's kept chains: start | anchors << 8)
+    __shared__ int8_t s_p[AF_RUN_LEN][64];
+    __shared__ uint8_t s_t[AF_RUN_LEN][64], s_sj[AF_RUN_LEN][64];       // s_sj: the lane's chain starts
+    // per read: the kept chains run by run (score << 8 | start), in the sorted starts' order (score << 8 | place there; then sorted by score) with their anchor counts
+    __shared__ uint32_t s_key[4][AF_RUN_CHAINS], s_ord[4][AF_RUN_CHAINS], s_piece[4][AF_RUN_CHAINS];
+    __shared__ uint16_t s_ipos[4][AF_RUN_CHAINS], s_jpos[4][AF_RUN_CHAINS];
+    __shared__ lsort::frame s_stack[4][16];
+    __shared__ uint8_t s_cnt[4][AF_RUN_CHAINS];
+    const af_grp_t<16> g;
+    const int lane = threadIdx.x, grp = lane >> 4, slot = lane & 15;
+    const ak_args_t& A = G.A;
+    const ac_params_t& P = A.P;
+    const uint32_t n_work = G.ctr[AFC_L0];
+    af_runcol_t C{s_node, s_f, s_msc, s_p, s_t, s_sj, lane};
+    uint32_t n_routed = 0;
+    for (uint32_t w0 = blockIdx.x * 4u; w0 < n_work; w0 += gridDim.x * 4u) {          // (the same for every lane: the barriers below are reached by all)
+        const uint32_t w = w0 + (uint32_t)grp;
+        const uint32_t r_in = w < n_work ? G.list0[w] : 0u;
+        const af_rstage_t& R = G.rstage[r_in];
+        const uint32_t n_runs = w < n_work ? G.rflag[r_in] : 0u;     // 0: the read was chained in place
+        const bool mine = (uint32_t)slot < n_runs;
+        uint32_t fb = 0, n = 0;
+        float avg = 0.f;
+        uint64_t xbase = 0;
+        if (mine) { fb = R.rs[slot]; n = (uint32_t)R.rs[slot + 1] - fb; avg = R.avg; xbase = R.xbase[slot]; }
+        if (n > AF_RUN_LEN) n = AF_RUN_LEN;                          // (af_chain's test has seen to it)
+        {   // the run's nodes into the lane's column, all loads in flight together
+            uint64_t v[AF_RUN_LEN];
+#pragma unroll
+            for (uint32_t q = 0; q < AF_RUN_LEN; ++q) v[q] = q < n ? R.node[fb + q] : 0ull;
+#pragma unroll
+            for (uint32_t q = 0; q < AF_RUN_LEN; ++q) { s_node[q][lane] = v[q]; s_t[q][lane] = 0; }
+        }
+        cc_run_dp<int32_t, uint32_t>(C, fb, n, (int32_t)P.max_iter, (uint32_t)P.max_pred, (long long)P.max_dist_x, (int32_t)P.max_dist_y, avg);
+        uint32_t ns = 0;                                             // the run's chain starts (at most one per anchor)
+        cc_run_starts(C, fb, n, P.min_chain_score, [&](uint32_t j) { C.set_start(ns++, j); });
+        // the starts in cc_start_before's order, every kept chain into the lane's list
+        uint32_t nk = 0, n_an = 0;
+        cc_run_chains(C, fb, n, ns, P.min_chain_score, P.min_chain_length, [](uint32_t) {},
+                      [&](uint32_t j0, int32_t, uint32_t cnt, bool keep) { if (keep) { s_msc[nk++][lane] = (int16_t)(j0 | (cnt << 8)); n_an += cnt; } });
+        // per read: starts, kept chains and their anchors, and where the lane's chains go in the read's list
+        uint32_t ns_all = ns, an_all = n_an, incl = nk;
+        for (int o = 1; o < 16; o <<= 1) { ns_all += (uint32_t)__shfl_xor((int)ns_all, o); an_all += (uint32_t)__shfl_xor((int)an_all, o); }
+        for (int o = 1; o < 16; o <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 16); if (slot >= o) incl += up; }
+        const uint32_t nk_all = (uint32_t)__shfl((int)incl, 15, 16);
+        const bool routed = n_runs > 0;                              // (the same in the 16 lanes of a read)
+        const bool big = routed && (ns_all > AF_RUN_CHAINS || an_all > AF_PLAN_AN);          // (kept chains: no more than starts)
+        const bool go = routed && !big;
+        if (go) for (uint32_t c = 0; c < nk; ++c) {
+            const uint32_t e = (uint32_t)(uint16_t)s_msc[c][lane], j = e & 0xFFu;
+            s_key[grp][incl - nk + c] = ((uint32_t)s_f[j - fb][lane] << 8) | j;
+            s_piece[grp][incl - nk + c] = e >> 8;                  // (its anchors; the sort's scratch is free until the sort)
+        }
+        __syncthreads();
+        // the chains' places in the sorted starts' order, the read's 16 lanes over its chains (a lane by itself over the chains of its run: as many passes of
+        // this loop as the fullest run of the wavefront has chains)
+#pragma unroll
+        for (uint32_t q = 0; q < (AF_RUN_CHAINS + 15) / 16; ++q) {
+            const uint32_t sidx = (uint32_t)slot + 16u * q;
+            if (go && sidx < nk_all) {
+                const uint32_t pos = cc_chain_pos(s_key[grp], nk_all, sidx);
+                s_ord[grp][pos] = (s_key[grp][sidx] & ~0xFFu) | pos;
+                s_cnt[grp][pos] = (uint8_t)s_piece[grp][sidx];
+                s_jpos[grp][sidx] = (uint16_t)pos;
+            }
+        }
+        __syncthreads();
+        if (go) for (uint32_t c = 0; c < nk; ++c) s_sj[c][lane] = (uint8_t)s_jpos[grp][incl - nk + c];
+        __syncthreads();
+        // std::sort of the chains by score (chain.hpp:402): ties.  (One wavefront per workgroup: the barriers inside only order the wave's own LDS traffic, and a
+        // read's 16 lanes go through it together, whatever the wavefront's other reads do - af_grp_t.)
+        if (go && nk_all > 16) af_wave_sort<(AF_RUN_CHAINS + 15) / 16>(g, s_ord[grp], nk_all, s_stack[grp], s_ipos[grp], s_jpos[grp], s_piece[grp], [](const uint32_t& x) { return -(int32_t)(x >> 8); });
+        __syncthreads();
+        {   // behind the sort: the place of every chain (s_ipos, by its place in the starts' order) and the anchors of the chains in front of a place (s_jpos)
+            uint32_t an_base = 0;
+#pragma unroll
+            for (uint32_t q = 0; q < (AF_RUN_CHAINS + 15) / 16; ++q) {
+                const uint32_t k = (uint32_t)slot + 16u * q;
+                const bool in = go && k < nk_all;
+                const uint32_t o = in ? (s_ord[grp][k] & 0xFFu) : 0u;
+                const uint32_t cn = in ? (uint32_t)s_cnt[grp][o] : 0u;
+                uint32_t inc = cn;
+                for (int d = 1; d < 16; d <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)inc, d, 16); if (slot >= d) inc += up; }
+                if (in) { s_ipos[grp][o] = (uint16_t)k; s_jpos[grp][k] = (uint16_t)(an_base + inc - cn); }
+                an_base += (uint32_t)__shfl((int)inc, 15, 16);
+            }
+        }
+        __syncthreads();
+        if (go) {
+            af_ctab_t* const CT = G.ctab + (size_t)r_in * AF_CTAB;
+            af_anchor_t* const AN = G.plans[r_in].an;
+            for (uint32_t c = 0; c < nk; ++c) {
+                const uint32_t e = (uint32_t)(uint16_t)s_msc[c][lane], cnt = e >> 8;
+                const uint32_t rank = s_ipos[grp][s_sj[c][lane]], an0 = s_jpos[grp][rank];      // the chain's place behind the sort, the anchors of the chains in front of it
+                int32_t j = (int32_t)(e & 0xFFu);
+                af_anchor_t X;
+                uint32_t mate = 0;
+                for (uint32_t q = 0; q < cnt; ++q) {                // right to left, as the chain was walked; fill_chain wants left to right
+                    const uint64_t nd = s_node[(uint32_t)j - fb][lane];
+                    const uint32_t len = (uint32_t)(nd >> 42) & 1023u;
+                    X.occ = xbase + (uint32_t)nd - len + 1; X.len = (uint16_t)len; X.idx = (uint16_t)((nd >> 52) & 1023u); X.gap_val = 0; X.gap_kind = AF_GAP_NONE; X.pad = 0;
+                    AN[an0 + cnt - 1 - q] = X;
+                    mate = (uint32_t)(nd >> 62);
+                    j = s_p[(uint32_t)j - fb][lane];
+                }
+                // check_left_MEM's coordinate of the chain: index(lift(leftmost anchor)).second + 1 (aligner_ksw2.hpp:565-576)
+                af_ctab_t E; E.score = (int32_t)(s_ord[grp][rank] >> 8); E.an0 = (uint16_t)an0; E.cnt = (uint8_t)cnt; E.strand = (mate & 2u) ? 1 : 0;
+                E.left_ref = ac_seq_off(P, ac_lift(P, X.occ)) + 1;
+                CT[rank] = E;
+            }
+            if (slot == 0) {          // the plan's header so far, as af_plan_read writes it: plan_kernel completes it; a read with no chain start is not chained
+                const uint64_t r = A.read_lo + r_in;
+                const uint32_t m = (uint32_t)(A.offs[r + 1] - A.offs[r]);
+                af_plan_t& PH = G.plans[r_in];
+                PH.status = ns_all == 0 ? AF_ST_UNALIGNED : AF_ST_CHAINS; PH.n_cand = 0; PH.n_chains = (uint16_t)nk_all; PH.final_cand = 0; PH.n_alt = 0; PH.pad = 0; PH.score2 = 0;
+                PH.ref_pos = PH.ref_len = 0; PH.tb0 = 0; PH.pad2 = 0;
+                PH.min_score = A.min_score_of_len[m <= A.max_len ? m : A.max_len];
+                G.ntasks[r_in] = 0;
+                ++n_routed;
+            }
+        } else if (big && slot == 0) G.big_list[atomicAdd(&G.ctr[AFC_BIG], 1u)] = r_in;          // rare: the large instance chains the read from its seeds
+        __syncthreads();                                             // (the read's tables are the next read's)
+    }
+    for (int o = 32; o > 0; o >>= 1) n_routed += (uint32_t)__shfl_xor((int)n_routed, o);
+    if (lane == 0 && n_routed) atomicAdd(&G.ctr[AFC_RUNS], n_routed);
 }
 
 // plan_kernel: one LANE per read whose chains chain_plan_kernel's LEVEL-0 instance has left in HBM (status AF_ST_CHAINS): the chain-selection loop ahead of its
@@ -3414,6 +3608,8 @@ __global__ void gather_summary_kernel(const uint64_t* __restrict__ len, const ui
 // by tile, then the global problems: their records (global_task_kernel), their bands and queues (global_band_kernel), banded where a narrow band is proven,
 // the full matrix otherwise.  n_units: plans of the launch (reads or pairs).
 // chunks up to which dp_wave_kernel takes a group (a pair costs it ~0.1 ms of one SIMD; dp_lane_kernel's launch ~2 ms whatever the count): MONI_AF_WAVE_MAX, 0 = never
+// MONI_AF_RUNS=0: no read leaves chain_plan_kernel behind its runs of anchors, all are chained in place (the A/B switch of chain_runs_kernel)
+static inline bool af_runs_on() { const char* v = getenv("MONI_AF_RUNS"); return !(v && atoi(v) == 0); }      // (read at every launch, as MONI_AF_DBG is)
 static inline uint32_t af_wave_max() { const char* v = getenv("MONI_AF_WAVE_MAX"); return v ? (uint32_t)strtoul(v, nullptr, 10) : 96u; }
 static inline void af_launch_dp(const af_args_t& G, hipStream_t sx, unsigned dp_grid, unsigned n_cu, uint64_t n_units) {
     if (!(G.dbg & 0x20000u)) hipLaunchKernelGGL(band_tasks_kernel, dim3((unsigned)((G.bin_cap + 255) / 256)), dim3(256), 0, sx, G);      // (the provisional list holds at most bin_cap problems)

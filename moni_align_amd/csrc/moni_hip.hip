@@ -172,7 +172,7 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
     DBuf<uint8_t> dp_dir_big;
     struct AfSet {          // device buffers of the staged align kernels (align_fast.hip), one set per launch stream
         DBuf<af_plan_t> plans; DBuf<moni_dp_task_t> tasks; DBuf<af_res_t> res; DBuf<uint32_t> bin_q, task_pos, tb_task, big_list, ctr; DBuf<uint8_t> ntasks;
-        DBuf<af_chunk_t> chunks; DBuf<uint8_t> dirs, fin; DBuf<uint32_t> recipes; DBuf<af_ctab_t> ctab; DBuf<af_tb_t> tb; DBuf<uint64_t> bnd; DBuf<unsigned long long> prof, prep_prof, txt_cur;
+        DBuf<af_chunk_t> chunks; DBuf<uint8_t> dirs, fin; DBuf<uint32_t> recipes; DBuf<af_ctab_t> ctab; DBuf<af_rstage_t> rstage; DBuf<uint8_t> rflag; DBuf<af_tb_t> tb; DBuf<uint64_t> bnd; DBuf<unsigned long long> prof, prep_prof, txt_cur;
     } af[AK_NSET], af_pe[PE_NSET];
     HBuf<unsigned long long> pe_hcur;       // paired path, per chunk: the pool cursors / DP counters (8 words) and the number of pairs handed over, copied behind the chunk's kernels
     HBuf<uint32_t> af_ctr_host;             // counters of the last batch's launches (64 words per sub-batch), pinned
@@ -1235,6 +1235,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
     std::string out;
     mh::AlignStats st;
     uint64_t why_out[12] = {};
+    uint64_t runs_routed = 0;          // reads chained by chain_runs_kernel
     const uint8_t* q = quals ? quals + b->offsets[0] : nullptr;
     static const bool host_only = getenv("MONI_ALIGN_HOST") != nullptr;
     bool out_done = false;
@@ -1390,7 +1391,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         if (use_fast) for (int x = 0; x < (int)std::min<uint64_t>(n_sub, AK_NSET); ++x) {
             moni_ctx::AfSet& S = c->af[x];
             if ((rc = S.plans.ensure(sub_reads + 1)) || (rc = S.tasks.ensure(af_slot_cap)) || (rc = S.res.ensure(af_slot_cap)) || (rc = S.ntasks.ensure(sub_reads + 8)) || (rc = S.bin_q.ensure((size_t)(AF_NBIN + 1) * af_task_cap)) ||
-                (rc = S.task_pos.ensure(af_slot_cap)) || (rc = S.tb_task.ensure(af_tb_cap)) || (rc = S.tb.ensure(af_tb_cap)) || (rc = S.big_list.ensure(3 * (sub_reads + 1))) || (rc = S.ctab.ensure((size_t)(sub_reads + 1) * AF_CTAB)) ||
+                (rc = S.task_pos.ensure(af_slot_cap)) || (rc = S.tb_task.ensure(af_tb_cap)) || (rc = S.tb.ensure(af_tb_cap)) || (rc = S.big_list.ensure(3 * (sub_reads + 1))) || (rc = S.ctab.ensure((size_t)(sub_reads + 1) * AF_CTAB)) || (af_runs_on() && ((rc = S.rstage.ensure(sub_reads + 1)) || (rc = S.rflag.ensure(sub_reads + 8)))) ||
                 (rc = S.ctr.ensure(AF_NCTR)) || (rc = S.txt_cur.ensure(AF_TXT_SHARDS * 8)) || (rc = S.bnd.ensure((size_t)af_dp_grid * AF_QCAP * 64)) || (rc = S.chunks.ensure(af_chunk_cap)) || (rc = S.dirs.ensure(af_dirs_cap)) || (rc = S.fin.ensure((size_t)af_fin_grid * 64 * sizeof(af_fin_t))) || (gpu_text && !fin_v1 && (rc = S.recipes.ensure((size_t)(sub_reads + 1) * AFP_WORDS))))
                 return rc;
         }
@@ -1606,6 +1607,14 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                 G.l0_mm = l0_mid ? (uint32_t)af_wave_mid_t::MM : (uint32_t)af_wave_small_t::MM; G.l0_ma = l0_mid ? (uint32_t)af_wave_mid_t::MA : (uint32_t)af_wave_small_t::MA;
                 const bool no_k2 = getenv("MONI_AF_NOPLANK") != nullptr;          // (measurement: the LEVEL-0 instance runs the selection loop and builds the plan itself, as the others do)
                 G.ctab = (no_k2 || l0_mid) ? nullptr : S.ctab.p;
+                // the runs' route (chain_runs_kernel): where the small plain instance chains one read per wavefront and plan_kernel takes the chain table
+                static const int l0_gw = getenv("MONI_AF_GW") ? atoi(getenv("MONI_AF_GW")) : 64;          // lanes of a read in the small instance (below)
+                G.rstage = (G.ctab && af_runs_on() && !(G.dbg & 64) && G.chain_narrow && l0_gw != 16) ? S.rstage.p : nullptr;
+#if defined(AF_PROFILE) || defined(AF_CUTS)
+                if (G.dbg & (4u | 8u | 16u | 32u | 128u | 256u | 512u | 1024u)) G.rstage = nullptr;      // the cut points of a phase split lie in the in-place path: every read stays there
+#endif
+                G.rflag = S.rflag.p;
+                if (G.rstage) HIPCHK(hipMemsetAsync(S.rflag.p, 0, nr, sx));          // (a read that takes the route sets its byte)
                 hipLaunchKernelGGL(classify_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, sx, G);
                 // MONI_AF_DBG=64, or chaining parameters beyond cc_narrow_ok, launch the general instances, which hold the serial sorts and the 64-bit chaining DP;
                 // the others have no call and no stack in them
@@ -1618,7 +1627,6 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                 } else {
                     // four reads per wavefront (16 lanes each, 4 x 4.6 KB of LDS): 8 wavefronts = 32 reads in flight per CU, as with one read per wavefront at
                     // 8 waves/SIMD, but the one-lane sections issue a quarter of the instructions.  MONI_AF_GW=64: one read per wavefront (MONI_AF_K1OCC waves/SIMD)
-                    static const int l0_gw = getenv("MONI_AF_GW") ? atoi(getenv("MONI_AF_GW")) : 64;
                     static const int k1occ = getenv("MONI_AF_K1OCC") ? atoi(getenv("MONI_AF_K1OCC")) : (l0_gw == 16 ? 2 : 8);      // one read per wavefront: measured 5, 6, 8 waves/SIMD
                     const dim3 g1((unsigned)std::min<uint64_t>(l0_gw == 16 ? (nr + 3) / 4 : nr, (uint64_t)n_cu * 4 * k1occ));
                     if (l0_gw == 16) AF_LAUNCH_CP(af_wave_small_t, 0, 2, 16, g1);
@@ -1627,6 +1635,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                     else if (k1occ == 8) AF_LAUNCH_CP(af_wave_small_t, 0, 8, 64, g1);
                     else AF_LAUNCH_CP(af_wave_small_t, 0, 6, 64, g1);
                 }
+                if (G.rstage) hipLaunchKernelGGL(chain_runs_kernel, dim3((unsigned)std::min<uint64_t>((nr + 3) / 4, (uint64_t)n_cu * 40)), dim3(64), 0, sx, G);      // feeds big_list: ahead of LEVEL 1
                 AF_LAUNCH_CP(af_wave_t, 1, 3, 64, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * 10)));
                 static const bool no_huge = getenv("MONI_AF_NOHUGE") != nullptr;          // (debugging aid: reads beyond the large instance then go straight to align_kernel)
                 if (!no_huge) AF_LAUNCH_CP(af_wave_huge_t, 2, 1, 64, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu)));      // ~90 KB of LDS per wave: one per CU
@@ -1704,9 +1713,10 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                     any_dirs_ovf_batch = any_dirs_ovf_batch || fc[AFC_DIRS_OVF] != 0;
                     st.dp_tasks += fc[AFC_NT] + (fc[AFC_TASKS] >= (uint32_t)(sub_lo[k + 1] - sub_lo[k]) * AF_MAX_TASKS_READ ? fc[AFC_TASKS] - (uint32_t)(sub_lo[k + 1] - sub_lo[k]) * AF_MAX_TASKS_READ : 0u); st.dp_cells += cells; st.kernel_fallback += fbn[16 * k]; st.dp_ref_bytes += rb;
                     for (int x = 0; x < AF_WHY_N; ++x) why_sum[x] += fc[AFC_WHY + x];
+                    runs_routed += fc[AFC_RUNS];
                     if (getenv("MONI_AK_PROFILE")) { unsigned long long du; memcpy(&du, fc + AFC_DIROFF, 8); fprintf(stderr, "  direction bits of sub-batch %llu: %.1f MB used of %.1f MB\n", (unsigned long long)k, du / 1e6, af_dirs_cap / 1e6); }
-                    if (getenv("MONI_AK_PROFILE")) fprintf(stderr, "  staged kernels, sub-batch %llu: %u DP tasks, %llu cells, %u traced, %u large + %u small + %u global chunks, %u reads to align_kernel%s\n",
-                                                           (unsigned long long)k, fc[AFC_NT], cells, fc[AFC_TRACED], fc[AFC_NCHUNKS], fc[AFC_NCHUNKS + 1], fc[AFC_NCHUNKS + 2], fbn[16 * k], fc[AFC_DIRS_OVF] ? " (direction bytes overflowed)" : "");
+                    if (getenv("MONI_AK_PROFILE")) fprintf(stderr, "  staged kernels, sub-batch %llu: %u DP tasks, %llu cells, %u traced, %u large + %u small + %u global chunks, %u reads to align_kernel%s; %u of the small instance's %u reads chained by chain_runs_kernel\n",
+                                                           (unsigned long long)k, fc[AFC_NT], cells, fc[AFC_TRACED], fc[AFC_NCHUNKS], fc[AFC_NCHUNKS + 1], fc[AFC_NCHUNKS + 2], fbn[16 * k], fc[AFC_DIRS_OVF] ? " (direction bytes overflowed)" : "", fc[AFC_RUNS], fc[AFC_L0]);
                     if (getenv("MONI_AK_PROFILE")) { fprintf(stderr, "    DP problems per bin (16 of the large tile by query length <= 8 13 16 24 32 48 64 .. 160 192 224 256, 3 of the small tile <= 8 16 32, 16 global by query length / 16):"); for (int x = 0; x < AF_NBIN; ++x) fprintf(stderr, " %u", fc[AFC_BINS + x]); fprintf(stderr, "\n"); }
 #if defined(AF_CUTS)
                     if (getenv("MONI_AK_PROFILE")) { fprintf(stderr, "    tile problems (extension | gap fill q = t | gap fill q != t) x (band <= 16 | wider | extension with t < q | no bound):"); for (int x = 0; x < 12; ++x) fprintf(stderr, "%s %u", x % 4 == 0 ? " |" : "", fc[180 + x]); fprintf(stderr, "\n"); }
@@ -1836,6 +1846,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         stats->kernel_fallback = st.kernel_fallback; stats->dp_ref_bytes = st.dp_ref_bytes; stats->dp_cells_cut = st.dp_cells_cut; stats->dp_slots = st.dp_slots;
         stats->t_k_chain = st.t_k_chain; stats->t_k_dp = st.t_k_dp; stats->t_k_select = st.t_k_select; stats->t_k_finish = st.t_k_finish;
         for (int x = 0; x < 12; ++x) stats->handover_why[x] = why_out[x];
+        stats->runs_routed = runs_routed;
     }
     return MONI_OK;
 }
