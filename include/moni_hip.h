@@ -550,6 +550,26 @@ int  moni_approx_fetch(moni_ctx_t *ctx, moni_approx_res_t *res, moni_approx_hit_
 int  moni_approx_batch(moni_ctx_t *ctx, const moni_read_batch_t *batch, const moni_approx_params_t *prm, moni_approx_res_t *res,
                        moni_approx_hit_t **hits, uint64_t **pos, uint32_t **seq, uint64_t **seq_off, uint64_t *n_hits_kept, uint64_t *n_occ);
 
+/* ---- BGZF output: the SAM text deflated on the GPU ------------------------------------ */
+/* The output is a concatenation of BGZF blocks (SAM specification 4.1): each one gzip member with the `BC` extra subfield and exactly one raw
+ * DEFLATE block (BFINAL = 1) of at most block_size bytes of the text - dynamic Huffman over an LZ77 parse that never leaves the block, or
+ * stored where that is not smaller (and always at level 0).  The bytes are a function of (text, block_size, level) alone: not of the context,
+ * the device, or how the text is cut into calls at multiples of block_size. */
+typedef struct { uint32_t block_size;  /* uncompressed bytes per block, 1 .. 65280; default 65280 */
+                 uint32_t level;       /* 0 stored blocks, 1 LZ77 + dynamic Huffman; default 1 */
+                 uint32_t eof;         /* append the 28-byte end-of-file block; default 0 */
+                 uint32_t reserved; } moni_bgzf_params_t;
+typedef struct { uint64_t in_bytes, out_bytes, blocks, stored_blocks, matches, literals;
+                 double t_kernel, t_total; } moni_bgzf_stats_t;      /* HIP-event seconds of the kernels; host seconds with the transfers */
+void moni_bgzf_params_default(moni_bgzf_params_t *p);
+/* text: len bytes of host memory (the context's pinned SAM buffer, as moni_align_stream / moni_pe_align_stream / moni_extend_run return it, is
+ * the intended caller).  *out points into a pinned buffer of the context: valid until the next moni_bgzf_compress or moni_ctx_destroy on this
+ * context, not to be freed.  blocks / out_bytes count the end-of-file block too.  The resident read batch and every result a later *_fetch may
+ * want stay as they are.  stats may be NULL.  MONI_EINVAL: a NULL ctx, prm, out or out_len, block_size 0 or above 65280, level above 1, a
+ * non-zero reserved, text NULL with len > 0.  len 0 gives MONI_OK and no byte (28 with eof).  MONI_ENOMEM is returned before anything is written. */
+int  moni_bgzf_compress(moni_ctx_t *ctx, const void *text, uint64_t len, const moni_bgzf_params_t *prm,
+                        const uint8_t **out, uint64_t *out_len, moni_bgzf_stats_t *stats);
+
 /* ---- the reference's on-disk liftidx (<prefix>.ldx: include/aligner/liftidx.hpp:117-143 over include/common/seqidx.hpp:197-238) ---- */
 /* Both layouts load: the current one (u64 w after u) and the older one the reference's fixture data/Chr21.10.ldx has. */
 int moni_ldx_info(const char *path, uint64_t *n_seq, uint64_t *u, uint64_t *w, int *has_w);

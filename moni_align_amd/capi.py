@@ -37,6 +37,7 @@ EXPORTS = [
     "moni_loci_params_default", "moni_loci_run", "moni_loci_sizes", "moni_loci_fetch", "moni_loci_batch",
     "moni_approx_params_default", "moni_approx_run", "moni_approx_sizes", "moni_approx_fetch", "moni_approx_batch",
     "moni_mslong_params_default", "moni_ms_long_batch",
+    "moni_bgzf_params_default", "moni_bgzf_compress",
 ]
 
 
@@ -129,6 +130,15 @@ class MslongStatsC(C.Structure):
     _fields_ = [("patterns", C.c_uint64), ("bases", C.c_uint64), ("segments", C.c_uint64), ("flagged", C.c_uint64), ("chain_runs", C.c_uint64),
                 ("steps_spec", C.c_uint64), ("steps_chain", C.c_uint64), ("jumps", C.c_uint64),
                 ("t_walk", C.c_double), ("t_len", C.c_double), ("t_chain", C.c_double), ("t_total", C.c_double)]
+
+
+class BgzfParamsC(C.Structure):
+    _fields_ = [("block_size", C.c_uint32), ("level", C.c_uint32), ("eof", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BgzfStatsC(C.Structure):
+    _fields_ = [("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("matches", C.c_uint64),
+                ("literals", C.c_uint64), ("t_kernel", C.c_double), ("t_total", C.c_double)]
 
 
 class DpParamsC(C.Structure):
@@ -286,6 +296,10 @@ def lib():
         L.moni_ms_file_write.argtypes = [C.POINTER(FlatIndexC), C.c_char_p]
         L.moni_index_load_reference.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
         L.moni_ldx_lift_batch.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.moni_bgzf_params_default.argtypes = [C.POINTER(BgzfParamsC)]
+        L.moni_bgzf_params_default.restype = None
+        L.moni_bgzf_compress.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BgzfParamsC), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                         C.POINTER(BgzfStatsC)]
         _lib = L
     return _lib
 
@@ -698,6 +712,18 @@ class Ctx:
         res = np.zeros(nr.value, dtype=SCREEN_RES_DTYPE)
         _chk(self._L.moni_screen_fetch(self._h, res.ctypes.data if nr.value else None), "moni_screen_fetch")
         return res
+
+    def bgzf_compress(self, data, block_size: int = 65280, level: int = 1, eof: bool = False, reserved: int = 0):
+        """moni_bgzf_compress: `data` (bytes, or a uint8 array) as a concatenation of BGZF blocks of at most block_size bytes of it each, with the
+        end-of-file block where asked for.  Returns (bytes, stats: the fields of moni_bgzf_stats_t)."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        p = BgzfParamsC()
+        self._L.moni_bgzf_params_default(C.byref(p))
+        p.block_size, p.level, p.eof, p.reserved = block_size, level, 1 if eof else 0, reserved
+        out, n, st = C.c_void_p(), C.c_uint64(), BgzfStatsC()
+        _chk(self._L.moni_bgzf_compress(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(p), C.byref(out), C.byref(n), C.byref(st)),
+             "moni_bgzf_compress")
+        return C.string_at(out.value, n.value) if n.value else b"", {k: getattr(st, k) for k, _ in BgzfStatsC._fields_}
 
     def _locate_params(self, strands: int, max_occ: int) -> "LocateParamsC":
         p = LocateParamsC()

@@ -47,6 +47,7 @@
 #include "loci_kernels.hip"
 #include "approx_kernels.hip"
 #include "mslong_kernels.hip"
+#include "bgzf_kernels.hip"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "moni_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return MONI_ENODEV; } } while (0)
 
@@ -239,7 +240,11 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
         DBuf<uint64_t> ptr, cnt, seg_off, head, run_idx; DBuf<uint32_t> lens, flags; DBuf<mslong_seg_t> segs; DBuf<mslong_state_t> states; DBuf<mslong_run_t> runs;
         DBuf<unsigned long long> counters;
     } msl;
-    int n_cu_cached = 0, pe_occ_cached = 0;          // hipGetDeviceProperties / the occupancy query take a millisecond each: asked once per context
+    struct BgzfBufs {       // BGZF output (bgzf_api.inc): the text, the blocks' staging slots, a token region per workgroup, the packed stream and its pinned copy; grow-only
+        DBuf<uint8_t> text, out; DBuf<uint32_t> staging, tok; DBuf<uint64_t> len, off, pos; DBuf<unsigned long long> counters; HBuf<unsigned long long> h_sum;
+        HBuf<uint8_t> h_out; Event e0, e1;
+    } bz;
+    int n_cu_cached = 0, pe_occ_cached = 0;         // hipGetDeviceProperties / the occupancy query take a millisecond each: asked once per context
 };
 
 namespace {
@@ -2062,5 +2067,6 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "loci_api.inc"
 #include "approx_api.inc"
 #include "mslong_api.inc"
+#include "bgzf_api.inc"
 
 }  // extern "C"

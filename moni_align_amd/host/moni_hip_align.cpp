@@ -79,6 +79,15 @@ static void die(const std::string& msg) { fprintf(stderr, "[ERROR] %s\n", msg.c_
 static void put(const void* p, size_t n, FILE* f) { if (n && fwrite(p, 1, n, f) != n) die("short write to the output file"); }
 static void close_out(FILE* f) { if (f && fclose(f) != 0) die("closing the output file failed (output incomplete)"); }
 static void info(const std::string& msg) { printf("[INFO] Message: %s\n", msg.c_str()); fflush(stdout); }
+// --bgzf: `len` bytes of text as BGZF blocks, in the context's pinned buffer until its next call; eof: the end-of-file block behind them
+static void bgzf_blocks(moni_ctx_t* c, const char* text, uint64_t len, bool eof, const char** z, uint64_t* zl) {
+    moni_bgzf_params_t bp; moni_bgzf_params_default(&bp);
+    bp.eof = eof ? 1 : 0;
+    const uint8_t* o = nullptr;
+    const int rc = moni_bgzf_compress(c, text, len, &bp, &o, zl, nullptr);
+    if (rc) die("moni_bgzf_compress failed (" + std::to_string(rc) + ")");
+    *z = (const char*)o;
+}
 
 struct Batch {
     std::vector<uint8_t> seq, qual, names;
@@ -226,6 +235,7 @@ struct Args {
     bool dry_write = false;     // --dry-run-write: no GPU, but the single-end front end's batching runs - ranges, workers of all (absent) GPUs, blocks placed in input order - with placeholder records
     moni_pe_params_t PE;               // -d, -D (paired-end)
     bool find_orphan = true;           // -u switches orphan recovery off
+    bool bgzf = false;                 // --bgzf: the SAM text as BGZF blocks in <out>.gz, deflated on the GPU by the context that aligned it (moni_bgzf_compress)
 };
 
 static void parse(int argc, char** argv, Args& a) {
@@ -240,6 +250,7 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--dry-run")) { a.dry_run = true; continue; }
         if (!strcmp(argv[i], "--dry-run-write")) { a.dry_run = true; a.dry_write = true; continue; }
         if (!strcmp(argv[i], "--ctx-per-gpu") && i + 1 < argc) { a.ctx_per_gpu = std::max(1, atoi(argv[++i])); continue; }
+        if (!strcmp(argv[i], "--bgzf")) { a.bgzf = true; continue; }
         if (!strcmp(argv[i], "--ms")) { a.legacy_ms = true; continue; }
         if (!strcmp(argv[i], "--mems")) { a.legacy_mems = true; continue; }
         if (!strcmp(argv[i], "--split")) { a.split = true; continue; }
@@ -271,8 +282,9 @@ static void parse(int argc, char** argv, Args& a) {
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
-                              "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n";
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
+                              "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n"
+                              "  --bgzf: the SAM output (single end, -1 / -2, -m, --extend) as blocked gzip in <output>.gz, compressed on the GPU; samtools, htslib and bgzip -d read it as SAM\n";
     int c;
     char* s;
     optind = 1;
@@ -552,9 +564,9 @@ static int run_paired(Args& a, const std::string& sam_filename) {
     if (a.dry_run) {
         Batch b;
         const size_t n = read_pairs(r1, r2, (size_t)-1, b);
-        printf("dry-run: pairs=%zu bases=%zu min_len=%u filter_dir=%u dir_thr=%.1f find_orphan=%u b=%zu threads=%zu gpus=%d out=%s first=%.*s second=%.*s\n", n, b.seq.size(),
+        printf("dry-run: pairs=%zu bases=%zu min_len=%u filter_dir=%u dir_thr=%.1f find_orphan=%u b=%zu threads=%zu gpus=%d out=%s first=%.*s second=%.*s%s\n", n, b.seq.size(),
                a.P.min_len, a.PE.filter_dir, a.PE.dir_thr, a.PE.find_orphan, a.b, a.th, a.gpus, sam_filename.c_str(), n ? (int)b.name_off[1] : 0,
-               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "");
+               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", a.bgzf ? " bgzf=1" : "");
         return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
@@ -572,7 +584,11 @@ static int run_paired(Args& a, const std::string& sam_filename) {
     const auto t0 = std::chrono::steady_clock::now();
     FILE* out = fopen(sam_filename.c_str(), "w");
     if (!out) die("open() file " + sam_filename + " failed");
-    { char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header"); put(h, hl, out); moni_free(h); }
+    // --bgzf: every piece of text goes through moni_bgzf_compress on the context that made it, and its blocks take the text's place
+    auto put_text = [&](moni_ctx_t* C, const char* p, uint64_t n) {
+        if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(C, p, n, false, &z, &zl); put(z, zl, out); } else put(p, n, out);
+    };
+    { char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header"); put_text(ctx[0], h, hl); moni_free(h); }
     // -c: <sam>.csv, one line per pair (aligner_ksw2.hpp:911-914; header of aligner::to_csv, :3230-3234); the blocks of the batches are kept and written in input order at the end
     FILE* out2 = nullptr;
     std::map<size_t, std::string> csv_blocks;
@@ -632,7 +648,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         if (all.n()) {
             char* sam = nullptr; uint64_t len = 0, n_al = 0;
             align_one(0, all, &sam, &len, &n_al);
-            put(sam, len, out); moni_free(sam);
+            put_text(ctx[0], sam, len); moni_free(sam);
             if (out2) put(csv_first.data(), csv_first.size(), out2);
             processed += all.n() / 2; aligned += n_al;
         }
@@ -717,6 +733,8 @@ static int run_paired(Args& a, const std::string& sam_filename) {
                 if (rc) die("moni_pe_align_stream failed (" + std::to_string(rc) + (rc == MONI_ERANGE ? ": a pair exceeds the paired path's capacities)" : ")"));
                 n_al = st.aligned;
             }
+            char* const lib_sam = sam;          // (what moni_free takes back in the -m path)
+            if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(C, sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
             uint64_t at = 0;
             const double x2 = now();
             {
@@ -739,7 +757,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
             t_lib[w] += x2 - x1; t_wait[w] += x3 - x2; t_write[w] += x4 - x3;
             if (verbose_batches) fprintf(stderr, "batch %zu (worker %d, %zu pairs): library %.0f ms, wait %.0f ms, write %.0f ms, done at %.3f s\n", it.id, w, v_n / 2, (x2 - x1) * 1e3, (x3 - x2) * 1e3, (x4 - x3) * 1e3,
                                         std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-            if (a.report_mems || a.csv) moni_free(sam);
+            if (a.report_mems || a.csv) moni_free(lib_sam);
             n_proc += v_n / 2; n_al_all += n_al;
             delete it.b; delete it.f;
         }
@@ -759,6 +777,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
              std::to_string(sl) + ", waiting for the block's place " + std::to_string(sw) + ", file writes " + std::to_string(sr));
     }
     if (fseeko(out, (off_t)off_upto, SEEK_SET) != 0) die("seek in the output file failed");
+    if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
     for (int g = 0; g < a.gpus; ++g) for (int k = 1; k < per_gpu; ++k) moni_ctx_destroy(wctx[(size_t)g * per_gpu + k]);
     close_out(out);
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -863,12 +882,25 @@ int main(int argc, char** argv) {
         if (a.legacy_ms) die("--extend cannot be combined with --ms");
         if (a.legacy_mems) die("--extend cannot be combined with --mems");
     }
+    if (a.bgzf) {            // BGZF output: the modes that write SAM
+        if (a.csv) die("--bgzf cannot be combined with -c");
+        if (a.dry_write) die("--bgzf cannot be combined with --dry-run-write");
+        if (a.legacy_ms) die("--bgzf cannot be combined with --ms");
+        if (a.legacy_mems) die("--bgzf cannot be combined with --mems");
+        if (a.pseudo_ms) die("--bgzf cannot be combined with --pseudo-ms");
+        if (a.screen) die("--bgzf cannot be combined with --screen");
+        if (a.locate) die("--bgzf cannot be combined with --locate");
+        if (a.seq_count) die("--bgzf cannot be combined with --seq-count");
+        if (a.loci) die("--bgzf cannot be combined with --loci");
+        if (a.approx) die("--bgzf cannot be combined with --approx");
+    }
     if (!paired && a.patterns.empty()) die("no reads given (-p)");
     std::string fn = a.filename;
     std::vector<char> tmp(fn.begin(), fn.end()); tmp.push_back(0);
     const std::string base_name = basename(tmp.data());
     std::string sam_filename = (paired ? a.mate1 : a.patterns) + "_" + base_name + "_" + std::to_string(a.P.min_len) + ".sam";   // align_full_ksw2.cpp:347-353
     if (!a.output.empty()) sam_filename = a.output;
+    if (a.bgzf) sam_filename += ".gz";
     if (paired) return run_paired(a, sam_filename);
     const bool legacy = a.legacy_ms || a.legacy_mems;
     if ((legacy || a.pseudo_ms || a.screen || a.locate || a.seq_count || a.loci || a.approx) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate / .seqcount)
@@ -881,9 +913,9 @@ int main(int argc, char** argv) {
         Batch b; size_t n = 0, bases = 0;
         while (next_record(b)) { ++n; }
         bases = b.seq.size();
-        printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s\n", n, bases, a.P.min_len,
+        printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : a.screen ? (a.one_strand ? " mode=screen strands=1" : " mode=screen strands=2") : (a.locate ? (a.both_strands ? " mode=locate strands=2" : " mode=locate strands=1") : (a.seq_count ? (a.both_strands ? " mode=seq-count strands=2" : " mode=seq-count strands=1") : (a.loci ? (a.both_strands ? " mode=loci strands=2" : " mode=loci strands=1") : (a.approx ? (" mode=approx k=" + std::to_string(a.approx_k) + (a.both_strands ? " strands=2" : " strands=1")).c_str() : ""))))));
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : a.screen ? (a.one_strand ? " mode=screen strands=1" : " mode=screen strands=2") : (a.locate ? (a.both_strands ? " mode=locate strands=2" : " mode=locate strands=1") : (a.seq_count ? (a.both_strands ? " mode=seq-count strands=2" : " mode=seq-count strands=1") : (a.loci ? (a.both_strands ? " mode=loci strands=2" : " mode=loci strands=1") : (a.approx ? (" mode=approx k=" + std::to_string(a.approx_k) + (a.both_strands ? " strands=2" : " strands=1")).c_str() : ""))))), a.bgzf ? " bgzf=1" : "");
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
@@ -915,7 +947,12 @@ int main(int argc, char** argv) {
         const int fd = ::open(sam_filename.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (fd < 0) die("open() file " + sam_filename + " failed");
         uint64_t hdr_len = 0;
-        if (!a.dry_write) { char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header"); pwrite_all(fd, h, hl, 0); hdr_len = hl; moni_free(h); }
+        if (!a.dry_write) {
+            char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
+            const char* hz = h; uint64_t hzl = hl;
+            if (a.bgzf) bgzf_blocks(ctx[0], h, hl, false, &hz, &hzl);          // the header as blocks of its own, before the workers take the contexts
+            pwrite_all(fd, hz, hzl, 0); hdr_len = hzl; moni_free(h);
+        }
         std::mutex mu; std::condition_variable cv;
         std::vector<uint64_t> lens(n_chunks, ~0ull), starts(n_chunks, 0);
         size_t upto = 0; uint64_t off_upto = hdr_len;
@@ -949,6 +986,8 @@ int main(int argc, char** argv) {
                 } else if (B.n) {
                     moni_read_batch_t rb{B.seq.p, B.off.data(), (uint64_t)B.n};
                     if (moni_align_stream(ctx[w], &rb, B.names.p, B.name_off.data(), fq ? B.qual.p : nullptr, &a.P, &sam, &len, &st)) die("moni_align_stream failed");
+                    // --bgzf: the range's text from the context's pinned buffer through the same context; its blocks take the text's place below
+                    if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[w], sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
                 }
                 double x2 = now(); t_lib[w] += x2 - x1;
                 uint64_t at;
@@ -979,6 +1018,7 @@ int main(int argc, char** argv) {
         std::vector<std::thread> th;
         for (size_t w = 0; w < ctx.size(); ++w) th.emplace_back(worker, (int)w);
         for (auto& t : th) t.join();
+        if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); pwrite_all(fd, z, zl, off_upto); }          // the end-of-file block
         if (::close(fd) != 0) die("close() of the output file failed");
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         info("Number of aligned reads: " + std::to_string(aligned.load()) + "/" + std::to_string(processed.load()));
@@ -1005,7 +1045,9 @@ int main(int argc, char** argv) {
     else {
         out = fopen(sam_filename.c_str(), "w");
         if (!out) die("open() file " + sam_filename + " failed");
-        char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header"); put(h, hl, out); moni_free(h);
+        char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
+        if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], h, hl, false, &z, &zl); put(z, zl, out); } else put(h, hl, out);
+        moni_free(h);
         if (a.csv) {          // -c: <sam>.csv (align_reads_dispatcher.hpp:302,334-339), header of aligner::to_csv (aligner_ksw2.hpp:3230-3234)
             out2 = fopen((sam_filename + ".csv").c_str(), "w");
             if (!out2) die("open() file " + sam_filename + ".csv failed");
@@ -1318,6 +1360,13 @@ int main(int argc, char** argv) {
                 if (moni_align_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &d.a, &d.la, &st)) die("moni_align_batch failed");
                 n_al = st.aligned;
             }
+            if (a.bgzf) {          // the batch's text through this worker's context; a copy of the blocks waits for the writer (the pinned buffer is the context's next call's)
+                const char* z; uint64_t zl;
+                bgzf_blocks(C, d.a, d.la, false, &z, &zl);
+                moni_free(d.a);
+                d.a = (char*)malloc(zl + 1); if (!d.a) die("out of memory");
+                memcpy(d.a, z, zl); d.la = zl;
+            }
             const size_t n_reads = b.n();
             delete it.b;
             const double a1 = now();
@@ -1335,6 +1384,7 @@ int main(int argc, char** argv) {
     for (auto& t : th) t.join();
     { std::lock_guard<std::mutex> lk(mu_out); workers_done = true; cv_out.notify_all(); }
     writer.join();
+    if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
     close_out(out);
     close_out(out2);
     delete zrd;
