@@ -15,30 +15,24 @@ static int approx_params_ok(const moni_approx_params_t* p) {
 
 static int approx_run_resident(moni_ctx* c, const moni_approx_params_t* prm) {
     moni_index* I = c->idx;
-    HIPCHK(hipSetDevice(I->device));
-    if (c->h_blk.empty()) return MONI_EINVAL;          // no batch was made resident
+    SearchDims D; int rc;
+    if ((rc = search_dims(c, prm->strands, D))) return rc;
     auto& B = c->apx;
     B.valid = false;
-    const uint64_t nr = c->n_reads, n_pack = 2 * nr, n_tasks = nr * prm->strands;
+    const uint64_t nr = D.nr, n_tasks = D.n_tasks;
+    const unsigned task_grid = D.task_grid;
     if (prm->max_hits && n_tasks > (~0ull >> 8) / prm->max_hits) return MONI_ENOMEM;          // the hit region's size in bytes does not fit 62 bits
     const uint64_t n_slots = n_tasks * prm->max_hits;
     const uint64_t ck_bound = prm->k ? prm->strands * (c->total_len / prm->chunk_len) + n_tasks : 0;      // sum of ceil(m / chunk_len) at most
-    int rc;
-    if ((rc = B.slots.ensure(n_slots + 1)) || (rc = c->pat.ensure(c->h_blk.back().y + 1)) || (rc = c->pflag.ensure(n_pack + 8)) || (rc = B.res.ensure(n_tasks + 1)) ||
-        (rc = B.cnt.ensure(n_tasks + 2)) || (rc = B.ck_off.ensure(n_tasks + 2)) || (rc = B.hit_off.ensure(n_tasks + 2)) || (rc = B.ckpt.ensure(ck_bound + 1))) {
-        (void)hipGetLastError();          // (a refused allocation is reported by the return value alone)
-        return rc;
-    }
+    if ((rc = B.slots.ensure(n_slots + 1)) || (rc = B.res.ensure(n_tasks + 1)) || (rc = B.cnt.ensure(n_tasks + 2)) || (rc = B.ck_off.ensure(n_tasks + 2)) ||
+        (rc = B.hit_off.ensure(n_tasks + 2)) || (rc = B.ckpt.ensure(ck_bound + 1)))
+        return refused(rc);
+    if ((rc = search_pack(c, D))) return rc;          // (before A: it places the patterns' workspace)
     apx_args_t A;
     A.rows = I->d_rows.p; A.frows = I->d_frows.p; A.cr = I->d_cr.p; A.recs = I->d_recs.p; A.pat = c->pat.p; A.offs = c->offs.p; A.blk = c->blk.p;
     A.strands = prm->strands; A.k = prm->k; A.max_hits = prm->max_hits; A.max_occ = prm->max_occ; A.chunk_len = prm->chunk_len; A.max_steps = prm->max_steps;
     A.res = B.res.p; A.slots = B.slots.p;
-    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
-    rec(c, EV_ALL0);
-    const unsigned task_grid = (unsigned)((n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK);          // (one thread more than tasks: it closes the counts for the scans)
     if (nr) {
-        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_pack + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, c->seq.p, c->offs.p, c->blk.p, n_pack,
-                           c->pat.p, c->pflag.p);
         if (prm->k) {
             hipLaunchKernelGGL(approx_plan_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, c->offs.p, n_tasks, prm->strands, prm->chunk_len, B.cnt.p);
             HIPCHK(hipGetLastError());
@@ -67,7 +61,7 @@ static int approx_run_resident(moni_ctx* c, const moni_approx_params_t* prm) {
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     if (n_hits) {
-        if ((rc = B.hits.ensure(n_hits + 1)) || (rc = B.occ_cnt.ensure(n_hits + 2)) || (rc = B.occ_off.ensure(n_hits + 2))) return rc;
+        if ((rc = B.hits.ensure(n_hits + 1)) || (rc = B.occ_cnt.ensure(n_hits + 2)) || (rc = B.occ_off.ensure(n_hits + 2))) return refused(rc);
         hipLaunchKernelGGL(approx_gather_kernel, dim3((unsigned)((n_slots + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, n_tasks, prm->max_hits, B.res.p, B.hit_off.p,
                            prm->max_occ ? 1u : 0u, B.slots.p, B.hits.p, B.occ_cnt.p);
         HIPCHK(hipGetLastError());
@@ -80,7 +74,7 @@ static int approx_run_resident(moni_ctx* c, const moni_approx_params_t* prm) {
     rec(c, EV_PC1);
     rec(c, EV_PE0);
     if (n_occ) {
-        if ((rc = B.pos.ensure(n_occ)) || (rc = B.seq.ensure(n_occ)) || (rc = B.seq_off.ensure(n_occ))) return rc;
+        if ((rc = B.pos.ensure(n_occ)) || (rc = B.seq.ensure(n_occ)) || (rc = B.seq_off.ensure(n_occ))) return refused(rc);
         phi_tab_t P; P.recs = I->d_phi.p; P.dir = I->d_phi_dir.p;
         hipLaunchKernelGGL(approx_walk_kernel, dim3((unsigned)((n_hits + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, P, I->d_seq_starts.p, n_hits, B.hits.p,
                            B.occ_off.p, B.pos.p, B.seq.p, B.seq_off.p, c->d_counters.p);
@@ -149,21 +143,14 @@ int moni_approx_batch(moni_ctx_t* c, const moni_read_batch_t* b, const moni_appr
     if (!b->n_reads) return MONI_OK;
     if ((rc = approx_run_resident(c, prm))) return rc;
     const uint64_t nh = c->apx.n_hits, n = c->apx.n_occ;
-    moni_approx_hit_t* hh = nullptr; uint64_t* hp = nullptr; uint32_t* hs = nullptr; uint64_t* ho = nullptr;
-    if (nh && hits) { hh = (moni_approx_hit_t*)malloc(nh * sizeof(moni_approx_hit_t)); if (!hh) rc = MONI_ENOMEM; }
-    if (n && hh) {
-        if (pos) hp = (uint64_t*)malloc(n * sizeof(uint64_t));
-        if (seq) hs = (uint32_t*)malloc(n * sizeof(uint32_t));
-        if (seq_off) ho = (uint64_t*)malloc(n * sizeof(uint64_t));
-        if ((pos && !hp) || (seq && !hs) || (seq_off && !ho)) rc = MONI_ENOMEM;
-    }
-    if (!rc) rc = moni_approx_fetch(c, res, hh, hp, hs, ho);
-    if (rc) { free(hh); free(hp); free(hs); free(ho); return rc; }
-    if (hits) *hits = hh;
-    if (pos) *pos = hp;
-    if (seq) *seq = hs;
-    if (seq_off) *seq_off = ho;
+    HostArrays H;
+    moni_approx_hit_t* hh = H.want(hits, nh);          // without the hits their positions have no owner: none is fetched
+    const uint64_t np = hh ? n : 0;
+    uint64_t* hp = H.want(pos, np); uint32_t* hs = H.want(seq, np); uint64_t* ho = H.want(seq_off, np);
+    if (!H.ok) return MONI_ENOMEM;
+    if ((rc = moni_approx_fetch(c, res, hh, hp, hs, ho))) return rc;
+    H.release();
     if (n_hits_kept) *n_hits_kept = hh ? nh : 0;
-    if (n_occ) *n_occ = hh ? n : 0;
+    if (n_occ) *n_occ = np;
     return MONI_OK;
 }

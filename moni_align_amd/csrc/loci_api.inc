@@ -24,66 +24,51 @@ static int loci_sort(moni_ctx* c, uint64_t* in, uint64_t* out, uint64_t n, unsig
 
 static int loci_run_resident(moni_ctx* c, const moni_loci_params_t* prm) {
     moni_index* I = c->idx;
-    HIPCHK(hipSetDevice(I->device));
-    if (c->h_blk.empty()) return MONI_EINVAL;          // no batch was made resident
+    SearchDims D; int rc;
+    if ((rc = search_dims(c, prm->strands, D))) return rc;
     auto& B = c->loci;
     B.valid = false;
-    const uint64_t nr = c->n_reads, n_pack = 2 * nr, n_tasks = nr * prm->strands;
+    const uint64_t nr = D.nr, n_tasks = D.n_tasks;
+    const unsigned task_grid = D.task_grid;
     if (n_tasks > LOCI_MAX_TASKS) return MONI_ERANGE;
-    int rc;
-    if ((rc = c->pat.ensure(c->h_blk.back().y + 1)) || (rc = c->pflag.ensure(n_pack + 8)) || (rc = B.lres.ensure(n_tasks + 1)) || (rc = B.toe.ensure(n_tasks + 1)) ||
-        (rc = B.cnt.ensure(n_tasks + 2)) || (rc = B.off.ensure(n_tasks + 2)) || (rc = B.occ_off.ensure(n_tasks + 2)) || (rc = B.sres.ensure(n_tasks + 1)) ||
-        (rc = B.k_lo.ensure(n_tasks + 1)) || (rc = B.res.ensure(n_tasks + 1))) {
-        (void)hipGetLastError();          // (a refused allocation is reported by the return value alone)
-        return rc;
-    }
-    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
-    rec(c, EV_ALL0);
-    const unsigned task_grid = (unsigned)((n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK);          // (one thread more than tasks: it closes the counts for the scan)
-    if (nr)
-        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_pack + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, c->seq.p, c->offs.p, c->blk.p, n_pack,
-                           c->pat.p, c->pflag.p);
-    rec(c, EV_MS0);
-    if (nr)
-        hipLaunchKernelGGL(count_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p,
-                           n_tasks, prm->strands, 0u, B.lres.p, B.toe.p, B.cnt.p, c->d_counters.p);
-    rec(c, EV_MS1);
-    HIPCHK(hipGetLastError());
+    if ((rc = B.s.ensure(n_tasks)) || (rc = B.occ_off.ensure(n_tasks + 2)) || (rc = B.sres.ensure(n_tasks + 1)) || (rc = B.k_lo.ensure(n_tasks + 1)) || (rc = B.res.ensure(n_tasks + 1)))
+        return refused(rc);
+    if ((rc = search_pack(c, D)) || (rc = search_count(c, D, prm->strands, 0u, B.s))) return rc;
     rec(c, EV_PC0);
     uint64_t totals[2] = {0, 0};          // walked occurrences, segments
     if (nr) {
-        hipLaunchKernelGGL(seqcount_plan_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_rows.p, n_tasks, prm->max_walk, B.lres.p, B.sres.p, B.k_lo.p, B.cnt.p);
+        hipLaunchKernelGGL(seqcount_plan_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_rows.p, n_tasks, prm->max_walk, B.s.res.p, B.sres.p, B.k_lo.p, B.s.cnt.p);
         HIPCHK(hipGetLastError());
-        if ((rc = exclusive_scan_u64(c, B.cnt.p, B.off.p, n_tasks + 1))) return rc;
-        hipLaunchKernelGGL(loci_plan_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, n_tasks, B.sres.p, B.off.p, B.cnt.p, B.occ_off.p);
+        if ((rc = exclusive_scan_u64(c, B.s.cnt.p, B.s.off.p, n_tasks + 1))) return rc;
+        hipLaunchKernelGGL(loci_plan_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, n_tasks, B.sres.p, B.s.off.p, B.s.cnt.p, B.occ_off.p);
         HIPCHK(hipGetLastError());
-        if ((rc = exclusive_scan_u64(c, B.cnt.p, B.occ_off.p, n_tasks + 1))) return rc;
+        if ((rc = exclusive_scan_u64(c, B.s.cnt.p, B.occ_off.p, n_tasks + 1))) return rc;
         HIPCHK(hipMemcpyAsync(totals, B.occ_off.p + n_tasks, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     const uint64_t total = totals[0], n_segs = totals[1];
     if (prm->max_total && total > prm->max_total) return MONI_ENOMEM;          // nothing of the result was written
     if (total) {
-        if ((rc = B.keys.ensure(total + 2)) || (rc = B.sorted.ensure(total + 2)) || (rc = B.idx.ensure(total + 2))) { (void)hipGetLastError(); return rc; }
+        if ((rc = B.keys.ensure(total + 2)) || (rc = B.sorted.ensure(total + 2)) || (rc = B.idx.ensure(total + 2))) return refused(rc);
         phi_tab_t P; P.recs = I->d_phi.p; P.dir = I->d_phi_dir.p;
         loci_lift_t T; T.pdir = I->d_pdir.p; T.seqs = I->d_lift_seqs.p; T.runs = I->d_lift_runs.p; T.n_text = I->K.n - 1; T.n_seq = I->K.n_seq;
         const uint64_t blocks = (n_segs + MS_BLOCK - 1) / MS_BLOCK;
         hipLaunchKernelGGL(loci_walk_kernel, dim3((unsigned)std::min<uint64_t>(blocks, SC_MAX_GRID)), dim3(MS_BLOCK), 0, c->stream, I->K, P, T, I->d_rows.p, I->d_cr.p, I->d_recs.p,
-                           n_tasks, n_segs, prm->lift, B.sres.p, B.toe.p, B.k_lo.p, B.off.p, B.occ_off.p, B.keys.p, c->d_counters.p);
+                           n_tasks, n_segs, prm->lift, B.sres.p, B.s.toe.p, B.k_lo.p, B.s.off.p, B.occ_off.p, B.keys.p, c->d_counters.p);
         HIPCHK(hipGetLastError());
     }
     rec(c, EV_PC1);
     rec(c, EV_PE0);
     uint64_t n_loci = 0;
     if (total) {
-        if ((rc = loci_sort(c, B.keys.p, B.sorted.p, total, loci_key_bits(n_tasks)))) { (void)hipGetLastError(); return rc; }
+        if ((rc = loci_sort(c, B.keys.p, B.sorted.p, total, loci_key_bits(n_tasks)))) return refused(rc);
         const unsigned key_grid = (unsigned)((total + 1 + MS_BLOCK - 1) / MS_BLOCK);
         hipLaunchKernelGGL(loci_head_kernel, dim3(key_grid), dim3(MS_BLOCK), 0, c->stream, B.sorted.p, total, B.keys.p);
         HIPCHK(hipGetLastError());
         if ((rc = exclusive_scan_u64(c, B.keys.p, B.idx.p, total + 1))) return rc;
         HIPCHK(hipMemcpyAsync(&n_loci, B.idx.p + total, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        if ((rc = B.lpos.ensure(n_loci)) || (rc = B.lseq.ensure(n_loci)) || (rc = B.lseq_off.ensure(n_loci)) || (rc = B.support.ensure(n_loci))) { (void)hipGetLastError(); return rc; }
+        if ((rc = B.lpos.ensure(n_loci)) || (rc = B.lseq.ensure(n_loci)) || (rc = B.lseq_off.ensure(n_loci)) || (rc = B.support.ensure(n_loci))) return refused(rc);
         hipLaunchKernelGGL(loci_emit_kernel, dim3(key_grid), dim3(MS_BLOCK), 0, c->stream, B.sorted.p, total, B.idx.p, I->d_seq_starts.p, I->K.n_seq, B.lpos.p, B.lseq.p, B.lseq_off.p,
                            B.keys.p);
     }
@@ -135,20 +120,11 @@ int moni_loci_batch(moni_ctx_t* c, const moni_read_batch_t* b, const moni_loci_p
     if (!b->n_reads) return MONI_OK;
     if ((rc = loci_run_resident(c, prm))) return rc;
     const uint64_t n = c->loci.n_loci;
-    uint64_t* hp = nullptr; uint32_t* hs = nullptr; uint64_t* ho = nullptr; uint64_t* hu = nullptr;
-    if (n) {
-        if (lpos) hp = (uint64_t*)malloc(n * sizeof(uint64_t));
-        if (lseq) hs = (uint32_t*)malloc(n * sizeof(uint32_t));
-        if (lseq_off) ho = (uint64_t*)malloc(n * sizeof(uint64_t));
-        if (support) hu = (uint64_t*)malloc(n * sizeof(uint64_t));
-        if ((lpos && !hp) || (lseq && !hs) || (lseq_off && !ho) || (support && !hu)) rc = MONI_ENOMEM;
-    }
-    if (!rc) rc = moni_loci_fetch(c, res, hp, hs, ho, hu);
-    if (rc) { free(hp); free(hs); free(ho); free(hu); return rc; }
-    if (lpos) *lpos = hp;
-    if (lseq) *lseq = hs;
-    if (lseq_off) *lseq_off = ho;
-    if (support) *support = hu;
+    HostArrays H;
+    uint64_t* hp = H.want(lpos, n); uint32_t* hs = H.want(lseq, n); uint64_t* ho = H.want(lseq_off, n); uint64_t* hu = H.want(support, n);
+    if (!H.ok) return MONI_ENOMEM;
+    if ((rc = moni_loci_fetch(c, res, hp, hs, ho, hu))) return rc;
+    H.release();
     if (n_loci) *n_loci = n;
     return MONI_OK;
 }

@@ -123,6 +123,10 @@ struct ResidentBatch {      // a batch of reads in HBM: the one a context works 
     std::vector<uint8_t> h_seq;              // host copy of the batch (SAM SEQ, MD/NM)
     std::vector<uint64_t> h_offs;
 };
+struct SearchBufs {         // the exact-search stage of a pattern query (count_kernel): per task its record and toehold, the counts a scan takes and that scan; grow-only
+    DBuf<moni_locate_res_t> res; DBuf<uint64_t> toe, cnt, off;
+    int ensure(uint64_t n_tasks) { int rc; return (rc = res.ensure(n_tasks + 1)) || (rc = toe.ensure(n_tasks + 1)) || (rc = cnt.ensure(n_tasks + 2)) || (rc = off.ensure(n_tasks + 2)) ? rc : MONI_OK; }
+};
 struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
     moni_index* idx = nullptr;
     Stream stream;
@@ -221,14 +225,14 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
         DBuf<moni_screen_res_t> res; uint64_t n_reads = 0; bool valid = false;
     } scr;
     struct LocBufs {        // exact-match count / locate (locate_api.inc): the last run's results, on the device until moni_locate_fetch; grow-only
-        DBuf<moni_locate_res_t> res; DBuf<uint64_t> toe, cnt, off, pos, seq_off; DBuf<uint32_t> seq; uint64_t n_tasks = 0, n_occ = 0; bool valid = false;
+        SearchBufs s; DBuf<uint64_t> pos, seq_off; DBuf<uint32_t> seq; uint64_t n_tasks = 0, n_occ = 0; bool valid = false;
     } loc;
     struct ScBufs {         // sequence counts (seqcount_api.inc): the last run's records and table, on the device until moni_seqcount_fetch; grow-only
-        DBuf<moni_locate_res_t> lres; DBuf<moni_seqcount_res_t> res; DBuf<uint64_t> toe, cnt, off, counts; DBuf<uint32_t> k_lo;
+        SearchBufs s; DBuf<moni_seqcount_res_t> res; DBuf<uint64_t> counts; DBuf<uint32_t> k_lo;
         uint64_t n_tasks = 0, n_segs = 0; uint32_t n_seq = 0; bool valid = false;
     } sc;
     struct LociBufs {       // reference loci (loci_api.inc): the last run's records and loci, on the device until moni_loci_fetch; grow-only
-        DBuf<moni_locate_res_t> lres; DBuf<moni_seqcount_res_t> sres; DBuf<moni_loci_res_t> res; DBuf<uint64_t> toe, cnt, off, occ_off, keys, sorted, idx, lpos, lseq_off, support;
+        SearchBufs s; DBuf<moni_seqcount_res_t> sres; DBuf<moni_loci_res_t> res; DBuf<uint64_t> occ_off, keys, sorted, idx, lpos, lseq_off, support;
         DBuf<uint32_t> k_lo, lseq; DBuf<uint8_t> sort_tmp;
         uint64_t n_tasks = 0, n_loci = 0, n_segs = 0; bool valid = false;
     } loci;
@@ -272,6 +276,59 @@ int exclusive_scan_u64(moni_ctx* c, uint64_t* in, uint64_t* out, size_t n) {
 }
 
 inline void rec(moni_ctx* c, int e) { (void)hipEventRecord(c->ev[e], c->stream); c->ev_valid[e] = true; }
+
+// ---- what the pattern queries share (locate_api.inc, seqcount_api.inc, loci_api.inc, approx_api.inc) ----
+inline int refused(int rc) { (void)hipGetLastError(); return rc; }          // a refused allocation is reported by the return value alone: the HIP error it left is cleared
+
+struct SearchDims { uint64_t nr, n_pack, n_tasks; unsigned task_grid; };      // task_grid: one thread more than tasks (it closes the counts for the scans)
+
+// A run begins on the resident batch: the device is set, and without a batch there is nothing to search.
+int search_dims(moni_ctx* c, uint32_t strands, SearchDims& D) {
+    HIPCHK(hipSetDevice(c->idx->device));
+    if (c->h_blk.empty()) return MONI_EINVAL;          // no batch was made resident
+    D.nr = c->n_reads; D.n_pack = 2 * D.nr; D.n_tasks = D.nr * strands;
+    D.task_grid = (unsigned)((D.n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK);
+    return MONI_OK;
+}
+
+// Once the run's own buffers stand: the workspace of the patterns, the counters cleared, EV_ALL0, pack_kernel.  EV_MS0 is the caller's (search_count).
+int search_pack(moni_ctx* c, const SearchDims& D) {
+    moni_index* I = c->idx;
+    int rc;
+    if ((rc = c->pat.ensure(c->h_blk.back().y + 1)) || (rc = c->pflag.ensure(D.n_pack + 8))) return refused(rc);
+    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    rec(c, EV_ALL0);
+    if (D.nr)
+        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((D.n_pack + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, c->seq.p, c->offs.p, c->blk.p, D.n_pack,
+                           c->pat.p, c->pflag.p);
+    return MONI_OK;
+}
+
+// The exact search of every task between EV_MS0 and EV_MS1 (max_occ 0: the search alone).
+int search_count(moni_ctx* c, const SearchDims& D, uint32_t strands, uint32_t max_occ, SearchBufs& S) {
+    moni_index* I = c->idx;
+    rec(c, EV_MS0);
+    if (D.nr)
+        hipLaunchKernelGGL(count_kernel, dim3(D.task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p,
+                           D.n_tasks, strands, max_occ, S.res.p, S.toe.p, S.cnt.p, c->d_counters.p);
+    rec(c, EV_MS1);
+    HIPCHK(hipGetLastError());
+    return MONI_OK;
+}
+
+// The host arrays a *_batch wrapper hands to its caller: malloc'ed where an out-pointer asks for one, all freed again unless released to those.
+struct HostArrays {
+    void* p[4] = {}; void* out[4] = {}; int k = 0; bool ok = true;
+    template <class T> T* want(T** o, uint64_t n) {          // null where not asked for, or empty
+        if (!o || !n) return nullptr;
+        T* a = (T*)malloc(n * sizeof(T));
+        if (!a) ok = false;
+        p[k] = a; out[k++] = o;
+        return a;
+    }
+    void release() { for (int i = 0; i < k; ++i) memcpy(out[i], &p[i], sizeof(void*)); k = 0; }
+    ~HostArrays() { for (int i = 0; i < k; ++i) free(p[i]); }
+};
 
 }  // namespace
 

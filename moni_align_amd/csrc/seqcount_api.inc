@@ -14,39 +14,23 @@ static int seqcount_params_ok(const moni_seqcount_params_t* p) { return p && (p-
 
 static int seqcount_run_resident(moni_ctx* c, const moni_seqcount_params_t* prm) {
     moni_index* I = c->idx;
-    HIPCHK(hipSetDevice(I->device));
-    if (c->h_blk.empty()) return MONI_EINVAL;          // no batch was made resident
+    SearchDims D; int rc;
+    if ((rc = search_dims(c, prm->strands, D))) return rc;
     auto& B = c->sc;
     B.valid = false;
-    const uint64_t nr = c->n_reads, n_pack = 2 * nr, n_tasks = nr * prm->strands, n_seq = I->K.n_seq;
+    const uint64_t nr = D.nr, n_tasks = D.n_tasks, n_seq = I->K.n_seq;
+    const unsigned task_grid = D.task_grid;
     if (n_seq && n_tasks > (~0ull >> 4) / n_seq) return MONI_ENOMEM;          // the table's size in bytes does not fit 60 bits
     const uint64_t n_cells = n_tasks * n_seq;
-    int rc;
-    if ((rc = c->pat.ensure(c->h_blk.back().y + 1)) || (rc = c->pflag.ensure(n_pack + 8)) || (rc = B.lres.ensure(n_tasks + 1)) || (rc = B.toe.ensure(n_tasks + 1)) ||
-        (rc = B.cnt.ensure(n_tasks + 2)) || (rc = B.off.ensure(n_tasks + 2)) || (rc = B.res.ensure(n_tasks + 1)) || (rc = B.k_lo.ensure(n_tasks + 1)) ||
-        (rc = B.counts.ensure(n_cells + 1))) {
-        (void)hipGetLastError();          // (a refused allocation is reported by the return value alone)
-        return rc;
-    }
-    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
-    rec(c, EV_ALL0);
-    const unsigned task_grid = (unsigned)((n_tasks + 1 + MS_BLOCK - 1) / MS_BLOCK);          // (one thread more than tasks: it closes the counts for the scan)
-    if (nr)
-        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_pack + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, c->seq.p, c->offs.p, c->blk.p, n_pack,
-                           c->pat.p, c->pflag.p);
-    rec(c, EV_MS0);
-    if (nr)
-        hipLaunchKernelGGL(count_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_tables.p, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p,
-                           n_tasks, prm->strands, 0u, B.lres.p, B.toe.p, B.cnt.p, c->d_counters.p);
-    rec(c, EV_MS1);
-    HIPCHK(hipGetLastError());
+    if ((rc = B.s.ensure(n_tasks)) || (rc = B.res.ensure(n_tasks + 1)) || (rc = B.k_lo.ensure(n_tasks + 1)) || (rc = B.counts.ensure(n_cells + 1))) return refused(rc);
+    if ((rc = search_pack(c, D)) || (rc = search_count(c, D, prm->strands, 0u, B.s))) return rc;
     rec(c, EV_PC0);
     uint64_t total = 0;
     if (nr) {
-        hipLaunchKernelGGL(seqcount_plan_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_rows.p, n_tasks, prm->max_walk, B.lres.p, B.res.p, B.k_lo.p, B.cnt.p);
+        hipLaunchKernelGGL(seqcount_plan_kernel, dim3(task_grid), dim3(MS_BLOCK), 0, c->stream, I->K, I->d_rows.p, n_tasks, prm->max_walk, B.s.res.p, B.res.p, B.k_lo.p, B.s.cnt.p);
         HIPCHK(hipGetLastError());
-        if ((rc = exclusive_scan_u64(c, B.cnt.p, B.off.p, n_tasks + 1))) return rc;
-        HIPCHK(hipMemcpyAsync(&total, B.off.p + n_tasks, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        if ((rc = exclusive_scan_u64(c, B.s.cnt.p, B.s.off.p, n_tasks + 1))) return rc;
+        HIPCHK(hipMemcpyAsync(&total, B.s.off.p + n_tasks, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         if (n_cells) HIPCHK(hipMemsetAsync(B.counts.p, 0, n_cells * sizeof(uint64_t), c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
@@ -54,7 +38,7 @@ static int seqcount_run_resident(moni_ctx* c, const moni_seqcount_params_t* prm)
         phi_tab_t P; P.recs = I->d_phi.p; P.dir = I->d_phi_dir.p;
         const uint64_t blocks = (total + MS_BLOCK - 1) / MS_BLOCK;
         hipLaunchKernelGGL(seqcount_walk_kernel, dim3((unsigned)std::min<uint64_t>(blocks, SC_MAX_GRID)), dim3(MS_BLOCK), 0, c->stream, I->K, P, I->d_rows.p, I->d_cr.p, I->d_recs.p,
-                           I->d_seq_starts.p, n_tasks, total, B.res.p, B.toe.p, B.k_lo.p, B.off.p, (unsigned long long*)B.counts.p, c->d_counters.p);
+                           I->d_seq_starts.p, n_tasks, total, B.res.p, B.s.toe.p, B.k_lo.p, B.s.off.p, (unsigned long long*)B.counts.p, c->d_counters.p);
         hipLaunchKernelGGL(seqcount_finish_kernel, dim3((unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, (uint32_t)n_seq, n_tasks,
                            (const unsigned long long*)B.counts.p, B.res.p);
     }

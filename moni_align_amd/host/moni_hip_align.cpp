@@ -788,6 +788,288 @@ static int run_paired(Args& a, const std::string& sam_filename) {
     return 0;
 }
 
+// ---- the single-end modes of the queue path -------------------------------------------------------------------------------------------
+struct Done { char* a = nullptr; uint64_t la = 0; std::string b; };      // a batch's output - a: a malloc'ed block (the library's, or give()'s); b: a second stream (.lengths, .csv)
+typedef std::vector<std::string> Names;
+// A mode's worker: the library call on batch b (rb: as the library takes it; its first read is number `first` of the input) and the text of its results into d; returns the batch's count for the summary line.
+typedef size_t RunFn(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t first, Args& a, const Names& seq_names, Done& d);
+
+static void give(Done& d, const std::string& s) { d.a = (char*)malloc(s.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, s.data(), s.size()); d.la = s.size(); }
+static void put_name(std::string& sa, const Batch& b, size_t r) { sa.append((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r])); }
+
+// One line per pattern lo .. hi - 1 and strand: name, strand, what line(task) writes (tasks count from lo); returns the patterns for which it said "occurs" on a strand.
+template <class F>
+static size_t task_lines(std::string& sa, const Batch& b, size_t lo, size_t hi, uint32_t strands, F line) {
+    size_t n = 0;
+    for (size_t r = lo; r < hi; ++r) {
+        bool occurs = false;
+        for (uint32_t s = 0; s < strands; ++s) {
+            put_name(sa, b, r);
+            sa += s ? "\t-\t" : "\t+\t";
+            if (line((r - lo) * strands + s)) occurs = true;
+            sa.push_back('\n');
+        }
+        if (occurs) ++n;
+    }
+    return n;
+}
+
+// seq:pos[,seq:pos...] of entries off .. off + n - 1 of the lists a call returned (`total` entries; su: each followed by :support)
+static void put_positions(std::string& sa, const Names& seq_names, const uint32_t* sq, const uint64_t* so, const uint64_t* su, uint64_t off, uint64_t n, uint64_t total, const char* call) {
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint64_t o = off + k;
+        if (o >= total || sq[o] >= seq_names.size()) die(std::string(call) + " returned a position outside the index");
+        if (k) sa.push_back(',');
+        sa += seq_names[sq[o]]; sa.push_back(':'); sa += std::to_string(so[o] + 1);
+        if (su) { sa.push_back(':'); sa += std::to_string(su[o]); }
+    }
+}
+
+static size_t run_ms(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t, Args& a, const Names&, Done& d) {          // --ms / --mems
+    std::vector<uint64_t> ptr(b.seq.size() + 1), len(b.seq.size() + 1);
+    if (a.split) {
+        moni_mslong_params_t sp; moni_mslong_params_default(&sp);
+        if (a.seg_len_set) sp.seg_len = a.seg_len;
+        if (a.overlap_set) sp.overlap = a.overlap;
+        const int sr = moni_ms_long_batch(C, &rb, &sp, ptr.data(), len.data(), nullptr);
+        if (sr) die("moni_ms_long_batch failed (" + std::to_string(sr) + ")");
+    } else if (moni_ms_lengths_batch(C, &rb, ptr.data(), len.data())) die("moni_ms_lengths_batch failed");
+    std::string sa, sb;
+    for (size_t r = 0; r < b.n(); ++r) {
+        const std::string hdr = ">" + std::string((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r])) + "\n";
+        sa += hdr;
+        const size_t o = b.off[r], m = b.off[r + 1] - o;
+        if (a.legacy_ms) {          // matching_statistics.cpp:565-600: values followed by a blank, one line per read
+            sb += hdr;
+            for (size_t k = 0; k < m; ++k) { sa += std::to_string(ptr[o + k]); sa.push_back(' '); sb += std::to_string(len[o + k]); sb.push_back(' '); }
+            sb.push_back('\n');
+        } else {                    // mems.cpp:241-262, 585-590: (offset,length) of every position whose length does not drop
+            for (size_t k = 0; k < m; ++k) if (k == 0 || len[o + k] >= len[o + k - 1]) { sa += "(" + std::to_string(k) + "," + std::to_string(len[o + k]) + ") "; }
+        }
+        sa.push_back('\n');
+    }
+    give(d, sa); d.b = std::move(sb);
+    return 0;
+}
+
+static size_t run_pseudo_ms(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t first, Args& a, const Names&, Done& d) {       // run_spumoni.cpp:495-498: ">" + the read's running number, then the lengths, each followed by a blank
+    std::vector<uint32_t> len(b.seq.size() + 1), hits(b.n() + 1);
+    const int pr = moni_pml_batch(C, &rb, a.P.min_len, len.data(), nullptr, hits.data());
+    if (pr) die("moni_pml_batch failed (" + std::to_string(pr) + ")");
+    std::string sa;
+    sa.reserve(b.seq.size() * 3 + b.n() * 12);
+    char num[24];
+    size_t n_al = 0;
+    for (size_t r = 0; r < b.n(); ++r) {
+        sa.push_back('>'); sa += std::to_string(first + r); sa.push_back('\n');
+        const size_t o = b.off[r], m = b.off[r + 1] - o;
+        for (size_t k = 0; k < m; ++k) { const int nc = snprintf(num, sizeof num, "%u ", len[o + k]); sa.append(num, (size_t)nc); }
+        sa.push_back('\n');
+        if (hits[r]) ++n_al;          // reads with a length >= -l somewhere
+    }
+    give(d, sa);
+    return n_al;
+}
+
+static size_t run_screen(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t, Args& a, const Names&, Done& d) {          // one line per read: name, length, call, strand, scored windows, then per strand positive windows, largest D, largest length
+    std::vector<moni_screen_res_t> res(b.n() + 1);
+    const int sr = moni_screen_batch(C, &rb, &a.SP, res.data());
+    if (sr) die("moni_screen_batch failed (" + std::to_string(sr) + ")");
+    std::string sa;
+    sa.reserve(b.n() * 64 + b.names.size());
+    char num[128];
+    size_t n_al = 0;
+    for (size_t r = 0; r < b.n(); ++r) {
+        const moni_screen_res_t& R = res[r];
+        const bool present = (R.flags & MONI_SCREEN_PRESENT) != 0;
+        put_name(sa, b, r);
+        const int nc = snprintf(num, sizeof num, "\t%llu\t%c\t%c\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", (unsigned long long)(b.off[r + 1] - b.off[r]),
+                                (R.flags & MONI_SCREEN_SHORT) ? 'S' : present ? 'P' : 'A', !present ? '.' : (R.flags & MONI_SCREEN_STRAND1) ? '-' : '+', R.n_win, R.n_pos[0],
+                                R.n_pos[1], R.d_max[0], R.d_max[1], R.max_pml[0], R.max_pml[1]);
+        sa.append(num, (size_t)nc);
+        if (present) ++n_al;
+    }
+    give(d, sa);
+    return n_al;
+}
+
+static size_t run_locate(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t, Args& a, const Names& seq_names, Done& d) {          // per pattern and strand: count, bytes matched, the occurrences kept
+    moni_locate_params_t lp; moni_locate_params_default(&lp);
+    lp.strands = a.both_strands ? 2 : 1; lp.max_occ = a.max_occ;
+    std::vector<moni_locate_res_t> res(b.n() * lp.strands + 1);
+    uint32_t* sq = nullptr; uint64_t* so = nullptr; uint64_t n_occ = 0;
+    const int lr = moni_locate_batch(C, &rb, &lp, res.data(), nullptr, &sq, &so, &n_occ);
+    if (lr) die("moni_locate_batch failed (" + std::to_string(lr) + ")");
+    std::string sa;
+    const size_t n_al = task_lines(sa, b, 0, b.n(), lp.strands, [&](size_t t) {
+        const moni_locate_res_t& R = res[t];
+        sa += std::to_string(R.count); sa.push_back('\t'); sa += std::to_string(R.matched); sa.push_back('\t');
+        if (!R.n_occ) sa.push_back('*');
+        put_positions(sa, seq_names, sq, so, nullptr, R.occ_off, R.n_occ, n_occ, "moni_locate_batch");
+        return R.count != 0;
+    });
+    moni_free(sq); moni_free(so);
+    give(d, sa);
+    return n_al;
+}
+
+static size_t run_seq_count(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t, Args& a, const Names& seq_names, Done& d) {       // per pattern and strand: count, bytes matched, sequences that hold it, their counts
+    moni_seqcount_params_t sp; moni_seqcount_params_default(&sp);
+    sp.strands = a.both_strands ? 2 : 1; sp.max_walk = a.max_walk;
+    const size_t n_seq = seq_names.size(), n_tasks = b.n() * sp.strands;
+    std::vector<moni_seqcount_res_t> res(n_tasks + 1);
+    std::vector<uint64_t> counts(n_tasks * n_seq + 1);
+    const int sr = moni_seqcount_batch(C, &rb, &sp, res.data(), counts.data());
+    if (sr) die("moni_seqcount_batch failed (" + std::to_string(sr) + ")");
+    std::string sa;
+    const size_t n_al = task_lines(sa, b, 0, b.n(), sp.strands, [&](size_t t) {
+        const moni_seqcount_res_t& R = res[t];
+        sa += std::to_string(R.count); sa.push_back('\t'); sa += std::to_string(R.matched); sa.push_back('\t'); sa += std::to_string(R.n_seqs); sa.push_back('\t');
+        if (!R.walked) sa.push_back('?');
+        else if (!R.n_seqs) sa.push_back('*');
+        else {
+            bool first = true;
+            for (size_t q = 0; q < n_seq; ++q) {
+                const uint64_t v = counts[t * n_seq + q];
+                if (!v) continue;
+                if (!first) sa.push_back(',');
+                first = false;
+                sa += seq_names[q]; sa.push_back(':'); sa += std::to_string(v);
+            }
+        }
+        return R.count != 0;
+    });
+    give(d, sa);
+    return n_al;
+}
+
+static size_t run_loci(moni_ctx_t* C, Batch& b, const moni_read_batch_t&, size_t, Args& a, const Names& seq_names, Done& d) {          // per pattern and strand: count, bytes matched, loci, each locus with its support
+    moni_loci_params_t lp; moni_loci_params_default(&lp);
+    lp.strands = a.both_strands ? 2 : 1; lp.max_walk = a.max_walk; lp.lift = a.no_lift ? 0 : 1;
+    std::string sa;
+    std::vector<moni_loci_res_t> res;
+    size_t n_al = 0;
+    // a batch whose occurrences do not fit the library's bound (MONI_ENOMEM) is run in halves, in order
+    std::function<void(size_t, size_t)> part = [&](size_t lo, size_t hi) {
+        const size_t n = hi - lo;
+        moni_read_batch_t sub{b.seq.data(), b.off.data() + lo, n};
+        res.assign(n * lp.strands + 1, moni_loci_res_t());
+        uint32_t* sq = nullptr; uint64_t* so = nullptr; uint64_t* su = nullptr; uint64_t n_loci = 0;
+        const int lr = moni_loci_batch(C, &sub, &lp, res.data(), nullptr, &sq, &so, &su, &n_loci);
+        if (lr == MONI_ENOMEM && n > 1) { part(lo, lo + n / 2); part(lo + n / 2, hi); return; }
+        if (lr == MONI_ENOMEM) die("--loci: the occurrences of one pattern do not fit in memory; lower --max-walk");
+        if (lr) die("moni_loci_batch failed (" + std::to_string(lr) + ")");
+        n_al += task_lines(sa, b, lo, hi, lp.strands, [&](size_t t) {
+            const moni_loci_res_t& R = res[t];
+            sa += std::to_string(R.count); sa.push_back('\t'); sa += std::to_string(R.matched); sa.push_back('\t'); sa += std::to_string(R.n_loci); sa.push_back('\t');
+            if (!R.walked) sa.push_back('?');
+            else if (!R.n_loci) sa.push_back('*');
+            put_positions(sa, seq_names, sq, so, su, R.loci_off, R.n_loci, n_loci, "moni_loci_batch");
+            return R.count != 0;
+        });
+        moni_free(sq); moni_free(so); moni_free(su);
+    };
+    if (b.n()) part(0, b.n());
+    give(d, sa);
+    return n_al;
+}
+
+static size_t run_approx(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t, Args& a, const Names& seq_names, Done& d) {          // per pattern and strand: complete, the counts per distance, the matching strings, those kept
+    moni_approx_params_t ap; moni_approx_params_default(&ap);
+    ap.strands = a.both_strands ? 2 : 1; ap.k = a.approx_k; ap.max_hits = a.max_hits; ap.max_occ = a.max_occ; ap.max_steps = a.max_steps;
+    std::vector<moni_approx_res_t> res(b.n() * ap.strands + 1);
+    moni_approx_hit_t* hits = nullptr; uint32_t* sq = nullptr; uint64_t* so = nullptr; uint64_t n_hits = 0, n_occ = 0;
+    const int ar = moni_approx_batch(C, &rb, &ap, res.data(), &hits, nullptr, &sq, &so, &n_hits, &n_occ);
+    if (ar) die("moni_approx_batch failed (" + std::to_string(ar) + ")");
+    std::string sa;
+    const size_t n_al = task_lines(sa, b, 0, b.n(), ap.strands, [&](size_t t) {
+        const moni_approx_res_t& R = res[t];
+        sa += std::to_string(R.complete); sa.push_back('\t');
+        for (uint32_t e = 0; e <= ap.k; ++e) { if (e) sa.push_back(','); sa += std::to_string(R.cnt[e]); }
+        sa.push_back('\t'); sa += std::to_string(R.n_hits); sa.push_back('\t');
+        if (!R.n_kept) sa.push_back('*');
+        for (uint32_t j = 0; j < R.n_kept; ++j) {
+            if (R.hit_off + j >= n_hits) die("moni_approx_batch returned a hit outside its list");
+            const moni_approx_hit_t& H = hits[R.hit_off + j];
+            if (j) sa.push_back(';');
+            sa += std::to_string(H.n_mis); sa.push_back(':'); sa += std::to_string(H.count); sa.push_back(':');
+            if (!H.n_occ) sa.push_back('*');
+            put_positions(sa, seq_names, sq, so, nullptr, H.occ_off, H.n_occ, n_occ, "moni_approx_batch");
+        }
+        return R.n_hits != 0;
+    });
+    moni_free(hits); moni_free(sq); moni_free(so);
+    give(d, sa);
+    return n_al;
+}
+
+static size_t run_extend(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t, Args& a, const Names&, Done& d) {          // extender::config_t from the flags it shares with the aligner (-l -L -A -B -O -E)
+    moni_extend_params_t xp; moni_extend_params_default(&xp);
+    xp.min_len = a.P.min_len; xp.ext_len = a.P.ext_len; xp.smatch = a.P.smatch; xp.smismatch = a.P.smismatch; xp.gapo = a.P.gapo; xp.gape = a.P.gape;
+    moni_extend_stats_t st;
+    const int xr = moni_extend_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &xp, &d.a, &d.la, &st);
+    if (xr) die("moni_extend_batch failed (" + std::to_string(xr) + ")");
+    return st.extended;
+}
+
+static size_t run_report_mems(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t, Args& a, const Names&, Done& d) {          // -m
+    if (moni_report_mems_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &d.a, &d.la)) die("moni_report_mems_batch failed");
+    return b.n();
+}
+
+static size_t run_csv(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t, Args& a, const Names&, Done& d) {          // -c
+    moni_align_stats_t st; char* cs = nullptr; uint64_t cl = 0;
+    if (moni_align_csv_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &d.a, &d.la, &cs, &cl, &st)) die("moni_align_csv_batch failed");
+    d.b.assign(cs, cl); moni_free(cs);
+    return st.aligned;
+}
+
+static size_t run_align(moni_ctx_t* C, Batch& b, const moni_read_batch_t& rb, size_t, Args& a, const Names&, Done& d) {          // plain alignment: no entry of the table
+    moni_align_stats_t st;
+    if (moni_align_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &d.a, &d.la, &st)) die("moni_align_batch failed");
+    return st.aligned;
+}
+
+// The table.  At most one of the modes past --mems is set (main refuses the rest), and the first set entry is the mode that runs.
+// id: the flag's bit in `older`, the flags a mode refuses to be combined with; they are named in the bits' order, which is the order the flags came to be.
+enum : unsigned { O_M = 1, O_C = 2, O_MS = 4, O_MEMS = 8, O_EXTEND = 16, O_PSEUDO_MS = 32, O_LOCATE = 64, O_SEQ_COUNT = 128, O_LOCI = 256, O_APPROX = 512, O_SCREEN = 1024 };
+enum Strands { S_NONE, S_BOTH, S_ONE };          // what --dry-run says of the strands: nothing, 2 with --both-strands, 1 with --one-strand
+struct Mode {
+    const char* flag;          // as spelled in messages
+    unsigned id, older;
+    bool Args::*set;
+    const char* suffix; const char* suffix2;          // of the output file(s); with one, the output is named <patterns>_<index> by default; without, the mode writes SAM
+    const char* dry; Strands strands;                 // --dry-run: mode=...
+    bool seq_names;                                   // its lines name the index's sequences
+    const char* label;                                // of the summary line
+    RunFn* run;
+};
+static const char L_ALIGNED[] = "Number of aligned reads: ", L_OCCUR[] = "Number of patterns that occur: ";
+static const Mode MODES[] = {
+    {"--ms", O_MS, 0, &Args::legacy_ms, ".pointers", ".lengths", nullptr, S_NONE, false, L_ALIGNED, run_ms},
+    {"--mems", O_MEMS, 0, &Args::legacy_mems, ".mems", nullptr, nullptr, S_NONE, false, L_ALIGNED, run_ms},
+    {"--pseudo-ms", O_PSEUDO_MS, O_PSEUDO_MS - 1, &Args::pseudo_ms, ".pseudo_lengths", nullptr, "pseudo-ms", S_NONE, false, "Number of reads with a pseudo-matching length >= -l: ", run_pseudo_ms},
+    {"--screen", O_SCREEN, O_SCREEN - 1, &Args::screen, ".screen", nullptr, "screen", S_ONE, false, "Number of reads called present: ", run_screen},
+    {"--locate", O_LOCATE, O_LOCATE - 1, &Args::locate, ".locate", nullptr, "locate", S_BOTH, true, L_OCCUR, run_locate},
+    {"--seq-count", O_SEQ_COUNT, O_SEQ_COUNT - 1, &Args::seq_count, ".seqcount", nullptr, "seq-count", S_BOTH, true, L_OCCUR, run_seq_count},
+    {"--loci", O_LOCI, (O_LOCI - 1) | O_APPROX, &Args::loci, ".loci", nullptr, "loci", S_BOTH, true, L_OCCUR, run_loci},
+    {"--approx", O_APPROX, O_LOCI - 1, &Args::approx, ".approx", nullptr, "approx", S_BOTH, true, L_OCCUR, run_approx},          // (it does not name --loci: --loci names it)
+    {"--extend", O_EXTEND, O_EXTEND - 1, &Args::extend, nullptr, nullptr, "extend", S_NONE, false, "Number of extended reads: ", run_extend},          // (extend_reads_dispatcher.hpp:478)
+    {"-m", O_M, 0, &Args::report_mems, nullptr, nullptr, nullptr, S_NONE, false, L_ALIGNED, run_report_mems},
+    {"-c", O_C, 0, &Args::csv, nullptr, nullptr, nullptr, S_NONE, false, L_ALIGNED, run_csv},
+};
+
+// Mode `id`, if set: single-end input, and none of the older flags it refuses beside it (the first of them in their order is the one named).
+static bool mode_alone(const Args& a, unsigned id, bool paired) {
+    const Mode* M = nullptr;
+    for (const Mode& m : MODES) if (m.id == id) M = &m;
+    if (!(a.*M->set)) return false;
+    if (paired) die(std::string(M->flag) + " takes single-end input (-p), not -1 / -2");
+    for (unsigned bit = 1; bit < O_SCREEN; bit <<= 1)
+        for (const Mode& o : MODES) if ((M->older & bit) && o.id == bit && a.*o.set) die(std::string(M->flag) + " cannot be combined with " + o.flag);
+    return true;
+}
+
 int main(int argc, char** argv) {
     // HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues; every context runs its launches on several streams (the paired
     // path on ~11), and streams that share a queue run one after the other
@@ -806,82 +1088,22 @@ int main(int argc, char** argv) {
     if (a.split && !(a.legacy_ms || a.legacy_mems)) die("--split belongs to --ms / --mems");
     if ((a.seg_len_set || a.overlap_set) && !a.split) die("--seg-len / --overlap belong to --split");
     if (a.seg_len_set && a.seg_len < 8) die("--seg-len must be at least 8");
-    if (a.pseudo_ms) {       // pseudo-matching lengths: single-end reads, one mode at a time
-        if (paired) die("--pseudo-ms takes single-end input (-p), not -1 / -2");
-        if (a.report_mems) die("--pseudo-ms cannot be combined with -m");
-        if (a.csv) die("--pseudo-ms cannot be combined with -c");
-        if (a.legacy_ms) die("--pseudo-ms cannot be combined with --ms");
-        if (a.legacy_mems) die("--pseudo-ms cannot be combined with --mems");
-        if (a.extend) die("--pseudo-ms cannot be combined with --extend");
-    }
-    if (a.screen) {          // read screening: single-end reads, one mode at a time
-        if (paired) die("--screen takes single-end input (-p), not -1 / -2");
-        if (a.report_mems) die("--screen cannot be combined with -m");
-        if (a.csv) die("--screen cannot be combined with -c");
-        if (a.legacy_ms) die("--screen cannot be combined with --ms");
-        if (a.legacy_mems) die("--screen cannot be combined with --mems");
-        if (a.extend) die("--screen cannot be combined with --extend");
-        if (a.pseudo_ms) die("--screen cannot be combined with --pseudo-ms");
-        if (a.locate) die("--screen cannot be combined with --locate");
-        if (a.seq_count) die("--screen cannot be combined with --seq-count");
-        if (a.loci) die("--screen cannot be combined with --loci");
-        if (a.approx) die("--screen cannot be combined with --approx");
+    // one mode at a time: the modes' checks in the order that decides which message a wrong combination gets; between them, the options that belong to one mode
+    mode_alone(a, O_PSEUDO_MS, paired);
+    if (mode_alone(a, O_SCREEN, paired)) {
         a.SP.strands = a.one_strand ? 1 : 2;
         if (a.SP.window < 8 || a.SP.window > 65535) die("--window takes 8 to 65535");
         if (a.SP.min_win < 1 || a.SP.min_win > a.SP.window) die("--min-win takes 1 to --window");
         if (a.SP.ks_num < 1 || a.SP.ks_num > a.SP.ks_den || a.SP.ks_den > 65535) die("--ks takes NUM/DEN with 1 <= NUM <= DEN <= 65535");
     } else if (a.screen_opt) die("--window / --min-win / --ks / --one-strand belong to --screen");
-    if (a.locate) {          // exact-match count and locate: single-end patterns, one mode at a time
-        if (paired) die("--locate takes single-end input (-p), not -1 / -2");
-        if (a.report_mems) die("--locate cannot be combined with -m");
-        if (a.csv) die("--locate cannot be combined with -c");
-        if (a.legacy_ms) die("--locate cannot be combined with --ms");
-        if (a.legacy_mems) die("--locate cannot be combined with --mems");
-        if (a.extend) die("--locate cannot be combined with --extend");
-        if (a.pseudo_ms) die("--locate cannot be combined with --pseudo-ms");
-    } else if (!a.approx && ((a.both_strands && !a.seq_count && !a.loci) || a.max_occ)) die("--max-occ / --both-strands belong to --locate");
-    if (a.seq_count) {       // per-sequence occurrence counts: single-end patterns, one mode at a time
-        if (paired) die("--seq-count takes single-end input (-p), not -1 / -2");
-        if (a.report_mems) die("--seq-count cannot be combined with -m");
-        if (a.csv) die("--seq-count cannot be combined with -c");
-        if (a.legacy_ms) die("--seq-count cannot be combined with --ms");
-        if (a.legacy_mems) die("--seq-count cannot be combined with --mems");
-        if (a.extend) die("--seq-count cannot be combined with --extend");
-        if (a.pseudo_ms) die("--seq-count cannot be combined with --pseudo-ms");
-        if (a.locate) die("--seq-count cannot be combined with --locate");
-    } else if (a.max_walk_set && !a.loci) die("--max-walk belongs to --seq-count / --loci");
-    if (a.loci) {            // reference loci: single-end patterns, one mode at a time
-        if (paired) die("--loci takes single-end input (-p), not -1 / -2");
-        if (a.report_mems) die("--loci cannot be combined with -m");
-        if (a.csv) die("--loci cannot be combined with -c");
-        if (a.legacy_ms) die("--loci cannot be combined with --ms");
-        if (a.legacy_mems) die("--loci cannot be combined with --mems");
-        if (a.extend) die("--loci cannot be combined with --extend");
-        if (a.pseudo_ms) die("--loci cannot be combined with --pseudo-ms");
-        if (a.locate) die("--loci cannot be combined with --locate");
-        if (a.seq_count) die("--loci cannot be combined with --seq-count");
-        if (a.approx) die("--loci cannot be combined with --approx");
-    } else if (a.no_lift) die("--no-lift belongs to --loci");
-    if (a.approx) {          // k-mismatch count and locate: single-end patterns, one mode at a time
-        if (a.approx_k > MONI_APPROX_MAX_K) die("--approx takes 0 to " + std::to_string(MONI_APPROX_MAX_K) + " mismatches");
-        if (paired) die("--approx takes single-end input (-p), not -1 / -2");
-        if (a.report_mems) die("--approx cannot be combined with -m");
-        if (a.csv) die("--approx cannot be combined with -c");
-        if (a.legacy_ms) die("--approx cannot be combined with --ms");
-        if (a.legacy_mems) die("--approx cannot be combined with --mems");
-        if (a.extend) die("--approx cannot be combined with --extend");
-        if (a.pseudo_ms) die("--approx cannot be combined with --pseudo-ms");
-        if (a.locate) die("--approx cannot be combined with --locate");
-        if (a.seq_count) die("--approx cannot be combined with --seq-count");
+    if (!mode_alone(a, O_LOCATE, paired) && !a.approx && ((a.both_strands && !a.seq_count && !a.loci) || a.max_occ)) die("--max-occ / --both-strands belong to --locate");
+    if (!mode_alone(a, O_SEQ_COUNT, paired) && a.max_walk_set && !a.loci) die("--max-walk belongs to --seq-count / --loci");
+    if (!mode_alone(a, O_LOCI, paired) && a.no_lift) die("--no-lift belongs to --loci");
+    if (a.approx && a.approx_k > MONI_APPROX_MAX_K) die("--approx takes 0 to " + std::to_string(MONI_APPROX_MAX_K) + " mismatches");
+    if (mode_alone(a, O_APPROX, paired)) {
         if (a.max_occ && !a.max_hits) die("--approx: --max-occ needs --max-hits above 0");
     } else if (a.max_hits_set || a.max_steps_set) die("--max-hits / --max-steps belong to --approx");
-    if (a.extend) {          // extend mode: single-end reads, one mode at a time
-        if (paired) die("--extend takes single-end input (-p), not -1 / -2");
-        if (a.report_mems) die("--extend cannot be combined with -m");
-        if (a.csv) die("--extend cannot be combined with -c");
-        if (a.legacy_ms) die("--extend cannot be combined with --ms");
-        if (a.legacy_mems) die("--extend cannot be combined with --mems");
-    }
+    mode_alone(a, O_EXTEND, paired);
     if (a.bgzf) {            // BGZF output: the modes that write SAM
         if (a.csv) die("--bgzf cannot be combined with -c");
         if (a.dry_write) die("--bgzf cannot be combined with --dry-run-write");
@@ -903,7 +1125,9 @@ int main(int argc, char** argv) {
     if (a.bgzf) sam_filename += ".gz";
     if (paired) return run_paired(a, sam_filename);
     const bool legacy = a.legacy_ms || a.legacy_mems;
-    if ((legacy || a.pseudo_ms || a.screen || a.locate || a.seq_count || a.loci || a.approx) && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate / .seqcount)
+    const Mode* M = nullptr;          // the mode that runs; none: plain alignment
+    for (const Mode& m : MODES) if (a.*m.set) { M = &m; break; }
+    if (M && M->suffix && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate / .seqcount)
     info("Output file: " + sam_filename);
     MappedReader mrd;
     const bool mapped = mrd.open(a.patterns);
@@ -913,13 +1137,19 @@ int main(int argc, char** argv) {
         Batch b; size_t n = 0, bases = 0;
         while (next_record(b)) { ++n; }
         bases = b.seq.size();
+        std::string mode;
+        if (M && M->dry) {
+            mode = std::string(" mode=") + M->dry;
+            if (M->id == O_APPROX) mode += " k=" + std::to_string(a.approx_k);
+            if (M->strands) mode += (M->strands == S_ONE ? !a.one_strand : a.both_strands) ? " strands=2" : " strands=1";
+        }
         printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", a.extend ? " mode=extend" : (a.pseudo_ms ? " mode=pseudo-ms" : a.screen ? (a.one_strand ? " mode=screen strands=1" : " mode=screen strands=2") : (a.locate ? (a.both_strands ? " mode=locate strands=2" : " mode=locate strands=1") : (a.seq_count ? (a.both_strands ? " mode=seq-count strands=2" : " mode=seq-count strands=1") : (a.loci ? (a.both_strands ? " mode=loci strands=2" : " mode=loci strands=1") : (a.approx ? (" mode=approx k=" + std::to_string(a.approx_k) + (a.both_strands ? " strands=2" : " strands=1")).c_str() : ""))))), a.bgzf ? " bgzf=1" : "");
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), a.bgzf ? " bgzf=1" : "");
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
-    const bool fast = mapped && !legacy && !a.report_mems && !a.csv && !a.extend && !a.pseudo_ms && !a.screen && !a.locate && !a.seq_count && !a.loci && !a.approx && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
+    const bool fast = mapped && !M && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
     const int per_gpu = legacy ? 1 : (fast ? a.ctx_per_gpu : 2);                      // contexts (batches in flight) per GPU
     std::vector<moni_index_t*> idx(a.gpus, nullptr);
     std::vector<moni_ctx_t*> ctx((size_t)a.gpus * per_gpu, nullptr);
@@ -1034,15 +1264,11 @@ int main(int argc, char** argv) {
     }
     if (a.dry_write) return 0;
     FILE* out = nullptr; FILE* out2 = nullptr;
-    if (a.legacy_ms) { out = fopen((sam_filename + ".pointers").c_str(), "w"); out2 = fopen((sam_filename + ".lengths").c_str(), "w"); if (!out || !out2) die("open() file " + sam_filename + ".pointers/.lengths failed"); }
-    else if (a.legacy_mems) { out = fopen((sam_filename + ".mems").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".mems failed"); }
-    else if (a.pseudo_ms) { out = fopen((sam_filename + ".pseudo_lengths").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".pseudo_lengths failed"); }
-    else if (a.screen) { out = fopen((sam_filename + ".screen").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".screen failed"); }
-    else if (a.locate) { out = fopen((sam_filename + ".locate").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".locate failed"); }
-    else if (a.seq_count) { out = fopen((sam_filename + ".seqcount").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".seqcount failed"); }
-    else if (a.loci) { out = fopen((sam_filename + ".loci").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".loci failed"); }
-    else if (a.approx) { out = fopen((sam_filename + ".approx").c_str(), "w"); if (!out) die("open() file " + sam_filename + ".approx failed"); }
-    else {
+    if (M && M->suffix) {
+        out = fopen((sam_filename + M->suffix).c_str(), "w");
+        if (M->suffix2) out2 = fopen((sam_filename + M->suffix2).c_str(), "w");
+        if (!out || (M->suffix2 && !out2)) die("open() file " + sam_filename + M->suffix + (M->suffix2 ? std::string("/") + M->suffix2 : "") + " failed");
+    } else {
         out = fopen(sam_filename.c_str(), "w");
         if (!out) die("open() file " + sam_filename + " failed");
         char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
@@ -1055,8 +1281,8 @@ int main(int argc, char** argv) {
             put(hdr, sizeof hdr - 1, out2);
         }
     }
-    std::vector<std::string> seq_names;          // --locate / --seq-count: the sequences' names, from the header's @SQ lines (one per sequence of the concatenation, in order)
-    if (a.locate || a.seq_count || a.loci || a.approx) {
+    Names seq_names;          // the sequences' names, from the header's @SQ lines (one per sequence of the concatenation, in order)
+    if (M && M->seq_names) {
         char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
         const std::string hs(h, hl); moni_free(h);
         for (size_t at = 0; (at = hs.find("@SQ\tSN:", at)) != std::string::npos;) { at += 7; seq_names.push_back(hs.substr(at, hs.find('\t', at) - at)); }
@@ -1068,7 +1294,6 @@ int main(int argc, char** argv) {
     auto t0 = std::chrono::steady_clock::now();
     // ---- reader thread -> bounded queue of parsed batches -> workers -> bounded in-order window -> writer thread ----
     struct Item { size_t id; Batch* b; size_t first; };      // first: the running number of the batch's first read in the input
-    struct Done { char* a = nullptr; uint64_t la = 0; std::string b; };      // a: malloc'ed block of the library; b: a second stream (.lengths)
     std::mutex mu_q, mu_out;
     std::condition_variable cv_q_put, cv_q_get, cv_out, cv_window;
     std::deque<Item> queue;
@@ -1138,228 +1363,10 @@ int main(int argc, char** argv) {
                 cv_q_put.notify_one();
             }
             Batch& b = *it.b;
-            moni_read_batch_t rb{b.seq.data(), b.off.data(), b.n()};
+            const moni_read_batch_t rb{b.seq.data(), b.off.data(), b.n()};
             Done d;
-            size_t n_al = 0;
             const double a0 = now();
-            if (legacy) {
-                std::vector<uint64_t> ptr(b.seq.size() + 1), len(b.seq.size() + 1);
-                if (a.split) {
-                    moni_mslong_params_t sp; moni_mslong_params_default(&sp);
-                    if (a.seg_len_set) sp.seg_len = a.seg_len;
-                    if (a.overlap_set) sp.overlap = a.overlap;
-                    const int sr = moni_ms_long_batch(C, &rb, &sp, ptr.data(), len.data(), nullptr);
-                    if (sr) die("moni_ms_long_batch failed (" + std::to_string(sr) + ")");
-                } else if (moni_ms_lengths_batch(C, &rb, ptr.data(), len.data())) die("moni_ms_lengths_batch failed");
-                std::string sa, sb;
-                for (size_t r = 0; r < b.n(); ++r) {
-                    const std::string hdr = ">" + std::string((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r])) + "\n";
-                    sa += hdr;
-                    const size_t o = b.off[r], m = b.off[r + 1] - o;
-                    if (a.legacy_ms) {          // matching_statistics.cpp:565-600: values followed by a blank, one line per read
-                        sb += hdr;
-                        for (size_t k = 0; k < m; ++k) { sa += std::to_string(ptr[o + k]); sa.push_back(' '); sb += std::to_string(len[o + k]); sb.push_back(' '); }
-                        sb.push_back('\n');
-                    } else {                    // mems.cpp:241-262, 585-590: (offset,length) of every position whose length does not drop
-                        for (size_t k = 0; k < m; ++k) if (k == 0 || len[o + k] >= len[o + k - 1]) { sa += "(" + std::to_string(k) + "," + std::to_string(len[o + k]) + ") "; }
-                    }
-                    sa.push_back('\n');
-                }
-                d.a = (char*)malloc(sa.size() + 1); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size(); d.b = std::move(sb);
-            } else if (a.pseudo_ms) {       // run_spumoni.cpp:495-498: ">" + the read's running number, then the lengths, each followed by a blank
-                std::vector<uint32_t> len(b.seq.size() + 1), hits(b.n() + 1);
-                const int pr = moni_pml_batch(C, &rb, a.P.min_len, len.data(), nullptr, hits.data());
-                if (pr) die("moni_pml_batch failed (" + std::to_string(pr) + ")");
-                std::string sa;
-                sa.reserve(b.seq.size() * 3 + b.n() * 12);
-                char num[24];
-                for (size_t r = 0; r < b.n(); ++r) {
-                    sa.push_back('>'); sa += std::to_string(it.first + r); sa.push_back('\n');
-                    const size_t o = b.off[r], m = b.off[r + 1] - o;
-                    for (size_t k = 0; k < m; ++k) { const int nc = snprintf(num, sizeof num, "%u ", len[o + k]); sa.append(num, (size_t)nc); }
-                    sa.push_back('\n');
-                    if (hits[r]) ++n_al;          // reads with a length >= -l somewhere
-                }
-                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
-            } else if (a.screen) {          // one line per read: name, length, call, strand, scored windows, then per strand positive windows, largest D, largest length
-                std::vector<moni_screen_res_t> res(b.n() + 1);
-                const int sr = moni_screen_batch(C, &rb, &a.SP, res.data());
-                if (sr) die("moni_screen_batch failed (" + std::to_string(sr) + ")");
-                std::string sa;
-                sa.reserve(b.n() * 64 + b.names.size());
-                char num[128];
-                for (size_t r = 0; r < b.n(); ++r) {
-                    const moni_screen_res_t& R = res[r];
-                    const bool present = (R.flags & MONI_SCREEN_PRESENT) != 0;
-                    sa.append((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r]));
-                    const int nc = snprintf(num, sizeof num, "\t%llu\t%c\t%c\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", (unsigned long long)(b.off[r + 1] - b.off[r]),
-                                            (R.flags & MONI_SCREEN_SHORT) ? 'S' : present ? 'P' : 'A', !present ? '.' : (R.flags & MONI_SCREEN_STRAND1) ? '-' : '+', R.n_win, R.n_pos[0],
-                                            R.n_pos[1], R.d_max[0], R.d_max[1], R.max_pml[0], R.max_pml[1]);
-                    sa.append(num, (size_t)nc);
-                    if (present) ++n_al;
-                }
-                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
-            } else if (a.locate) {          // one line per pattern and strand: name, strand, count, bytes matched, the occurrences kept
-                moni_locate_params_t lp; moni_locate_params_default(&lp);
-                lp.strands = a.both_strands ? 2 : 1; lp.max_occ = a.max_occ;
-                std::vector<moni_locate_res_t> res(b.n() * lp.strands + 1);
-                uint32_t* sq = nullptr; uint64_t* so = nullptr; uint64_t n_occ = 0;
-                const int lr = moni_locate_batch(C, &rb, &lp, res.data(), nullptr, &sq, &so, &n_occ);
-                if (lr) die("moni_locate_batch failed (" + std::to_string(lr) + ")");
-                std::string sa;
-                for (size_t r = 0; r < b.n(); ++r) {
-                    bool occurs = false;
-                    for (uint32_t s = 0; s < lp.strands; ++s) {
-                        const moni_locate_res_t& R = res[r * lp.strands + s];
-                        sa.append((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r]));
-                        sa += s ? "\t-\t" : "\t+\t";
-                        sa += std::to_string(R.count); sa.push_back('\t'); sa += std::to_string(R.matched); sa.push_back('\t');
-                        if (!R.n_occ) sa.push_back('*');
-                        for (uint32_t k = 0; k < R.n_occ; ++k) {
-                            const uint64_t o = R.occ_off + k;
-                            if (o >= n_occ || sq[o] >= seq_names.size()) die("moni_locate_batch returned a position outside the index");
-                            if (k) sa.push_back(',');
-                            sa += seq_names[sq[o]]; sa.push_back(':'); sa += std::to_string(so[o] + 1);
-                        }
-                        sa.push_back('\n');
-                        occurs = occurs || R.count;
-                    }
-                    if (occurs) ++n_al;
-                }
-                moni_free(sq); moni_free(so);
-                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
-            } else if (a.seq_count) {       // one line per pattern and strand: name, strand, count, bytes matched, sequences that hold it, their counts
-                moni_seqcount_params_t sp; moni_seqcount_params_default(&sp);
-                sp.strands = a.both_strands ? 2 : 1; sp.max_walk = a.max_walk;
-                const size_t n_seq = seq_names.size(), n_tasks = b.n() * sp.strands;
-                std::vector<moni_seqcount_res_t> res(n_tasks + 1);
-                std::vector<uint64_t> counts(n_tasks * n_seq + 1);
-                const int sr = moni_seqcount_batch(C, &rb, &sp, res.data(), counts.data());
-                if (sr) die("moni_seqcount_batch failed (" + std::to_string(sr) + ")");
-                std::string sa;
-                for (size_t r = 0; r < b.n(); ++r) {
-                    bool occurs = false;
-                    for (uint32_t s = 0; s < sp.strands; ++s) {
-                        const size_t t = r * sp.strands + s;
-                        const moni_seqcount_res_t& R = res[t];
-                        sa.append((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r]));
-                        sa += s ? "\t-\t" : "\t+\t";
-                        sa += std::to_string(R.count); sa.push_back('\t'); sa += std::to_string(R.matched); sa.push_back('\t'); sa += std::to_string(R.n_seqs); sa.push_back('\t');
-                        if (!R.walked) sa.push_back('?');
-                        else if (!R.n_seqs) sa.push_back('*');
-                        else {
-                            bool first = true;
-                            for (size_t q = 0; q < n_seq; ++q) {
-                                const uint64_t v = counts[t * n_seq + q];
-                                if (!v) continue;
-                                if (!first) sa.push_back(',');
-                                first = false;
-                                sa += seq_names[q]; sa.push_back(':'); sa += std::to_string(v);
-                            }
-                        }
-                        sa.push_back('\n');
-                        occurs = occurs || R.count;
-                    }
-                    if (occurs) ++n_al;
-                }
-                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
-            } else if (a.loci) {            // one line per pattern and strand: name, strand, count, bytes matched, loci, each locus with its support
-                moni_loci_params_t lp; moni_loci_params_default(&lp);
-                lp.strands = a.both_strands ? 2 : 1; lp.max_walk = a.max_walk; lp.lift = a.no_lift ? 0 : 1;
-                std::string sa;
-                std::vector<moni_loci_res_t> res;
-                // a batch whose occurrences do not fit the library's bound (MONI_ENOMEM) is run in halves, in order
-                std::function<void(size_t, size_t)> part = [&](size_t lo, size_t hi) {
-                    const size_t n = hi - lo;
-                    moni_read_batch_t sub{b.seq.data(), b.off.data() + lo, n};
-                    res.assign(n * lp.strands + 1, moni_loci_res_t());
-                    uint32_t* sq = nullptr; uint64_t* so = nullptr; uint64_t* su = nullptr; uint64_t n_loci = 0;
-                    const int lr = moni_loci_batch(C, &sub, &lp, res.data(), nullptr, &sq, &so, &su, &n_loci);
-                    if (lr == MONI_ENOMEM && n > 1) { part(lo, lo + n / 2); part(lo + n / 2, hi); return; }
-                    if (lr == MONI_ENOMEM) die("--loci: the occurrences of one pattern do not fit in memory; lower --max-walk");
-                    if (lr) die("moni_loci_batch failed (" + std::to_string(lr) + ")");
-                    for (size_t r = lo; r < hi; ++r) {
-                        bool occurs = false;
-                        for (uint32_t s = 0; s < lp.strands; ++s) {
-                            const moni_loci_res_t& R = res[(r - lo) * lp.strands + s];
-                            sa.append((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r]));
-                            sa += s ? "\t-\t" : "\t+\t";
-                            sa += std::to_string(R.count); sa.push_back('\t'); sa += std::to_string(R.matched); sa.push_back('\t'); sa += std::to_string(R.n_loci); sa.push_back('\t');
-                            if (!R.walked) sa.push_back('?');
-                            else if (!R.n_loci) sa.push_back('*');
-                            for (uint64_t k = 0; k < R.n_loci; ++k) {
-                                const uint64_t o = R.loci_off + k;
-                                if (o >= n_loci || sq[o] >= seq_names.size()) die("moni_loci_batch returned a position outside the index");
-                                if (k) sa.push_back(',');
-                                sa += seq_names[sq[o]]; sa.push_back(':'); sa += std::to_string(so[o] + 1); sa.push_back(':'); sa += std::to_string(su[o]);
-                            }
-                            sa.push_back('\n');
-                            occurs = occurs || R.count;
-                        }
-                        if (occurs) ++n_al;
-                    }
-                    moni_free(sq); moni_free(so); moni_free(su);
-                };
-                if (b.n()) part(0, b.n());
-                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
-            } else if (a.approx) {          // one line per pattern and strand: name, strand, complete, the counts per distance, the matching strings, those kept
-                moni_approx_params_t ap; moni_approx_params_default(&ap);
-                ap.strands = a.both_strands ? 2 : 1; ap.k = a.approx_k; ap.max_hits = a.max_hits; ap.max_occ = a.max_occ; ap.max_steps = a.max_steps;
-                std::vector<moni_approx_res_t> res(b.n() * ap.strands + 1);
-                moni_approx_hit_t* hits = nullptr; uint32_t* sq = nullptr; uint64_t* so = nullptr; uint64_t n_hits = 0, n_occ = 0;
-                const int ar = moni_approx_batch(C, &rb, &ap, res.data(), &hits, nullptr, &sq, &so, &n_hits, &n_occ);
-                if (ar) die("moni_approx_batch failed (" + std::to_string(ar) + ")");
-                std::string sa;
-                for (size_t r = 0; r < b.n(); ++r) {
-                    bool occurs = false;
-                    for (uint32_t s = 0; s < ap.strands; ++s) {
-                        const moni_approx_res_t& R = res[r * ap.strands + s];
-                        sa.append((const char*)b.names.data() + b.name_off[r], (size_t)(b.name_off[r + 1] - b.name_off[r]));
-                        sa += s ? "\t-\t" : "\t+\t";
-                        sa += std::to_string(R.complete); sa.push_back('\t');
-                        for (uint32_t e = 0; e <= ap.k; ++e) { if (e) sa.push_back(','); sa += std::to_string(R.cnt[e]); }
-                        sa.push_back('\t'); sa += std::to_string(R.n_hits); sa.push_back('\t');
-                        if (!R.n_kept) sa.push_back('*');
-                        for (uint32_t j = 0; j < R.n_kept; ++j) {
-                            if (R.hit_off + j >= n_hits) die("moni_approx_batch returned a hit outside its list");
-                            const moni_approx_hit_t& H = hits[R.hit_off + j];
-                            if (j) sa.push_back(';');
-                            sa += std::to_string(H.n_mis); sa.push_back(':'); sa += std::to_string(H.count); sa.push_back(':');
-                            if (!H.n_occ) sa.push_back('*');
-                            for (uint32_t k = 0; k < H.n_occ; ++k) {
-                                const uint64_t o = H.occ_off + k;
-                                if (o >= n_occ || sq[o] >= seq_names.size()) die("moni_approx_batch returned a position outside the index");
-                                if (k) sa.push_back(',');
-                                sa += seq_names[sq[o]]; sa.push_back(':'); sa += std::to_string(so[o] + 1);
-                            }
-                        }
-                        sa.push_back('\n');
-                        occurs = occurs || R.n_hits;
-                    }
-                    if (occurs) ++n_al;
-                }
-                moni_free(hits); moni_free(sq); moni_free(so);
-                d.a = (char*)malloc(sa.size() + 1); if (!d.a) die("out of memory"); memcpy(d.a, sa.data(), sa.size()); d.la = sa.size();
-            } else if (a.extend) {          // extender::config_t from the flags it shares with the aligner (-l -L -A -B -O -E)
-                moni_extend_params_t xp; moni_extend_params_default(&xp);
-                xp.min_len = a.P.min_len; xp.ext_len = a.P.ext_len; xp.smatch = a.P.smatch; xp.smismatch = a.P.smismatch; xp.gapo = a.P.gapo; xp.gape = a.P.gape;
-                moni_extend_stats_t st;
-                const int xr = moni_extend_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &xp, &d.a, &d.la, &st);
-                if (xr) die("moni_extend_batch failed (" + std::to_string(xr) + ")");
-                n_al = st.extended;
-            } else if (a.report_mems) {
-                if (moni_report_mems_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &d.a, &d.la)) die("moni_report_mems_batch failed");
-                n_al = b.n();
-            } else if (a.csv) {
-                moni_align_stats_t st; char* cs = nullptr; uint64_t cl = 0;
-                if (moni_align_csv_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &d.a, &d.la, &cs, &cl, &st)) die("moni_align_csv_batch failed");
-                d.b.assign(cs, cl); moni_free(cs);
-                n_al = st.aligned;
-            } else {
-                moni_align_stats_t st;
-                if (moni_align_batch(C, &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &d.a, &d.la, &st)) die("moni_align_batch failed");
-                n_al = st.aligned;
-            }
+            const size_t n_al = (M ? M->run : run_align)(C, b, rb, it.first, a, seq_names, d);
             if (a.bgzf) {          // the batch's text through this worker's context; a copy of the blocks waits for the writer (the pinned buffer is the context's next call's)
                 const char* z; uint64_t zl;
                 bgzf_blocks(C, d.a, d.la, false, &z, &zl);
@@ -1389,7 +1396,7 @@ int main(int argc, char** argv) {
     close_out(out2);
     delete zrd;
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    info(std::string(a.extend ? "Number of extended reads: " : a.pseudo_ms ? "Number of reads with a pseudo-matching length >= -l: " : a.screen ? "Number of reads called present: " : (a.locate || a.seq_count || a.loci || a.approx) ? "Number of patterns that occur: " : "Number of aligned reads: ") + std::to_string(aligned) + "/" + std::to_string(processed));      // (extend_reads_dispatcher.hpp:478)
+    info(std::string(M ? M->label : L_ALIGNED) + std::to_string(aligned) + "/" + std::to_string(processed));
     info("Elapsed time (s): " + std::to_string(el));
     info("Reads per second: " + std::to_string(processed / (el > 0 ? el : 1)));
     info("Stage busy seconds: reader (parse) " + std::to_string(t_reader) + ", library calls summed over " + std::to_string(ctx.size()) + " workers " + std::to_string(t_align) +

@@ -283,3 +283,99 @@ def test_cli_csv_mem_statistics(exe, medium_case, tmp_path):
     assert open(out + ".csv", "rb").read() == hdr + csv
     body = open(out, "rb").read()
     assert body.endswith(sam) and body[:3] == b"@HD"
+
+
+# ---- the modes' combination rules -------------------------------------------------------------------------------------------------------
+# A model of main()'s checks, written from the rule and not from the binary: the blocks of the modes are visited in BLOCKS' order; a block that
+# is set first refuses paired input, then names the first flag of its own list (the flags older than the mode, in the order they came) that is set too.
+OLDER = ["-m", "-c", "--ms", "--mems", "--extend", "--pseudo-ms", "--locate", "--seq-count", "--loci", "--approx"]
+REFUSES = {"--pseudo-ms": OLDER[:5], "--screen": OLDER, "--locate": OLDER[:6], "--seq-count": OLDER[:7], "--loci": OLDER[:8] + ["--approx"],
+           "--approx": OLDER[:8], "--extend": OLDER[:4]}
+BLOCKS = ["--pseudo-ms", "--screen", "--locate", "--seq-count", "--loci", "--approx", "--extend"]
+MODE_FLAGS = OLDER + ["--screen"]
+
+
+def expected_refusal(flags, paired=False):
+    for blk in BLOCKS:
+        if blk in flags:
+            if paired:
+                return "%s takes single-end input (-p), not -1 / -2" % blk
+            for o in REFUSES[blk]:
+                if o in flags:
+                    return "%s cannot be combined with %s" % (blk, o)
+    return None
+
+
+def _argv(flags):
+    return [x for f in flags for x in ((f, "1") if f == "--approx" else (f,))]
+
+
+@pytest.fixture(scope="module")
+def four_lines(tmp_path_factory):
+    fq = str(tmp_path_factory.mktemp("modes") / "x.fq")
+    open(fq, "w").write("@a\nACGT\n+\nIIII\n")
+    return fq
+
+
+def _refused(exe, args, msg):
+    r = subprocess.run([exe, "idx/pref"] + args + ["--dry-run"], capture_output=True)
+    assert r.returncode == 1 and r.stderr == b"[ERROR] %s\n" % msg.encode(), (args, msg, r.returncode, r.stderr)
+
+
+def test_mode_pairs(exe, four_lines):
+    """every unordered pair of the eleven mode flags, in both orders on the command line: refused with the model's message, or - the pairs among
+    -m, -c, --ms, --mems, which nothing refuses - accepted"""
+    import itertools
+    n_refused = 0
+    for pair in itertools.combinations(MODE_FLAGS, 2):
+        msg = expected_refusal(pair)
+        for flags in (pair, pair[::-1]):
+            if msg:
+                _refused(exe, ["-p", four_lines] + _argv(flags), msg)
+            else:
+                assert subprocess.run([exe, "idx/pref", "-p", four_lines] + _argv(flags) + ["--dry-run"], capture_output=True).returncode == 0, flags
+        n_refused += msg is not None
+    assert n_refused == 55 - 6
+    for mode in BLOCKS:
+        _refused(exe, ["-1", four_lines, "-2", four_lines] + _argv([mode]), expected_refusal([mode], paired=True))
+
+
+def test_mode_triples(exe, four_lines):
+    """all 35 triples of the seven modes: the message is that of the first block visited, naming the oldest flag it refuses"""
+    import itertools
+    for flags in itertools.combinations(BLOCKS, 3):
+        _refused(exe, ["-p", four_lines] + _argv(flags[::-1]), expected_refusal(flags))
+    assert expected_refusal(["--loci", "--approx", "--screen"]) == "--screen cannot be combined with --loci"
+    assert expected_refusal(["--loci", "--approx"]) == "--loci cannot be combined with --approx"
+
+
+def test_orphan_options(exe, four_lines):
+    """the options of --locate, --seq-count / --loci and --approx without their mode (those of --screen, --loci, --ms / --mems and --split: test_cli_screen,
+    test_cli_loci, test_mslong_model), and the modes that lend theirs"""
+    for args, msg in ((["--max-occ", "3"], "--max-occ / --both-strands belong to --locate"), (["--both-strands"], "--max-occ / --both-strands belong to --locate"),
+                      (["--extend", "--both-strands"], "--max-occ / --both-strands belong to --locate"), (["--seq-count", "--max-occ", "3"], "--max-occ / --both-strands belong to --locate"),
+                      (["--max-walk", "5"], "--max-walk belongs to --seq-count / --loci"), (["--locate", "--max-walk", "5"], "--max-walk belongs to --seq-count / --loci"),
+                      (["--max-hits", "3"], "--max-hits / --max-steps belong to --approx"), (["--locate", "--max-steps", "3"], "--max-hits / --max-steps belong to --approx"),
+                      (["--approx", "4"], "--approx takes 0 to 3 mismatches"), (["--approx", "1", "--max-occ", "2", "--max-hits", "0"], "--approx: --max-occ needs --max-hits above 0"),
+                      (["--screen", "--window", "7"], "--window takes 8 to 65535"), (["--screen", "--min-win", "0"], "--min-win takes 1 to --window"),
+                      (["--screen", "--ks", "3/2"], "--ks takes NUM/DEN with 1 <= NUM <= DEN <= 65535")):
+        _refused(exe, ["-p", four_lines] + args, msg)
+    for args in (["--seq-count", "--both-strands", "--max-walk", "5"], ["--loci", "--both-strands", "--max-walk", "5", "--no-lift"], ["--approx", "1", "--both-strands", "--max-occ", "2", "--max-steps", "9"]):
+        assert subprocess.run([exe, "idx/pref", "-p", four_lines] + args + ["--dry-run"], capture_output=True).returncode == 0, args
+
+
+def test_dry_run_names_the_mode_and_the_output(exe, four_lines):
+    """--dry-run of every mode: the mode=... tail of its line and the output's default name (<patterns>_<index> for the modes with files of their own,
+    <patterns>_<index>_<-l>.sam for those that write SAM, .gz behind it with --bgzf) or the one -o gives"""
+    sam, own = four_lines + "_pref_30.sam", four_lines + "_pref"
+    cases = [([], sam, ""), (["-m"], sam, ""), (["-c"], sam, ""), (["--ms"], own, ""), (["--mems"], own, ""), (["--ms", "-m", "-c"], own, ""), (["--extend"], sam, " mode=extend"),
+             (["--pseudo-ms"], own, " mode=pseudo-ms"), (["--screen"], own, " mode=screen strands=2"), (["--screen", "--one-strand"], own, " mode=screen strands=1"),
+             (["--approx", "2"], own, " mode=approx k=2 strands=1"), (["--approx", "0", "--both-strands"], own, " mode=approx k=0 strands=2")]
+    for mode in ("locate", "seq-count", "loci"):
+        cases += [(["--" + mode], own, " mode=%s strands=1" % mode), (["--" + mode, "--both-strands"], own, " mode=%s strands=2" % mode)]
+    cases += [(c[0] + ["--bgzf"], c[1] + ".gz", c[2] + " bgzf=1") for c in cases[:2] + cases[6:7]]
+    for args, name, tail in cases:
+        for given in (None, "o.x"):
+            out = subprocess.check_output([exe, "idx/pref", "-p", four_lines, "-l", "30"] + args + (["-o", given] if given else []) + ["--dry-run"]).decode()
+            want = name if not given else given + (".gz" if "--bgzf" in args else "")
+            assert ("[INFO] Message: Output file: %s\n" % want) in out and out.endswith(" out=%s first=a%s\n" % (want, tail)), (args, given, out)

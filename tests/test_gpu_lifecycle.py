@@ -213,3 +213,52 @@ def test_out_buffer_regrows_and_keeps_text(small_case, monkeypatch):
         idx.close()
     assert got[0].count(b"\n") == 8 and got[1].count(b"\n") == 400 and len(got[1]) > 20 * len(got[0]) and got[2].count(b"\n") >= 300
     assert got == want
+
+
+QUERY_MODES = {          # run and fetch of the four pattern queries that share the search prologue, the patterns' workspace and the counters
+    "locate": (lambda c, s: c.locate_run(strands=s, max_occ=4), lambda c: c.locate_fetch()),
+    "seqcount": (lambda c, s: c.seqcount_run(strands=s), lambda c: c.seqcount_fetch()),
+    "loci": (lambda c, s: c.loci_run(strands=s), lambda c: c.loci_fetch()),
+    "approx": (lambda c, s: c.approx_run(strands=s, k=1, max_hits=4, max_occ=4), lambda c: c.approx_fetch()),
+}
+
+
+@pytest.mark.parametrize("strands", [1, 2])
+def test_pattern_queries_keep_to_their_own_results(small_case, strands):
+    """129 patterns on one context - 129 tasks at one strand, 258 at two: a 256-thread block and one thread, or one block and two threads - among
+    them one that occurs nowhere and one with a byte outside ACGT.  locate, seq-count, loci and approx run in two orders; after every run its
+    fetch, and after the last run of an order the fetch of all four, equal what the same mode returns in a context that ran nothing else."""
+    from moni_align_amd import capi
+    s0 = small_case.pg.seqs[0].tobytes()
+    pats = [s0[29 * k + 3: 29 * k + 3 + 16 + k % 9] for k in range(127)]
+    absent = b"ACGTTGCA" * 4
+    assert absent not in small_case.text
+    pats += [absent, s0[500:510] + b"N" + s0[511:524]]
+    seq, offs = _ragged(pats)
+    idx = capi.Index(fi=small_case.fi, device=0)
+    try:
+        want = {}
+        for name, (run, fetch) in QUERY_MODES.items():
+            ctx = capi.Ctx(idx)
+            try:
+                ctx.upload(seq, offs)
+                run(ctx, strands)
+                want[name] = fetch(ctx)
+            finally:
+                ctx.close()
+        assert len(want["locate"][0]) == 129 * strands and int(want["locate"][0]["count"][: 127 * strands: strands].min()) > 0
+        assert not want["locate"][0]["count"][127 * strands:].any() and len(want["locate"][1]) > 0 and len(want["approx"][1]) > 0
+        assert int(want["seqcount"][1].sum()) > 0 and len(want["loci"][1]) > 0
+        ctx = capi.Ctx(idx)
+        try:
+            ctx.upload(seq, offs)
+            for order in (("locate", "seqcount", "loci", "approx"), ("approx", "loci", "locate", "seqcount")):
+                for name in order:
+                    QUERY_MODES[name][0](ctx, strands)
+                    assert all(_same(g, w) for g, w in zip(QUERY_MODES[name][1](ctx), want[name])), (order, name)
+                for name in order:
+                    assert all(_same(g, w) for g, w in zip(QUERY_MODES[name][1](ctx), want[name])), (order, name, "after the order's last run")
+        finally:
+            ctx.close()
+    finally:
+        idx.close()
