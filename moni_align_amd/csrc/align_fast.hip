@@ -36,8 +36,6 @@
 #define AF_MAX_CAND 16            // chains the selection loop scores for one read (the small LDS instance holds 8)
 #define AF_PLAN_AN 96             // anchors of all those chains together (a chain's anchors are a slice of the plan's anchor pool: one long chain
                                   // or many short ones; the round-2 form gave every chain 6 slots, and 250 bp reads left the staged path for a 7th anchor)
-#define AF_FIN_AN 16              // anchors / traced problems of the final chain that finish_wave_kernel stages in LDS (beyond: read from HBM)
-#define AF_FIN_TB 12
 #define AF_MAX_READ 512          // longest read of the staged path
 #define AF_QCAP 256              // longest query of a DP task
 #define AF_TB 104                // longest target of an extension / gap problem
@@ -91,7 +89,7 @@ struct af_cand_t {               // one chain the selection loop scores (in loop
     uint32_t pad2;
 };
 static_assert(sizeof(af_cand_t) == 32, "af_cand_t");
-// the plan's 40-byte header: status, final chain, strand, traced problems, window - all finish_wave_kernel needs to start its fetches
+// the plan's 40-byte header: status, final chain, strand, traced problems, window - all finish_prep_kernel needs to start its fetches
 #define AF_PLAN_HEADER \
     uint8_t status, n_cand; uint16_t n_chains; \
     int32_t min_score; \
@@ -300,16 +298,17 @@ __device__ __forceinline__ bool af_target_exc(const af_args_t& G, const moni_dp_
     return x;
 }
 
-// The lanes that work on one read: the whole wavefront (GW = 64) or a GROUP of GW consecutive lanes (GW = 16: four reads per wavefront, each with
-// its own LDS state).  chain_plan_kernel issues mostly one-lane instructions - the selection loop, the backtracking, a lane per run of anchors - and
-// with one read per wavefront 63 of 64 lanes idle while the SIMD's issue slots are the bound (8 waves per SIMD x 0.11 VALU-active = 0.89 of the issue
-// cycles); with four reads per wavefront those sections run four wide.  Control flow is uniform within a group and may diverge between the groups of
-// a wavefront: a ballot is cut down to the group's own lanes (lanes of another group that are not at the same instruction read as 0 and are not
+// a value that is the same in every lane of the wavefront: the compiler is told so (an SGPR: scalar compares and branches, no VGPR held across the phases)
+__device__ __forceinline__ uint32_t af_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// The lanes that work on one read or sort one array (af_wave_sort): the whole wavefront (GW = 64: a read of chain_plan_kernel) or a GROUP of GW consecutive lanes (GW = 16:
+// the four reads of a wavefront of chain_runs_kernel, each with its own LDS tables).  Control flow is uniform within a group and may diverge between the
+// groups of a wavefront: a ballot is cut down to the group's own lanes (lanes of another group that are not at the same instruction read as 0 and are not
 // looked at), shuffles stay inside the group, and __syncthreads() - one wavefront per workgroup - only orders the wave's own LDS traffic.
 template <int GW>
 struct af_grp_t {
     static constexpr int W = GW;
-    static_assert(GW == 64 || GW == 32 || GW == 16, "group width");
+    static_assert(GW == 64 || GW == 16, "group width");
     int lane, base;          // lane within the group; the group's first lane in the wavefront
     __device__ __forceinline__ af_grp_t() : lane((int)(threadIdx.x & (GW - 1))), base((int)(threadIdx.x & 63u & ~(unsigned)(GW - 1))) {}
     __device__ __forceinline__ unsigned long long ballot(bool p) const {
@@ -319,10 +318,8 @@ struct af_grp_t {
     }
     __device__ __forceinline__ unsigned long long lt_mask() const { return (1ull << lane) - 1ull; }
     template <class T> __device__ __forceinline__ T shfl(T v, int src) const { return __shfl(v, base + src); }
-    __device__ __forceinline__ int id() const { return base / GW; }
-    // a value that is the same in every lane of the group: with the whole wavefront as the group the compiler is told so (an SGPR: scalar compares and
-    // branches, no VGPR held across the phases); narrower groups of one wavefront differ from each other and keep it per lane
-    __device__ __forceinline__ uint32_t uni(uint32_t v) const { return GW == 64 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)v) : v; }
+    // narrower groups of one wavefront differ from each other and keep a group's value per lane
+    __device__ __forceinline__ uint32_t uni(uint32_t v) const { return GW == 64 ? af_uni(v) : v; }
 };
 
 // std::sort of n <= 16 elements is one insertion sort, i.e. a stable sort: every lane places one element by its stable rank
@@ -509,12 +506,11 @@ __device__ __forceinline__ void af_chain_run(WT& L, const ac_params_t& P, uint32
 // ROUTE (the small plain LEVEL-0 instance alone, and only with G.rstage): a read of at most AF_RUN_SLOTS runs of at most AF_RUN_LEN anchors each stops behind
 // the runs.  Its sorted anchors, the runs' boundaries and a header go to the staging slot of read r_in, chain_runs_kernel does everything below with one lane
 // per run, and AF_ST_RUNS is returned.  The test is the same for every lane of the wavefront.
-template <class WT, class GT = af_grp_t<64>, bool GEN = true, bool ROUTE = false>
-__device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t na, float avg_mem_length, const GT g = GT(), const bool sec_on = false, const uint32_t r_in = 0) {
+template <class WT, bool GEN = true, bool ROUTE = false>
+__device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t na, float avg_mem_length, const bool sec_on = false, const uint32_t r_in = 0) {
     const ac_params_t& P = G.A.P;
-    constexpr uint32_t GW = GT::W;
-    const int lane = g.lane;
-    na = g.uni(na);
+    const int lane = (int)(threadIdx.x & 63u);
+    na = af_uni(na);
     // ---- std::sort of the anchors by reference end (chain.hpp:246) ----
     AF_STAMP(s0);
 #if defined(AF_PROFILE) || defined(AF_CUTS)
@@ -524,17 +520,17 @@ __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t
         if (na <= 16) af_small_sort(L.anch, na, [](const uint64_t& a, const uint64_t& b) { return AF_X(a) < AF_X(b); }, lane);
         else { if (lane == 0) lsort::sort(L.anch, (long)na, [](const uint64_t& a, const uint64_t& b) { return AF_X(a) < AF_X(b); }, L.stack); __syncthreads(); }
     } else {
-        af_wave_sort<(WT::MA + GT::W - 1) / GT::W>(g, L.anch, na, L.stack, L.run_start, reinterpret_cast<uint16_t*>(L.p), reinterpret_cast<uint32_t*>(L.f), [](const uint64_t& x) { return AF_X(x); });
-        for (uint32_t i = lane; i < na; i += GW) L.p[i] = 0;        // (scratch of the sort)
+        af_wave_sort<(WT::MA + 63) / 64>(af_grp_t<64>(), L.anch, na, L.stack, L.run_start, reinterpret_cast<uint16_t*>(L.p), reinterpret_cast<uint32_t*>(L.f), [](const uint64_t& x) { return AF_X(x); });
+        for (uint32_t i = lane; i < na; i += 64) L.p[i] = 0;        // (scratch of the sort)
         __syncthreads();
     }
     AF_STAMP(s1); AF_PROF(G, 5, s0, s1);
     // ---- runs ----
     uint32_t n_runs = 0;
-    for (uint32_t i0 = 0; i0 < na; i0 += GW) {
+    for (uint32_t i0 = 0; i0 < na; i0 += 64) {
         const uint32_t i = i0 + lane;
         const bool brk = i < na && (i == 0 || (long long)AF_X(L.anch[i]) > (long long)AF_X(L.anch[i - 1]) + P.max_dist_x);
-        const unsigned long long bal = g.ballot(brk);
+        const unsigned long long bal = __ballot(brk);
         if (brk) L.run_start[n_runs + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)i;
         n_runs += (uint32_t)__popcll(bal);
     }
@@ -542,9 +538,9 @@ __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t
     __syncthreads();
     if (ROUTE && G.rstage != nullptr && n_runs <= AF_RUN_SLOTS) {
         const bool lng = (uint32_t)lane < n_runs && (uint32_t)L.run_start[lane + 1] - (uint32_t)L.run_start[lane] > AF_RUN_LEN;
-        if (g.ballot(lng) == 0) {
+        if (__ballot(lng) == 0) {
             af_rstage_t& R = G.rstage[r_in];
-            for (uint32_t i = lane; i < na; i += GW) {
+            for (uint32_t i = lane; i < na; i += 64) {
                 const uint64_t aw = L.anch[i];
                 const af_mem_t mi = L.mem[aw >> 40];
                 uint32_t fb = 0;                                   // the first anchor of the anchor's run
@@ -562,7 +558,7 @@ __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t
 #endif
     // ---- chaining DP (chain.hpp:278-362), one lane per run ----
     // (G.chain_narrow: the host's cc_narrow_ok(P), the same for every lane and every launch of a context's parameters)
-    for (uint32_t k = lane; k < n_runs; k += GW) {
+    for (uint32_t k = lane; k < n_runs; k += 64) {
         const uint32_t fb = L.run_start[k], fe = L.run_start[k + 1];
         if (!GEN || (G.chain_narrow && !(G.dbg & 64))) af_chain_run<int32_t, uint32_t>(L, P, fb, fe, avg_mem_length, WT::SEC && sec_on);
         // (the cross-check runs the reference's arithmetic as well)
@@ -579,17 +575,17 @@ __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t
     // instance's capacities do not hold the track.
     uint32_t n_chains = 0;
     auto track = [&](int32_t* F, int32_t* MSC, int16_t* PP, int16_t* TT, uint32_t pool0, bool by_score_alone, uint32_t& n_starts) -> bool {
-        for (uint32_t i = lane; i < na; i += GW) TT[i] = 0;
+        for (uint32_t i = lane; i < na; i += 64) TT[i] = 0;
         __syncthreads();
-        for (uint32_t i = lane; i < na; i += GW) if (PP[i] >= 0) TT[PP[i]] = 1;
+        for (uint32_t i = lane; i < na; i += 64) if (PP[i] >= 0) TT[PP[i]] = 1;
         __syncthreads();
         uint32_t ns = 0;
-        for (uint32_t i0 = 0; i0 < na; i0 += GW) {
+        for (uint32_t i0 = 0; i0 < na; i0 += 64) {
             const uint32_t i = i0 + lane;
             const bool is_end = i < na && TT[i] == 0 && MSC[i] > P.min_chain_score;
             af_start_t st; st.f = 0; st.j = 0;
             if (is_end) { uint32_t j = i; while (F[j] < MSC[j]) j = (uint32_t)PP[j]; st.f = F[j]; st.j = (int32_t)j; }
-            const unsigned long long bal = g.ballot(is_end);
+            const unsigned long long bal = __ballot(is_end);
             const uint32_t at = ns + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
             if (is_end && at < (uint32_t)WT::MC) L.starts[at] = st;
             ns += (uint32_t)__popcll(bal);
@@ -599,24 +595,24 @@ __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t
         __syncthreads();
         if (ns == 0) return true;
         if (by_score_alone) {          // (t, s_off and this track's part of the pool are free: scratch of the sort)
-            af_wave_sort<(WT::MC + GT::W - 1) / GT::W>(g, L.starts, ns, L.stack, reinterpret_cast<uint16_t*>(TT), L.s_off, reinterpret_cast<uint32_t*>(L.pool + pool0), [](const af_start_t& x) { return -(int64_t)x.f; });
+            af_wave_sort<(WT::MC + 63) / 64>(af_grp_t<64>(), L.starts, ns, L.stack, reinterpret_cast<uint16_t*>(TT), L.s_off, reinterpret_cast<uint32_t*>(L.pool + pool0), [](const af_start_t& x) { return -(int64_t)x.f; });
         } else {
-            af_start_t v[(WT::MC + GT::W - 1) / GT::W]; uint32_t rk[(WT::MC + GT::W - 1) / GT::W];
+            af_start_t v[(WT::MC + 63) / 64]; uint32_t rk[(WT::MC + 63) / 64];
 #pragma unroll
-            for (int q = 0; q < (WT::MC + GT::W - 1) / GT::W; ++q) {
-                const uint32_t s = (uint32_t)lane + GW * q;
+            for (int q = 0; q < (WT::MC + 63) / 64; ++q) {
+                const uint32_t s = (uint32_t)lane + 64u * q;
                 rk[q] = 0;
                 if (s < ns) { v[q] = L.starts[s]; for (uint32_t k = 0; k < ns; ++k) { const af_start_t w = L.starts[k]; rk[q] += (w.f > v[q].f || (w.f == v[q].f && (w.j > v[q].j || (w.j == v[q].j && k < s)))) ? 1u : 0u; } }
             }
             __syncthreads();
 #pragma unroll
-            for (int q = 0; q < (WT::MC + GT::W - 1) / GT::W; ++q) if ((uint32_t)lane + GW * q < ns) L.starts[rk[q]] = v[q];
+            for (int q = 0; q < (WT::MC + 63) / 64; ++q) if ((uint32_t)lane + 64u * q < ns) L.starts[rk[q]] = v[q];
             __syncthreads();
         }
         // backtracking (chain.hpp:166-200), one lane per run, every lane over the sorted starts of its run in order
-        for (uint32_t i = lane; i < na; i += GW) TT[i] = 0;
+        for (uint32_t i = lane; i < na; i += 64) TT[i] = 0;
         __syncthreads();
-        for (uint32_t k = lane; k < n_runs; k += GW) {
+        for (uint32_t k = lane; k < n_runs; k += 64) {
             const uint32_t fb = L.run_start[k], fe = L.run_start[k + 1];
             uint32_t used = pool0 + fb;                           // a run's chains use at most one pool entry per anchor and one more per start
             for (uint32_t s = 0; s < ns; ++s) used += (uint32_t)L.starts[s].j < fb ? 1u : 0u;
@@ -643,10 +639,10 @@ __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t
         }
         __syncthreads();
         uint32_t kept = 0;
-        for (uint32_t s0 = 0; s0 < ns; s0 += GW) {
+        for (uint32_t s0 = 0; s0 < ns; s0 += 64) {
             const uint32_t sx = s0 + lane;
             const bool keep = sx < ns && L.s_cnt[sx] > 0;
-            const unsigned long long bal = g.ballot(keep);
+            const unsigned long long bal = __ballot(keep);
             const uint32_t at = n_chains + kept + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
             if (keep && at < (uint32_t)WT::MC) {
                 af_chain_t c;
@@ -672,7 +668,7 @@ __device__ __forceinline__ uint32_t af_chain(const af_args_t& G, WT& L, uint32_t
         if (n_chains <= 16) af_small_sort(L.chains, n_chains, [](const af_chain_t& x, const af_chain_t& y) { return x.score > y.score; }, lane);
         else { if (lane == 0) lsort::sort(L.chains, (long)n_chains, [](const af_chain_t& x, const af_chain_t& y) { return x.score > y.score; }, L.stack); __syncthreads(); }
     } else          // by the whole wave (run_start and p are free again: scratch)
-        af_wave_sort<(WT::MC + GT::W - 1) / GT::W>(g, L.chains, n_chains, L.stack, L.run_start, reinterpret_cast<uint16_t*>(L.p), reinterpret_cast<uint32_t*>(L.f), [](const af_chain_t& x) { return -(int64_t)x.score; });
+        af_wave_sort<(WT::MC + 63) / 64>(af_grp_t<64>(), L.chains, n_chains, L.stack, L.run_start, reinterpret_cast<uint16_t*>(L.p), reinterpret_cast<uint32_t*>(L.f), [](const af_chain_t& x) { return -(int64_t)x.score; });
     if (lane == 0) L.n_chains_sh = n_chains;
     __syncthreads();
     AF_STAMP(s3); AF_PROF(G, 7, s2, s3);
@@ -823,11 +819,11 @@ __device__ __forceinline__ uint32_t af_build_cand(const af_args_t& G, WT& L, af_
 // it scores - by lane 0 (a few comparisons per chain, no memory traffic), then one LANE per chain to score builds that chain's anchors and problems
 // (af_build_cand: the one-base gaps read the read and the text - dependent HBM loads that one lane used to take one after the other for every chain).
 // All lanes call it; the returned status is uniform: AF_ST_CAND, a fallback, or 0xFF (does not fit this instance: the next larger one takes the read).
-template <class WT, class GT>
-__device__ __forceinline__ uint32_t af_plan_cands(const af_args_t& G, WT& L, uint64_t off, uint32_t m, const GT g) {
+template <class WT>
+__device__ __forceinline__ uint32_t af_plan_cands(const af_args_t& G, WT& L, uint64_t off, uint32_t m, const af_grp_t<64> g) {
     const ac_params_t& P = G.A.P;
     const int lane = g.lane;
-    static_assert(WT::NC <= GT::W, "one lane per chain to score");
+    static_assert(WT::NC <= 64, "one lane per chain to score");
     const uint32_t n_chains = L.n_chains_sh;
     auto& PL = L.plan;
     // a capacity of THIS instance (chains to score, their anchors, their problems): the next larger instance takes the read; the largest hands it to align_kernel
@@ -942,10 +938,9 @@ __global__ void __launch_bounds__(256) classify_kernel(const af_args_t G) {
 }
 
 // One read of chain_plan_kernel once its seeds and anchors are in LDS: chains (af_chain), check_left_MEM's lifts, the selection loop and the plan
-// (af_plan_cands), the hand-over lists, the plan and the tasks to HBM.  All lanes of the read's group call it.
-template <class WT, int LEVEL, bool GEN, class GT>
-__device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT g, uint32_t r_in, uint64_t off, uint32_t m, uint32_t na, float avg, bool fallback, bool too_big) {
-    constexpr uint32_t GW = GT::W;
+// (af_plan_cands), the hand-over lists, the plan and the tasks to HBM.  All lanes of the wavefront call it (g: the wavefront as af_wave_sort's group of lanes).
+template <class WT, int LEVEL, bool GEN>
+__device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const af_grp_t<64> g, uint32_t r_in, uint64_t off, uint32_t m, uint32_t na, float avg, bool fallback, bool too_big) {
     const int lane = g.lane;
     const ak_args_t& A = G.A;
     const uint64_t r = A.read_lo + r_in;
@@ -954,9 +949,9 @@ __device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT
     if (G.dbg & 4) na = 0;                                   // timing experiments (results are wrong): stop after the anchors ...
 #endif
     // (the runs' route: the small plain instance alone, and only where plan_kernel takes the chain table)
-    constexpr bool ROUTE = LEVEL == 0 && !GEN && GW == 64 && !WT::SEC && (uint32_t)WT::MA <= AF_RUN_NODES && (uint32_t)WT::MC <= AF_CTAB && (uint32_t)WT::MA <= AF_PLAN_AN;
+    constexpr bool ROUTE = LEVEL == 0 && !GEN && !WT::SEC && (uint32_t)WT::MA <= AF_RUN_NODES && (uint32_t)WT::MC <= AF_CTAB && (uint32_t)WT::MA <= AF_PLAN_AN;
     if (!fallback && !too_big && na > 0) {
-        status = af_chain<WT, GT, GEN, ROUTE>(G, L, na, avg, g, false, r_in);
+        status = af_chain<WT, GEN, ROUTE>(G, L, na, avg, false, r_in);
         status = (uint32_t)g.shfl((int)status, 0);
         __syncthreads();
         if (ROUTE && status == AF_ST_RUNS) return;              // chain_runs_kernel goes on from here
@@ -966,7 +961,7 @@ __device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT
         if (status == 0xFFu) too_big = true;
         else if (status == AF_ST_CAND) {
             // check_left_MEM's coordinate of every chain: index(lift(leftmost anchor)).second + 1 (aligner_ksw2.hpp:565-576)
-            for (uint32_t ci = lane; ci < L.n_chains_sh; ci += GW) {
+            for (uint32_t ci = lane; ci < L.n_chains_sh; ci += 64) {
                 const af_chain_t ch = L.chains[ci];
                 const uint64_t aw = L.anch[L.pool[ch.off + ch.cnt - 1]];
                 const af_mem_t ml = L.mem[aw >> 40];
@@ -984,11 +979,11 @@ __device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT
                 af_ctab_t* const CT = G.ctab + (size_t)r_in * AF_CTAB;
                 af_anchor_t* const AN = G.plans[r_in].an;
                 uint32_t an0 = 0;                                  // exclusive prefix sum of the chains' anchor counts over the lanes
-                for (uint32_t c0 = 0; c0 < n_chains; c0 += GW) {
+                for (uint32_t c0 = 0; c0 < n_chains; c0 += 64) {
                     const uint32_t ci = c0 + (uint32_t)lane;
                     const uint32_t cnt = ci < n_chains ? L.chains[ci].cnt : 0u;
                     uint32_t incl = cnt;
-                    for (int o = 1; o < (int)GW; o <<= 1) { const uint32_t x = (uint32_t)__shfl_up((int)incl, o); if (lane >= o) incl += x; }
+                    for (int o = 1; o < 64; o <<= 1) { const uint32_t x = (uint32_t)__shfl_up((int)incl, o); if (lane >= o) incl += x; }
                     if (ci < n_chains) {
                         const af_chain_t ch = L.chains[ci];
                         const uint32_t at = an0 + incl - cnt;
@@ -1003,7 +998,7 @@ __device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT
                         af_ctab_t E; E.score = ch.score; E.an0 = (uint16_t)at; E.cnt = (uint8_t)ch.cnt; E.strand = (uint8_t)strand; E.left_ref = L.left_ref[ci];
                         CT[ci] = E;
                     }
-                    an0 += (uint32_t)g.shfl((int)incl, (int)GW - 1);
+                    an0 += (uint32_t)g.shfl((int)incl, 63);
                 }
                 if (lane == 0) {          // the plan's header so far; plan_kernel completes it
                     af_plan_t& PH = G.plans[r_in];
@@ -1031,7 +1026,7 @@ __device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT
     const uint32_t nt = status == AF_ST_CAND ? L.n_tasks : 0u;
     const uint32_t t0 = r_in * AF_MAX_TASKS_READ;                 // the read's own slots (bin_tasks_kernel queues them)
     if (status == AF_ST_CAND) {
-        for (uint32_t k = lane; k < nt; k += GW) G.tasks[t0 + k] = PL.tasks[k];
+        for (uint32_t k = lane; k < nt; k += 64) G.tasks[t0 + k] = PL.tasks[k];
         if ((uint32_t)lane < PL.n_cand) PL.cand[lane].task0 += t0;
     }
     if (lane == 0) G.ntasks[r_in] = (uint8_t)nt;
@@ -1046,47 +1041,44 @@ __device__ __forceinline__ void af_plan_read(const af_args_t& G, WT& L, const GT
         const uint32_t words = (uint32_t)((offsetof(af_plan_t, cand) + (status == AF_ST_CAND ? PL.n_cand : 0u) * sizeof(af_cand_t)) / 4);
         const uint32_t* src = reinterpret_cast<const uint32_t*>(&PL);
         uint32_t* dst = reinterpret_cast<uint32_t*>(G.plans + r_in);
-        for (uint32_t w = lane; w < words; w += GW) dst[w] = src[w];
+        for (uint32_t w = lane; w < words; w += 64) dst[w] = src[w];
         const uint32_t awords = status == AF_ST_CAND ? PL.n_an * (uint32_t)(sizeof(af_anchor_t) / 4) : 0u;
         const uint32_t* asrc = reinterpret_cast<const uint32_t*>(PL.an);
         uint32_t* adst = reinterpret_cast<uint32_t*>(G.plans[r_in].an);
-        for (uint32_t w = lane; w < awords; w += GW) adst[w] = asrc[w];
+        for (uint32_t w = lane; w < awords; w += 64) adst[w] = asrc[w];
     }
     __syncthreads();
 }
 
 // WT: the LDS instance (capacities).  LEVEL 0 / 1 / 2: the reads of list0 / big_list / huge_list (classify_kernel); a read whose chains or plan overflow
-// the instance it was given goes to the next list, from the largest instance to align_kernel.  GW: the lanes of one read (af_grp_t): 64 / GW reads per
-// wavefront side by side, each in its own copy of WT.
-// (Measured and not kept, profiles/r04f: classify_kernel gathering a read's seeds and anchors into a slot that the LEVEL-0 instance asks for one read ahead - the
-// kernel is bound by VALU issue, not by those loads: 9.36 against 9.2 ms per 1 M reads, and 1.5 ms more in classify_kernel.)
+// the instance it was given goes to the next list, from the largest instance to align_kernel.  One read per wavefront.  OCC: the waves per SIMD the
+// instance is compiled for (its launch site names it: what its LDS admits).
+// (Measured and not kept, profiles/r04a: four reads per wavefront in groups of 16 lanes, each in its own copy of WT - 14.7 against 9.2 ms per 1 M reads: the
+// kernel is bound by VALU issue, and the groups fit 2 waves per SIMD.  profiles/r04f: classify_kernel gathering a read's seeds and anchors into a slot that
+// the LEVEL-0 instance asks for one read ahead - 9.36 against 9.2 ms, and 1.5 ms more in classify_kernel.)
 // GEN: the general instance (af_chain), launched for MONI_AF_DBG=64 and for chaining parameters beyond cc_narrow_ok: it alone holds the serial sorts of the
 // cross-check and the 64-bit chaining DP.
-template <class WT, int LEVEL, int OCC = (LEVEL == 0 ? 6 : LEVEL == 1 ? 3 : 1), int GW = 64, bool GEN = false>
+template <class WT, int LEVEL, int OCC, bool GEN>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) chain_plan_kernel(const af_args_t G) {
-    constexpr uint32_t NG = 64 / GW;          // reads per wavefront
-    __shared__ WT Ls[NG];                     // one wavefront per workgroup: __syncthreads() orders the wave's own LDS traffic
-    typedef af_grp_t<GW> GT;
-    const GT g;
-    WT& L = Ls[NG > 1 ? g.id() : 0];
-    const int lane = g.lane;
+    __shared__ WT L;                          // one wavefront per workgroup: __syncthreads() orders the wave's own LDS traffic
+    const af_grp_t<64> g;                     // the wavefront as one group of lanes, for af_plan_read
+    const int lane = (int)(threadIdx.x & 63u);
     const ak_args_t& A = G.A;
     constexpr bool BIG = LEVEL > 0;
     const uint32_t n_work = G.ctr[LEVEL == 0 ? AFC_L0 : LEVEL == 1 ? AFC_BIG : AFC_HUGE];
     const uint32_t* const work_list = LEVEL == 0 ? G.list0 : LEVEL == 1 ? G.big_list : G.huge_list;
-    constexpr uint32_t GRAB = BIG ? 1u : NG > 1 ? 2u : 8u;          // reads a group takes per visit of the wavefront to the shared cursor
+    constexpr uint32_t GRAB = BIG ? 1u : 8u;          // reads the wavefront takes per visit to the shared cursor
     uint32_t w_base = 0, w_k = GRAB;          // wave-uniform
     while (true) {
         if (w_k >= GRAB) {
-            if (threadIdx.x == 0) w_base = atomicAdd(&G.ctr[LEVEL == 0 ? AFC_READ_CUR : LEVEL == 1 ? AFC_BIG_CUR : AFC_HUGE_CUR], GRAB * NG);
-            w_base = GW == 64 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)w_base) : (uint32_t)__shfl((int)w_base, 0);
+            if (threadIdx.x == 0) w_base = atomicAdd(&G.ctr[LEVEL == 0 ? AFC_READ_CUR : LEVEL == 1 ? AFC_BIG_CUR : AFC_HUGE_CUR], GRAB);
+            w_base = af_uni(w_base);
             w_k = 0;
         }
-        if (w_base + w_k * NG >= n_work) break;          // (wave-uniform: the groups leave together)
-        const uint32_t w_in = w_base + w_k * NG + (NG > 1 ? (uint32_t)g.id() : 0u);
+        const uint32_t w_in = w_base + w_k;
+        if (w_in >= n_work) break;
         ++w_k;
-        if (w_in >= n_work) continue;                    // the list's last reads: fewer than the wavefront has groups
-        const uint32_t r_in = g.uni(work_list[w_in]);
+        const uint32_t r_in = af_uni(work_list[w_in]);
         const uint64_t r = A.read_lo + r_in;
         const uint64_t off = A.offs[r];
         const uint32_t m = (uint32_t)(A.offs[r + 1] - off);
@@ -1099,10 +1091,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OC
         if (!fallback && b > a) {
             // ---- seed_freq_filter (aligner_ksw2.hpp:1905-1933): lanes over the read's seeds ----
             unsigned long long total = 0;
-            for (uint64_t k = a + lane; k < b; k += GW) total += A.mems[k].occ_cnt;
-            for (int o = GW / 2; o > 0; o >>= 1) total += __shfl_xor(total, o);
+            for (uint64_t k = a + lane; k < b; k += 64) total += A.mems[k].occ_cnt;
+            for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
             unsigned long long tot_len = 0, n_anch = 0;
-            for (uint64_t k0 = a; k0 < b; k0 += GW) {
+            for (uint64_t k0 = a; k0 < b; k0 += 64) {
                 const uint64_t k = k0 + lane;
                 bool keep = false;
                 moni_mem_t gm;
@@ -1111,8 +1103,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OC
                     keep = true;
                     if (A.P.filter_freq) { const double fr = static_cast<double>(gm.occ_cnt) / (double)(size_t)total; if (fr > A.P.freq_thr) keep = false; }
                 }
-                const unsigned long long bal = g.ballot(keep);
-                const uint32_t at = n_mems + (uint32_t)__popcll(bal & g.lt_mask());
+                const unsigned long long bal = __ballot(keep);
+                const uint32_t at = n_mems + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
                 if (keep && at < (uint32_t)WT::MM) {
                     af_mem_t x; x.occ_off = gm.occ_off; x.nocc = gm.occ_cnt; x.len = (uint16_t)gm.len; x.idx = (uint16_t)gm.idx; x.rpos = (uint16_t)gm.rpos; x.mate = (uint8_t)gm.mate; x.pad = 0;
                     L.mem[at] = x;
@@ -1120,22 +1112,22 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OC
                 if (keep) { tot_len += (unsigned long long)gm.len * gm.occ_cnt; n_anch += gm.occ_cnt; }
                 n_mems += (uint32_t)__popcll(bal);
             }
-            for (int o = GW / 2; o > 0; o >>= 1) { tot_len += __shfl_xor(tot_len, o); n_anch += __shfl_xor(n_anch, o); }
+            for (int o = 32; o > 0; o >>= 1) { tot_len += __shfl_xor(tot_len, o); n_anch += __shfl_xor(n_anch, o); }
             if (n_mems > (uint32_t)WT::MM || n_anch > (unsigned long long)WT::MA) too_big = true;
-            na = g.uni((uint32_t)n_anch);
+            na = af_uni((uint32_t)n_anch);
             if (!too_big && na > 0) {
                 avg = (float)(size_t)tot_len / (size_t)n_anch;
                 __syncthreads();
                 // ---- populate_anchors (chain.hpp:83-95): mem by mem, occurrence by occurrence.  Every lane finds the seed of its anchors (a seed has about as
                 // many occurrences as the index has sequences), so all of a read's occurrences are asked for at once: seed by seed they were as many dependent
                 // round trips to HBM as the read has seeds, with a fifth of the lanes at work ----
-                for (uint32_t x = lane; x < na; x += GW) {
+                for (uint32_t x = lane; x < na; x += 64) {
                     uint32_t i = 0, base = 0;
                     while (base + L.mem[i].nocc <= x) { base += L.mem[i].nocc; ++i; }
                     const af_mem_t mi = L.mem[i];
                     L.anch[x] = (A.occs[mi.occ_off + (x - base)] + mi.len - 1) | ((uint64_t)i << 40);
                 }
-                for (uint32_t i = lane; i < na; i += GW) { L.f[i] = 0; L.msc[i] = 0; L.p[i] = 0; L.t[i] = 0; }
+                for (uint32_t i = lane; i < na; i += 64) { L.f[i] = 0; L.msc[i] = 0; L.p[i] = 0; L.t[i] = 0; }
             }
         }
         __syncthreads();
@@ -2575,7 +2567,7 @@ __global__ void __launch_bounds__(256) select_kernel(const af_args_t G) {
         }
         af_window(C, PL.an + C.an0, m, lc_t, rc_t, PL.ref_pos, PL.ref_len);
         const uint32_t n_tb = C.overlap ? 1u : (uint32_t)C.has_lc + C.has_rc + C.n_gap_tasks;
-        PL.pad = (uint16_t)(C.strand | (n_tb << 8));          // finish_wave_kernel starts its fetches from the plan's header alone
+        PL.pad = (uint16_t)(C.strand | (n_tb << 8));          // finish_prep_kernel starts its fetches from the plan's header alone
         PL.pad2 = (uint32_t)C.an0 | ((uint32_t)C.n_an << 16);
         if (!fallback && n_tb) {
             const uint32_t tb0 = atomicAdd(&G.ctr[AFC_TRACED], n_tb);
@@ -2696,13 +2688,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// finish_wave_kernel: the same work as finish_kernel, one wavefront per read, the SAM line assembled in LDS and written out with
-// coalesced stores.  The lanes stage the chain record, the traceback records and the strand-oriented read; lane 0 stitches the CIGAR
-// and lifts it (aligner_ksw2.hpp:3049-3108, 3133-3175); MD / NM (write_MD_core, sam.hpp:249-287) come from 64-column ballots, every
-// mismatching lane writing its own MD item.  The line itself (sam.hpp:144-188) is not spelled character by character: lane 0 lists
-// its SEGMENTS (a literal, a decimal number, a sequence name, SEQ, QUAL, reference bases ...: ~60 per line, a few instructions each)
-// and then all lanes render the bytes of the line side by side, each finding its segment by binary search.  MAPQ (mapq.hpp:146-184) in
-// IEEE double operations in the reference's order.  A line, CIGAR or MD beyond the LDS staging goes to the host pipeline.
+// A SAM line in LDS: the sizes and helpers that the kernels spelling lines share (finish_render_kernel below; one wavefront per pair
+// in pe_lines.hip).  A line (sam.hpp:144-188) is not spelled character by character: it is a list of SEGMENTS (a literal, a decimal
+// number, a sequence name, SEQ, QUAL, a CIGAR, the MD string ...: ~60 per line), assembled in LDS and written out with coalesced
+// stores.  pe_lines.hip has lane 0 list the segments (afs_push and its kin, a few instructions each) and then all lanes render the
+// bytes of the line side by side, each finding its segment by binary search; it takes MD / NM (write_MD_core, sam.hpp:249-287) from
+// 64-column ballots, every mismatching lane writing its own MD item (afs_md).  finish_render_kernel lays the segments out by all lanes
+// (render_core.h).  A line, CIGAR or MD beyond the LDS staging goes to the host pipeline.
 // ------------------------------------------------------------------------------------------------------------------------------
 #define AFS_LINE 1280            // bytes of one line in LDS
 #define AFS_MAXSEG 96            // segments of one line (a CIGAR and the MD string are one segment each)
@@ -2711,23 +2703,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 #define AFS_LCIG 128             // ... and of the lifted one
 #define AFW_NAMES 1024           // sequence names kept in LDS when they fit (else they are read from HBM)
 #define AFW_NSEQ 126
-#define AFW_TB_WORDS (AF_TB_CIG + 1)
 static __device__ const char afs_lit[] = AFR_LIT_TEXT;          // (the text and the LT_* / SK_* names: render_core.h)
 static_assert(sizeof(afs_lit) == 89, "literal table");
-struct af_finw_t {
-    uint8_t line[AFS_LINE];
-    uint8_t seq[AF_MAX_READ];            // the read in alignment orientation (ASCII, kpbseq.h:120-137 complement)
-    uint32_t cig[AFS_CIG], lcig[AFS_LCIG];
-    uint32_t n_cig, n_lcig, ovf, n_seg, total, seq_at, qual_at;      // seq_at / qual_at: where SEQ and QUAL start in the line (QUAL absent: ~0)
-    uint8_t names[AFW_NAMES]; uint16_t name_off[AFW_NSEQ + 2];      // the index's sequence names (kernel lifetime)
-    af_cand_t cand; af_anchor_t an[AF_FIN_AN];                       // the final chain's record, its first anchors and the alternatives, fetched by all lanes at once
-    uint64_t alt_pos[AF_MAX_CAND]; int32_t alt_score[AF_MAX_CAND]; uint32_t alt_sid[AF_MAX_CAND], alt_p1[AF_MAX_CAND];
-    uint32_t md_item[AFS_MAXMD];         // type (2 bits: 0 closing count, 1 mismatch, 2 deletion) | matches before it << 2 | mismatch: reference base << 12;
-                                         // deletion: length << 12 | offset of its first base in the reference window << 21
-    uint16_t md_off[AFS_MAXMD + 1];      // where an item's text starts in the MD string
-    uint16_t cig_off[AFS_CIG + 1], lcig_off[AFS_LCIG + 1];      // the same for the operations of the two CIGAR strings
-    uint16_t seg_off[AFS_MAXSEG + 1]; uint8_t seg_kind[AFS_MAXSEG]; uint32_t seg_val[AFS_MAXSEG];
-};
 
 __device__ __forceinline__ uint32_t afs_ndig(uint32_t u) {
     return 1u + (u >= 10u) + (u >= 100u) + (u >= 1000u) + (u >= 10000u) + (u >= 100000u) + (u >= 1000000u) + (u >= 10000000u) + (u >= 100000000u) + (u >= 1000000000u);
@@ -2758,7 +2735,7 @@ __device__ __forceinline__ void afs_cigar(LT& L, uint32_t& n, uint32_t& p, const
 // MD / NM of one CIGAR over the window that starts at text position t0 (write_MD_core).  All lanes call it (uniform control flow).
 // items: the MD string as a list in L.md_item (a mismatching lane writes its own item: the matches before it and its base); n_items
 // counts them (AFS_MAXMD + 1: something did not fit, the caller sends the read to the host pipeline).  Returns NM (uniform).
-// LT: holds the read in alignment orientation (seq) and the item list (md_item): af_finw_t, or one mate of a pair (pe_lines.hip).
+// LT: holds the read in alignment orientation (seq) and the item list (md_item): one mate of a pair (pe_lines.hip).
 template <class LT>
 __device__ __forceinline__ int afs_md(const dp_launch_t& D, LT& L, const uint32_t* cg, uint32_t n_cig, uint64_t t0, bool items, uint32_t& n_items,
                                       const uint8_t* win) {          // win: the window's nt4 codes in LDS (or nullptr: read the text)
@@ -2805,334 +2782,15 @@ __device__ __forceinline__ int afs_md(const dp_launch_t& D, LT& L, const uint32_
     return NM;
 }
 
-// traced problem k / anchor j of the final chain: the first AF_FIN_TB / AF_FIN_AN are staged in LDS, the rest is read where it lies in HBM
-__device__ __forceinline__ const af_tb_t* afw_tb(const uint32_t* tbs, const af_tb_t* tb, uint32_t tb0, uint32_t k) {
-    return k < AF_FIN_TB ? reinterpret_cast<const af_tb_t*>(tbs + k * (AF_TB_CIG + 1)) : tb + tb0 + k;
-}
-__device__ __forceinline__ const af_anchor_t* afw_anchor(const af_anchor_t* staged, const af_anchor_t* all, uint32_t j) { return j < AF_FIN_AN ? staged + j : all + j; }
-
-#if defined(AF_CUTS)
-#define AFW_CUT(bit) if (G.dbg & (bit)) { if (lane == 0) { moni_aln_rec_t rc_; memset(&rc_, 0, sizeof rc_); A.recs[r_in] = rc_; if (A.dev_len) { A.dev_len[r_in] = 0; A.dev_off[r_in] = 0; } } continue; }
-#else
-#define AFW_CUT(bit)
-#endif
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) finish_wave_kernel(const af_args_t G) {
-    __shared__ af_finw_t L;
-    const int lane = threadIdx.x;
-    const ak_args_t& A = G.A;
-    const ak_fmt_t& F = A.fmt;
-    // the sequence names: in LDS for the kernel's lifetime when they fit
-    const uint32_t n_seq = (uint32_t)A.P.n_seq;
-    const bool names_lds = n_seq <= AFW_NSEQ && F.sname_off[n_seq] <= AFW_NAMES;
-    if (names_lds) {
-        for (uint32_t k = lane; k <= n_seq; k += 64) L.name_off[k] = (uint16_t)F.sname_off[k];
-        for (uint32_t k = lane; k < F.sname_off[n_seq]; k += 64) L.names[k] = F.snames[k];
-    }
-    uint32_t* const tbs = reinterpret_cast<uint32_t*>(L.line);       // staged traceback records: the line buffer is free until the line is rendered
-#define TB(k) (*afw_tb(tbs, G.tb, h_tb0, (k)))          // (the argument is evaluated once: call sites pass tbx++)
-#define ANCH(j) (*afw_anchor(L.an, PL.an + h_an0, (j)))
-#define NAME_LEN(sid) (names_lds ? (uint32_t)(L.name_off[(sid) + 1] - L.name_off[sid]) : F.sname_off[(sid) + 1] - F.sname_off[sid])
-    // the plan's 40-byte header (status, final chain, strand, traced problems, window) says where everything else is: it is read with
-    // one round trip, the next read's while this one is worked on
-    uint64_t h0 = 0, h1 = 0, h2 = 0, h4 = 0, g0 = 0, g1 = 0, g2 = 0, g4 = 0;
-    if (blockIdx.x < A.n_reads) { const uint64_t* H = reinterpret_cast<const uint64_t*>(&G.plans[blockIdx.x]); h0 = H[0]; h1 = H[1]; h2 = H[2]; h4 = H[4]; }
-    for (uint64_t r_in = blockIdx.x; r_in < A.n_reads; r_in += gridDim.x, h0 = g0, h1 = g1, h2 = g2, h4 = g4) {
-        if (r_in + gridDim.x < A.n_reads) { const uint64_t* H = reinterpret_cast<const uint64_t*>(&G.plans[r_in + gridDim.x]); g0 = H[0]; g1 = H[1]; g2 = H[2]; g4 = H[4]; }
-        af_plan_t& PL = G.plans[r_in];
-        const uint32_t st = (uint32_t)(h0 & 0xFFu);
-        if (st == AF_ST_FALLBACK) continue;
-        const uint32_t h_final = (uint32_t)(h1 & 0xFFu), h_nalt = (uint32_t)((h1 >> 8) & 0xFFu), h_strand = (uint32_t)((h1 >> 16) & 0xFFu), h_ntb = (uint32_t)((h1 >> 24) & 0xFFu);
-        const int32_t h_score2 = (int32_t)(uint32_t)(h1 >> 32);
-        const uint32_t h_tb0 = (uint32_t)h4, h_an0 = (uint32_t)(h4 >> 32) & 0xFFFFu, h_nan = (uint32_t)(h4 >> 48) & 0xFFu;
-        const uint64_t r = A.read_lo + r_in;
-        const uint64_t off = A.offs[r];
-        const uint32_t m = (uint32_t)(A.offs[r + 1] - off);
-        const bool aligned = st == AF_ST_FINAL;
-        __syncthreads();
-        AF_STAMP(fw0);
-        // where the alignment starts in the lift tables: these dependent loads (directory, sequence record, first run) are started before the
-        // staging below instead of inside lane 0's serial section
-        const uint64_t aln_pos = aligned ? h2 : 0ull;
-        uint32_t hint0 = 0xFFFFFFFFu;
-        const uint32_t sid0 = aligned ? ac_seq_of(A.P, aln_pos, &hint0) : 0u;
-        moni_lift_seq_t LS0; LS0.second = 0; LS0.run_off = 0; LS0.n_runs = 0; LS0.start = 0; LS0.end = 0;
-        if (aligned) LS0 = A.P.lift_seqs[sid0];
-        // the final chain's record, the alternatives and (below) its traceback records come with one round trip each instead of field by field
-        if (aligned) {
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(&PL.cand[h_final]);
-            uint32_t* dst = reinterpret_cast<uint32_t*>(&L.cand);
-            for (uint32_t w = lane; w < sizeof(af_cand_t) / 4; w += 64) dst[w] = src[w];
-            const uint32_t* asrc = reinterpret_cast<const uint32_t*>(PL.an + h_an0);
-            uint32_t* adst = reinterpret_cast<uint32_t*>(L.an);
-            for (uint32_t w = lane; w < (h_nan < AF_FIN_AN ? h_nan : AF_FIN_AN) * (uint32_t)(sizeof(af_anchor_t) / 4); w += 64) adst[w] = asrc[w];
-            if (lane < AF_MAX_CAND) L.alt_score[lane] = PL.alt_score[lane];
-        }
-        const af_cand_t* C = aligned ? &L.cand : nullptr;
-        const uint32_t strand = aligned ? h_strand : 0u;
-        const uint32_t n_alt = aligned ? h_nalt : 0u;
-        if (aligned) {
-            for (uint32_t w = lane; w < (h_ntb < AF_FIN_TB ? h_ntb : AF_FIN_TB) * AFW_TB_WORDS; w += 64) {
-                const uint32_t k = w / AFW_TB_WORDS, x = w % AFW_TB_WORDS;
-                tbs[w] = reinterpret_cast<const uint32_t*>(&G.tb[h_tb0 + k])[x];
-            }
-            if ((uint32_t)lane < n_alt) {       // the alternatives' sequences and 1-based positions: one lane each
-                const uint64_t ap = PL.alt_pos[lane];
-                const uint32_t s2 = ac_seq_of(A.P, ap);
-                L.alt_sid[lane] = s2; L.alt_p1[lane] = (uint32_t)(ap - A.P.lift_seqs[s2].start + 1);
-            }
-        }
-        // ---- the read in alignment orientation ----
-        for (uint32_t k = lane; k < m && k < AF_MAX_READ; k += 64) L.seq[k] = strand ? ak_compl(A.D.reads[off + m - 1 - k]) : A.D.reads[off + k];
-        __syncthreads();
-        AFW_CUT(16384)         // timing experiment: stop after the staging
-        bool ovf = false;
-        uint64_t lifted = 0;
-        if (aligned && lane == 0) {
-            // ---- CIGAR stitching (aligner_ksw2.hpp:3049-3108) ----
-            uint32_t n = 0;
-#define PUSH(op) do { if (n < AFS_CIG) L.cig[n++] = (op); else ovf = true; } while (0)
-#define PUSH_MERGE_FIRST(op, first) do { const uint32_t o_ = (op); if ((first) && (o_ & 0xf) == 0 && n > 0) L.cig[n - 1] += o_; else PUSH(o_); } while (0)
-            uint32_t tbx = 0;
-            if (C->overlap) {
-                const af_tb_t& T = TB(tbx);
-                if (T.n_ops == ~0u) ovf = true; else for (uint32_t k = 0; k < T.n_ops; ++k) PUSH(T.ops[T.n_ops - 1 - k]);
-            } else {
-                if (C->has_lc) { const af_tb_t& T = TB(tbx++); if (T.n_ops == ~0u) ovf = true; else for (uint32_t k = 0; k < T.n_ops; ++k) PUSH(T.ops[k]); }
-                const uint32_t rc_x = C->has_rc ? tbx++ : 0u;
-                for (uint32_t j = 0; j < C->n_an; ++j) {
-                    const af_anchor_t g = ANCH(j);
-                    const uint32_t mlen = g.len;
-                    if (n > 0 && (L.cig[n - 1] & 0xf) == 0) L.cig[n - 1] += mlen << 4; else PUSH(mlen << 4);
-                    if (j + 1 < C->n_an) {
-                        if (g.gap_kind == AF_GAP_TASK) { const af_tb_t& T = TB(tbx++); if (T.n_ops == ~0u) ovf = true; else for (uint32_t k = 0; k < T.n_ops; ++k) PUSH_MERGE_FIRST(T.ops[T.n_ops - 1 - k], k == 0); }
-                        else if (g.gap_kind == AF_GAP_INS) PUSH_MERGE_FIRST(((uint32_t)(uint16_t)g.gap_val << 4) | 1u, true);
-                        else if (g.gap_kind == AF_GAP_DEL0) PUSH_MERGE_FIRST(2u, true);
-                        else if (g.gap_kind == AF_GAP_1X1) PUSH_MERGE_FIRST(1u << 4, true);
-                    }
-                }
-                if (C->has_rc) { const af_tb_t& T = TB(rc_x); if (T.n_ops == ~0u) ovf = true; else for (uint32_t k = 0; k < T.n_ops; ++k) PUSH_MERGE_FIRST(T.ops[T.n_ops - 1 - k], k == 0); }
-            }
-#undef PUSH
-#undef PUSH_MERGE_FIRST
-#if defined(AF_CUTS)
-            if (G.dbg & 32768) { L.n_cig = n; L.n_lcig = 0; L.ovf = 1; } else {      // timing experiment: no lift
-#endif
-            // ---- the alignment lifted to the reference contig (aligner_ksw2.hpp:3133-3160) ----
-            const moni_lift_seq_t LS = LS0;
-            const moni_lift_run_t* __restrict__ runs = A.P.lift_runs + LS.run_off;
-            const uint64_t start = aln_pos - LS.start;
-            const uint32_t rel = hint0 == 0xFFFFFFFFu ? hint0 : hint0 - LS.run_off;
-            uint64_t lp = 0;
-            const int nl = ovf ? -1 : lift_cigar(runs, LS.n_runs, start, L.cig, n, L.lcig, AFS_LCIG, rel, &lp);
-            if (nl < 0) ovf = true;
-            lifted = LS.second + (ovf ? 0ull : lp);
-            L.n_cig = n; L.n_lcig = nl < 0 ? 0u : (uint32_t)nl; L.ovf = ovf ? 1u : 0u;
-#if defined(AF_CUTS)
-            }
-#endif
-        }
-        __syncthreads();
-        AF_STAMP(fw1); AF_PROF(G, 16, fw0, fw1);
-        AFW_CUT(2048)          // timing experiment: stop after staging, stitching, lifting
-        if (aligned) { ovf = L.ovf != 0; lifted = ((uint64_t)(uint32_t)__shfl((int)(lifted >> 32), 0) << 32) | (uint32_t)__shfl((int)(lifted & 0xFFFFFFFFull), 0); }
-        moni_aln_rec_t rec;
-        rec.status = aligned ? 1u : 0u; rec.strand = strand; rec.ref_pos = aligned ? aln_pos : 0; rec.score = aligned ? C->score : 0; rec.score2 = aligned ? h_score2 : 0;
-        rec.n_cigar = 0; rec.n_alt = 0; rec.cigar_off = 0; rec.alt_off = 0; rec.nm = 0; rec.md_len = 0; rec.md_off = 0; rec.txt_len = 0; rec.lift_nm = 0; rec.txt_off = 0;
-        bool to_host = (aligned && ovf) || m > AF_MAX_READ;       // more CIGAR operations than the staging holds (align_kernel runs beside this kernel, its list is closed)
-        if (aligned && ovf && lane == 0) atomicAdd(&G.ctr[AFC_WHY + AF_WHY_CIGAR], 1u);
-        uint32_t p = 0;
-        const uint64_t n0 = F.rname_off[r], n1 = F.rname_off[r + 1];
-        if (!to_host) {
-            // ---- what the line needs besides the CIGARs: NM / MD of the lifted alignment, NM of the one on the pangenome text, MAPQ ----
-            int nm = 0, lift_nm = 0, mapq = 0, oa_pos = 0, pos1 = 0;
-            uint32_t n_md = 0, sid = 0, lsid = 0;
-            bool mapped = false;
-            const uint32_t n_cig = aligned ? L.n_cig : 0u, n_lcig = aligned ? L.n_lcig : 0u;
-            const int32_t score = aligned ? C->score : 0, score2 = aligned ? h_score2 : 0;
-            if (aligned) {
-                uint64_t ref_len = 0;
-                for (uint32_t k = 0; k < n_lcig; ++k) { const int op = L.lcig[k] & 0xf; if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += L.lcig[k] >> 4; }
-                mapped = ref_len > 0;
-                sid = sid0; lsid = ac_seq_of(A.P, lifted);
-                oa_pos = (int)(aln_pos - LS0.start + 1);
-                pos1 = (int)(lifted - A.P.lift_seqs[lsid].start + 1);
-                // compute_mapq_se_bwa (mapq.hpp:146-184), the operations in the host's order, none contracted
-                {
-                    const int32_t rl = mapped ? (int32_t)ref_len : 0;
-                    const int32_t l = rl > (int32_t)m ? rl : (int32_t)m;
-                    const int32_t sub = score2 ? score2 : F.min_len * F.smatch;
-                    if (sub < score) {
-                        const double identity = __dsub_rn(1., __ddiv_rn(__ddiv_rn((double)(l * F.smatch - score), (double)(F.smatch + F.smismatch)), (double)l));
-                        if (score != 0) {
-                            double tmp = (double)l < 50.0 ? 1. : ((uint32_t)l < F.mapq_tab_n ? F.mapq_tab[l] : F.mapq_tab[F.mapq_tab_n - 1]);
-                            tmp = __dmul_rn(tmp, __dmul_rn(identity, identity));
-                            const double v = __dadd_rn(__dmul_rn(__dmul_rn(__ddiv_rn(__dmul_rn(6.02, (double)(score - sub)), (double)F.smatch), tmp), tmp), .499);
-                            mapq = (int)v;
-                        }
-                        if (mapq > 60) mapq = 60;
-                        if (mapq < 0) mapq = 0;
-                        mapq = (int)__dadd_rn(__dmul_rn((double)mapq, 1.), .499);
-                    }
-                }
-                bool same = n_lcig == n_cig && lifted == aln_pos;
-                for (uint32_t k = 0; same && k < n_cig; ++k) same = L.lcig[k] == L.cig[k];
-                uint32_t dummy = 0;
-                // the two reference windows (lifted, and on the pangenome text) go to LDS with one round trip: the MD walks read them there
-                uint64_t ref_len_u = 0;
-                for (uint32_t k = 0; k < n_cig; ++k) { const int op = L.cig[k] & 0xf; if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len_u += L.cig[k] >> 4; }
-                const bool win = ref_len <= AFS_LINE / 2 && ref_len_u <= AFS_LINE / 2;
-                if (win) {
-                    if (mapped) for (uint32_t k = lane; k < (uint32_t)ref_len; k += 64) { const uint64_t a = lifted + k; L.line[k] = (uint8_t)dp_nt4(a < A.D.n_text ? A.D.text[a] : 0u); }
-                    if (!same) for (uint32_t k = lane; k < (uint32_t)ref_len_u; k += 64) { const uint64_t a = aln_pos + k; L.line[AFS_LINE / 2 + k] = (uint8_t)dp_nt4(a < A.D.n_text ? A.D.text[a] : 0u); }
-                    __syncthreads();
-                }
-                if (mapped) nm = afs_md(G.A.D, L, L.lcig, n_lcig, lifted, true, n_md, win ? L.line : nullptr);
-                lift_nm = same ? nm : afs_md(G.A.D, L, L.cig, n_cig, aln_pos, false, dummy, win ? L.line + AFS_LINE / 2 : nullptr);
-                if (n_md > AFS_MAXMD) { to_host = true; if (lane == 0) atomicAdd(&G.ctr[AFC_WHY + AF_WHY_CIGAR], 1u); }
-            }
-            __syncthreads();
-            AF_STAMP(fw2); AF_PROF(G, 17, fw1, fw2);
-            AFW_CUT(4096)      // ... after MD / NM / MAPQ
-            // ---- the segments of the line (sam.hpp:144-188), lane 0 ----
-            if (lane == 0 && !to_host) {
-                uint32_t n = 0, q = 0;
-                afs_push(L, n, q, SK_RNAME, 0, (uint32_t)(n1 - n0));
-                if (!aligned) {
-                    afs_lits(L, n, q, LT_UNAL, 19);
-                    L.seq_at = q; afs_push(L, n, q, SK_SEQ, 0, m); afs_lits(L, n, q, LT_TAB, 1);
-                    L.qual_at = F.quals ? q : ~0u;
-                    if (F.quals) afs_push(L, n, q, SK_QUAL, 0, m); else afs_lits(L, n, q, LT_STAR, 1);
-                    afs_lits(L, n, q, LT_NL, 1);
-                } else {
-                    afs_lits(L, n, q, LT_TAB, 1); afs_num(L, n, q, strand ? 16 : 0); afs_lits(L, n, q, LT_TAB, 1);
-                    if (mapped) afs_push(L, n, q, SK_NAME, lsid, NAME_LEN(lsid)); else afs_lits(L, n, q, LT_STAR, 1);
-                    afs_lits(L, n, q, LT_TAB, 1); afs_num(L, n, q, mapped ? pos1 : 0); afs_lits(L, n, q, LT_TAB, 1); afs_num(L, n, q, mapq); afs_lits(L, n, q, LT_TAB, 1);
-                    if (mapped) afs_cigar(L, n, q, L.lcig, n_lcig, L.lcig_off, 0u); else afs_lits(L, n, q, LT_STAR, 1);
-                    afs_lits(L, n, q, LT_MATE, 7);
-                    L.seq_at = q; afs_push(L, n, q, SK_SEQ, 0, m); afs_lits(L, n, q, LT_TAB, 1);
-                    L.qual_at = F.quals ? q : ~0u;
-                    if (F.quals) afs_push(L, n, q, SK_QUAL, 0, m); else afs_lits(L, n, q, LT_STAR, 1);
-                    afs_lits(L, n, q, LT_AS, 6); afs_num(L, n, q, score); afs_lits(L, n, q, LT_NM, 6); afs_num(L, n, q, mapped ? nm : 0);
-                    if (score2 != 0) { afs_lits(L, n, q, LT_ZS, 6); afs_num(L, n, q, score2); }
-                    afs_lits(L, n, q, LT_MD, 6);
-                    {   // the MD string as one segment: where every item's text starts
-                        uint32_t w = 0;
-                        for (uint32_t k = 0; k < n_md; ++k) {
-                            const uint32_t it = L.md_item[k], ty = it & 3u;
-                            L.md_off[k] = (uint16_t)w;
-                            w += afs_ndig((it >> 2) & 0x3FFu) + (ty == 1 ? 1u : ty == 2 ? 1u + ((it >> 12) & 0x1FFu) : 0u);
-                        }
-                        L.md_off[n_md] = (uint16_t)w;
-                        afs_push(L, n, q, SK_MD, n_md, w);
-                    }
-                    afs_lits(L, n, q, LT_OA, 6); afs_push(L, n, q, SK_NAME, sid, NAME_LEN(sid));
-                    afs_lits(L, n, q, LT_COMMA, 1); afs_num(L, n, q, oa_pos); afs_lits(L, n, q, strand ? LT_MINUS : LT_PLUS, 3);
-                    afs_cigar(L, n, q, L.cig, n_cig, L.cig_off, 1u);
-                    afs_lits(L, n, q, LT_COMMA, 1); afs_num(L, n, q, mapq); afs_lits(L, n, q, LT_COMMA, 1); afs_num(L, n, q, lift_nm); afs_lits(L, n, q, LT_SEMI, 1);
-                    afs_lits(L, n, q, LT_AA, 6);
-                    for (uint32_t k = 0; k < n_alt; ++k) {
-                        const uint32_t s2 = L.alt_sid[k];
-                        afs_push(L, n, q, SK_NAME, s2, NAME_LEN(s2));
-                        afs_lits(L, n, q, LT_COMMA, 1); afs_num(L, n, q, (int)L.alt_p1[k]); afs_lits(L, n, q, LT_COMMA, 1); afs_num(L, n, q, L.alt_score[k]); afs_lits(L, n, q, LT_SEMI, 1);
-                    }
-                    afs_lits(L, n, q, LT_NL, 1);
-                }
-                if (n <= AFS_MAXSEG) L.seg_off[n] = (uint16_t)(q < 0xFFFFu ? q : 0xFFFFu);
-                L.n_seg = n; L.total = q;
-            }
-            __syncthreads();
-            AF_STAMP(fw3); AF_PROF(G, 18, fw2, fw3);
-            AFW_CUT(8192)      // ... after the segment list
-            const uint32_t n_seg = to_host ? 0u : L.n_seg;
-            p = to_host ? 0u : L.total;
-            if (!to_host && (n_seg > AFS_MAXSEG || p > AFS_LINE)) { to_host = true; if (lane == 0) atomicAdd(&G.ctr[AFC_WHY + AF_WHY_CAPACITY], 1u); }
-            if (!to_host) {
-                // ---- SEQ and QUAL are plain copies; every lane renders its share of the other bytes of the line ----
-                const uint32_t s_at = L.seq_at, q_at = L.qual_at, holes = m + (q_at != ~0u ? m : 0u);
-                if (s_at + m <= AFS_LINE) for (uint32_t k = lane; k < m; k += 64) L.line[s_at + k] = L.seq[k];
-                if (q_at != ~0u && q_at + m <= AFS_LINE) for (uint32_t k = lane; k < m; k += 64) L.line[q_at + k] = F.quals[strand ? off + m - 1 - k : off + k];
-                for (uint32_t i = lane; i + holes < p; i += 64) {
-                    uint32_t b = i;
-                    if (b >= s_at) b += m;
-                    if (q_at != ~0u && b >= q_at) b += m;
-                    uint32_t lo = 0, hi = n_seg;                       // last segment that starts at or before b
-                    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if ((uint32_t)L.seg_off[mid] <= b) lo = mid; else hi = mid; }
-                    const uint32_t d = b - L.seg_off[lo], kind = L.seg_kind[lo], val = L.seg_val[lo];
-                    uint8_t ch;
-                    if (kind == SK_LIT) ch = (uint8_t)afs_lit[val + d];
-                    else if (kind == SK_NUM || kind == SK_NEG) {
-                        const uint32_t len = (uint32_t)L.seg_off[lo + 1] - L.seg_off[lo];
-                        if (kind == SK_NEG && d == 0) ch = '-';
-                        else { uint32_t u = val; for (uint32_t t = d + 1; t < len; ++t) u /= 10u; ch = (uint8_t)('0' + u % 10u); }
-                    }
-                    else if (kind == SK_SEQ) ch = L.seq[d];
-                    else if (kind == SK_QUAL) ch = F.quals[strand ? off + m - 1 - d : off + d];
-                    else if (kind == SK_NAME) ch = names_lds ? L.names[L.name_off[val] + d] : F.snames[F.sname_off[val] + d];
-                    else if (kind == SK_RNAME) ch = F.rnames[n0 + d];
-                    else if (kind == SK_CIG) {          // operation k of a CIGAR: its length, then its letter
-                        const uint16_t* offs = (val & 1u) ? L.cig_off : L.lcig_off; const uint32_t* cg = (val & 1u) ? L.cig : L.lcig;
-                        uint32_t a = 0, z = val >> 1;
-                        while (z - a > 1) { const uint32_t mid = (a + z) >> 1; if ((uint32_t)offs[mid] <= d) a = mid; else z = mid; }
-                        const uint32_t e = d - offs[a], nd = (uint32_t)offs[a + 1] - offs[a] - 1u;
-                        if (e == nd) ch = (uint8_t)afs_lit[LT_OPS + (cg[a] & 0xfu)];
-                        else { uint32_t u = cg[a] >> 4; for (uint32_t t = e + 1; t < nd; ++t) u /= 10u; ch = (uint8_t)('0' + u % 10u); }
-                    } else {                            // SK_MD: item k of the MD string: the count of matches, then the base or ^ and the deleted bases
-                        uint32_t a = 0, z = val;
-                        while (z - a > 1) { const uint32_t mid = (a + z) >> 1; if ((uint32_t)L.md_off[mid] <= d) a = mid; else z = mid; }
-                        const uint32_t it = L.md_item[a], ty = it & 3u, run = (it >> 2) & 0x3FFu, e = d - L.md_off[a], nd = afs_ndig(run);
-                        if (e < nd) { uint32_t u = run; for (uint32_t t = e + 1; t < nd; ++t) u /= 10u; ch = (uint8_t)('0' + u % 10u); }
-                        else if (ty == 1) { const uint32_t bc = (it >> 12) & 7u; ch = (uint8_t)afs_lit[LT_BASES + (bc > 4 ? 4 : bc)]; }
-                        else if (e == nd) ch = '^';
-                        else { const uint64_t ta = lifted + (it >> 21) + (e - nd - 1u); ch = (uint8_t)afs_lit[LT_BASES + dp_nt4(ta < A.D.n_text ? A.D.text[ta] : 0u)]; }
-                    }
-                    L.line[b] = ch;
-                }
-            }
-            AF_STAMP(fw4); AF_PROF(G, 19, fw3, fw4);
-        }
-        __syncthreads();
-        AF_STAMP(fw6);
-        // ---- out: the text pool (8-byte words, bump-allocated), coalesced; the record ----
-        if (to_host) rec.status = 2;           // does not fit the staging: the host pipeline redoes the read
-        else {
-            const unsigned long long words = (unsigned long long)((p + 7) >> 3);
-            const uint32_t shard = blockIdx.x % AF_TXT_SHARDS;
-            unsigned long long to = 0;
-            if (lane == 0) to = atomicAdd(&G.txt_cur[shard * 8], words);
-            to = ((unsigned long long)(uint32_t)__shfl((int)(to >> 32), 0) << 32) | (uint32_t)__shfl((int)(to & 0xFFFFFFFFull), 0);
-            if (to + words > G.txt_shard_words) rec.status = 2;
-            else {
-                to += (unsigned long long)(shard + 1) * G.txt_shard_words;
-                const uint64_t* src = reinterpret_cast<const uint64_t*>(L.line);
-                for (unsigned long long k = lane; k < words; k += 64) F.txt_pool[to + k] = src[k];
-                rec.txt_len = p; rec.txt_off = to;
-            }
-        }
-        if (lane == 0) {
-            A.recs[r_in] = rec;
-            if (A.dev_len) {
-                A.dev_len[r_in] = rec.txt_len; A.dev_off[r_in] = rec.txt_off;
-                if (rec.status == 2 || rec.txt_len == 0) atomicAdd(&A.dev_sum[0], 1ull);
-                else if (rec.status == 1) atomicAdd(&A.dev_sum[8 + 8 * (blockIdx.x % 16)], 1ull);      // sharded: one address takes only ~50 M atomics/s
-            }
-        }
-        AF_STAMP(fw7); AF_PROF(G, 21, fw6, fw7); AF_PROF(G, 22, fw0, fw7);
-    }
-#undef TB
-#undef ANCH
-#undef NAME_LEN
-}
-
-
 // ------------------------------------------------------------------------------------------------------------------------------
-// finish_prep_kernel + finish_render_kernel: finish_wave_kernel's work in two kernels.  What lane 0 of a wavefront did alone there - stitch the CIGAR
-// (aligner_ksw2.hpp:3049-3108), lift it (:3133-3160), MAPQ (mapq.hpp:146-184), and the MD / NM walks (sam.hpp:249-287), which were 64 columns wide but a
-// few items long - is ONE LANE's work per read here: 64 reads per wavefront, 1 / 64 of the wavefront instructions (finish_wave_kernel issued ~3500 per
-// read, 63 of 64 lanes idle in two thirds of them: profiles/r04t).  The lane leaves a "recipe" in HBM (AFP_WORDS words per read: header numbers, the
-// alternatives, the stitched and the lifted CIGAR, the MD items).  finish_render_kernel, one wavefront per read, lays the line's segments
-// out BY ALL LANES (a segment's kind and length follow from its index; offsets by a wavefront scan - finish_wave_kernel's lane 0 listed them one by one),
-// has every piece of the line written by the lanes that own it (render_core.h) and stores the bytes as before.  Same bytes, same records, same hand-overs
-// to the host pipeline.
+// finish_prep_kernel + finish_render_kernel: the same work as finish_kernel with the SAM line spelled on the GPU, in two kernels.  The serial work of a
+// read - stitch the CIGAR (aligner_ksw2.hpp:3049-3108), lift it (:3133-3175), MAPQ (mapq.hpp:146-184, in IEEE double operations in the reference's order),
+// and the MD / NM walks (write_MD_core, sam.hpp:249-287), which are a few items long - is ONE LANE's work per read: 64 reads per wavefront (a wavefront
+// per read issued ~3500 instructions per read for it, 63 of 64 lanes idle in two thirds of them: profiles/r04t).  The lane leaves a "recipe" in HBM
+// (AFP_WORDS words per read: header numbers, the alternatives, the stitched and the lifted CIGAR, the MD items).  finish_render_kernel, one wavefront
+// per read, lays the line's segments out BY ALL LANES (a segment's kind and length follow from its index; offsets by a wavefront scan - no lane lists
+// them one by one), has every piece of the line written by the lanes that own it (render_core.h) and stores the bytes of the line, assembled in LDS,
+// with coalesced stores.  A line, CIGAR or MD beyond the staging goes to the host pipeline.
 // ------------------------------------------------------------------------------------------------------------------------------
 #define AFP_WORDS 512u
 #define AFP_CIG 64u
@@ -3201,7 +2859,7 @@ __device__ __forceinline__ int afl_md(const dp_launch_t& D, const afl_two_t& W, 
                         const uint64_t a = t + k;
                         const uint32_t tc = a < D.n_text ? dp_nt4(afl_at(TS, (uint32_t)(a - t0))) : dp_nt4(0u);
                         const uint32_t rb = q + k < m ? afl_at(RS, q + k) : 0u;
-                        const uint32_t rc = dp_nt4(strand ? (uint32_t)ak_compl((uint8_t)rb) : rb);          // the read in alignment orientation (kpbseq.h:120-137), as finish_wave_kernel stages it
+                        const uint32_t rc = dp_nt4(strand ? (uint32_t)ak_compl((uint8_t)rb) : rb);          // the read in alignment orientation (kpbseq.h:120-137)
                         if (rc != tc) {
                             if (items) { if (ni < AFS_MAXMD) md[ni] = 1u | ((l_MD & 0x3FFu) << 2) | (tc << 12); if (l_MD > 0x3FFu) bad = true; }
                             ++ni; ++NM; l_MD = 0;

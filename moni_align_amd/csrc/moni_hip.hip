@@ -1359,12 +1359,10 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         double prof[7] = {0, 0, 0, 0, 0, 0, 0};
         uint64_t why_sum[AF_WHY_N] = {};
         double hist[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cyc[7] = {0, 0, 0, 0, 0, 0, 0};
-        uint64_t waves_used = 0;
 
         // SAM text in the kernel (default; MONI_ALIGN_HOST_FORMAT=1 leaves the formatting to the host stage): read names and
         // qualities go to the device while the seeding runs
         const bool gpu_text = getenv("MONI_ALIGN_HOST_FORMAT") == nullptr && NR > 0;
-        const bool fin_v1 = getenv("MONI_AF_FIN_V1") != nullptr;          // finish_wave_kernel (one wavefront per read for all of it) instead of finish_prep_kernel + finish_render_kernel
         std::thread uploader;
         int rc_up = MONI_OK;
         if (gpu_text) {
@@ -1382,8 +1380,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
             });
         }
         struct JoinGuard { std::thread& t; ~JoinGuard() { if (t.joinable()) t.join(); } } join_guard{uploader};
-        // The staged kernels (align_fast.hip) take the common case; align_kernel takes the reads they hand over (MONI_ALIGN_V1=1: every read)
-        static const bool use_fast = getenv("MONI_ALIGN_V1") == nullptr;
+        // The staged kernels (align_fast.hip) take the common case; align_kernel takes the reads they hand over
         // seeding runs over the whole batch before the align kernels of its sub-batches (seeding sub-batch k+1 beside the align kernels of
         // sub-batch k was measured in round 2 and did not pay inside one context: the two align streams already fill the GPU; a streaming
         // caller gets that overlap from two or three contexts per GPU)
@@ -1421,7 +1418,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         }
         int n_cu = 256;
         n_cu = ctx_n_cu(c);
-        const uint64_t ak_waves = use_fast ? std::min<uint64_t>(waves_full, 1024) : waves_full;       // in-flight read slots of align_kernel (75 KB each)
+        const uint64_t ak_waves = std::min<uint64_t>(waves_full, 1024);       // in-flight read slots of align_kernel (75 KB each): it takes only the reads handed over
         if ((rc = c->ak_slots.ensure(AK_NSET * ak_waves * AK_NL)) || (rc = c->ak_waves.ensure(AK_NSET * ak_waves)) || (rc = c->h_recs.ensure(NR + 1)) ||
             (rc = c->h_cig.ensure(cig_per * n_sub + 1)) || (rc = c->h_alt.ensure(alt_per * n_sub + 1)) || (rc = c->h_md.ensure(md_per * n_sub + 1)) || (rc = c->ak_minscore.ensure(msc.size())) ||
             (rc = c->ak_cursors.ensure(AK_CUR * n_sub + AK_CUR)))
@@ -1441,7 +1438,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         const unsigned af_fin_grid = (unsigned)std::min<uint64_t>((sub_reads + 63) / 64, (uint64_t)n_cu * 16);
         // in-order text on the GPU: when the caller takes the context-owned buffer and the kernels spell the text, every sub-batch's lines are
         // put in read order on the device and arrive with one transfer; the host threads are needed only for sub-batches with hand-backs
-        const bool inorder = use_fast && gpu_text && ctx_out && force_back == 0 && getenv("MONI_ALIGN_HOST_ORDER") == nullptr;
+        const bool inorder = gpu_text && ctx_out && force_back == 0 && getenv("MONI_ALIGN_HOST_ORDER") == nullptr;
         if (inorder && ((rc = c->ak_recs.ensure(NR + 1)) || (rc = c->ak_block.ensure(txt_per * n_sub + 8)) || (rc = c->ak_dev_len.ensure(NR + n_sub + 8)) || (rc = c->ak_dev_off.ensure(NR + n_sub + 8)) ||
                         (rc = c->ak_dev_pos.ensure(NR + 2 * n_sub + 8)) || (rc = c->ak_dev_sum.ensure(160 * n_sub + 8)) || (rc = c->h_sum.ensure(4 * n_sub + 4)))) return rc;
         size_t gather_tmp_bytes = 0;
@@ -1450,11 +1447,11 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
             for (int x = 0; x < AK_NSET; ++x) if ((rc = c->gather_tmp[x].ensure(gather_tmp_bytes + 16))) return rc;
         }
         if (inorder) { HIPCHK(hipMemsetAsync(c->ak_dev_sum.p, 0, (160 * n_sub + 8) * sizeof(unsigned long long), c->stream)); memset(c->h_sum.p, 0, (4 * n_sub + 4) * sizeof(unsigned long long)); }
-        if (use_fast) for (int x = 0; x < (int)std::min<uint64_t>(n_sub, AK_NSET); ++x) {
+        for (int x = 0; x < (int)std::min<uint64_t>(n_sub, AK_NSET); ++x) {
             moni_ctx::AfSet& S = c->af[x];
             if ((rc = S.plans.ensure(sub_reads + 1)) || (rc = S.tasks.ensure(af_slot_cap)) || (rc = S.res.ensure(af_slot_cap)) || (rc = S.ntasks.ensure(sub_reads + 8)) || (rc = S.bin_q.ensure((size_t)(AF_NBIN + 1) * af_task_cap)) ||
                 (rc = S.task_pos.ensure(af_slot_cap)) || (rc = S.tb_task.ensure(af_tb_cap)) || (rc = S.tb.ensure(af_tb_cap)) || (rc = S.big_list.ensure(3 * (sub_reads + 1))) || (rc = S.ctab.ensure((size_t)(sub_reads + 1) * AF_CTAB)) || (af_runs_on() && ((rc = S.rstage.ensure(sub_reads + 1)) || (rc = S.rflag.ensure(sub_reads + 8)))) ||
-                (rc = S.ctr.ensure(AF_NCTR)) || (rc = S.txt_cur.ensure(AF_TXT_SHARDS * 8)) || (rc = S.bnd.ensure((size_t)af_dp_grid * AF_QCAP * 64)) || (rc = S.chunks.ensure(af_chunk_cap)) || (rc = S.dirs.ensure(af_dirs_cap)) || (rc = S.fin.ensure((size_t)af_fin_grid * 64 * sizeof(af_fin_t))) || (gpu_text && !fin_v1 && (rc = S.recipes.ensure((size_t)(sub_reads + 1) * AFP_WORDS))))
+                (rc = S.ctr.ensure(AF_NCTR)) || (rc = S.txt_cur.ensure(AF_TXT_SHARDS * 8)) || (rc = S.bnd.ensure((size_t)af_dp_grid * AF_QCAP * 64)) || (rc = S.chunks.ensure(af_chunk_cap)) || (rc = S.dirs.ensure(af_dirs_cap)) || (rc = S.fin.ensure((size_t)af_fin_grid * 64 * sizeof(af_fin_t))) || (gpu_text && (rc = S.recipes.ensure((size_t)(sub_reads + 1) * AFP_WORDS))))
                 return rc;
         }
         // the launches alternate between the context's stream and one more: HIP multiplexes streams onto a handful of hardware queues
@@ -1463,9 +1460,10 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream.h, hipStreamNonBlocking));
         while (c->ak_done.size() < n_sub) { Event e0, e1, e2; HIPCHK(hipEventCreate(&e0.h)); HIPCHK(hipEventCreate(&e1.h)); HIPCHK(hipEventCreate(&e2.h));
                                             c->ak_begin.push_back(std::move(e0)); c->ak_done.push_back(std::move(e1)); c->ak_fin.push_back(std::move(e2)); }
-        for (int x = 0; x < AK_NSET; ++x) if (use_fast && !c->fb_stream[x]) HIPCHK(hipStreamCreateWithFlags(&c->fb_stream[x].h, hipStreamNonBlocking));
+        for (int x = 0; x < AK_NSET; ++x) if (!c->fb_stream[x]) HIPCHK(hipStreamCreateWithFlags(&c->fb_stream[x].h, hipStreamNonBlocking));
         while (c->af_ev.size() < 3 * n_sub) { Event e; HIPCHK(hipEventCreate(&e.h)); c->af_ev.push_back(std::move(e)); }
-        if (use_fast) { if ((rc = c->fb_all.ensure(16 * n_sub + n_sub * (sub_reads + 1) + 16))) return rc; HIPCHK(hipMemsetAsync(c->fb_all.p, 0, 16 * n_sub * sizeof(uint32_t), c->stream)); }
+        if ((rc = c->fb_all.ensure(16 * n_sub + n_sub * (sub_reads + 1) + 16))) return rc;
+        HIPCHK(hipMemsetAsync(c->fb_all.p, 0, 16 * n_sub * sizeof(uint32_t), c->stream));
         HIPCHK(hipMemsetAsync(c->ak_cursors.p, 0, (AK_CUR * n_sub + AK_CUR) * sizeof(unsigned long long), c->stream));
         HIPCHK(hipMemcpyAsync(c->ak_minscore.p, msc.data(), msc.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1485,7 +1483,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
             if (getenv("MONI_AK_PROFILE")) fprintf(stderr, "  sub-batch %llu: waited for the launch from %.1f to %.1f ms\n", (unsigned long long)k, (f0 - t_enter) * 1e3, (f1 - t_enter) * 1e3);
             if (force_back) for (uint64_t r = 0; r < nr; ++r) if ((r0 + r) % force_back == 0) R.recs[r].status = 2;
             if (gpu_text) {        // the text the launch wrote: copy engine transfers next to the running kernels, one per used region of the pool
-                const uint64_t n_reg = use_fast ? AF_TXT_SHARDS + 1 : 1, reg_words = use_fast ? txt_per / (AF_TXT_SHARDS + 1) : txt_per;
+                const uint64_t n_reg = AF_TXT_SHARDS + 1, reg_words = txt_per / (AF_TXT_SHARDS + 1);
                 uint64_t used[AF_TXT_SHARDS + 1];
                 for (uint64_t g = 0; g < n_reg; ++g) used[g] = 0;
                 for (uint64_t r = 0; r < nr; ++r) if (R.recs[r].txt_len) {
@@ -1598,9 +1596,6 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         };
         for (uint64_t k = 0; k < n_sub; ++k) {
             const uint64_t r0 = sub_lo[k], nr = sub_lo[k + 1] - sub_lo[k];
-            uint64_t n_waves = ak_waves;
-            if (!use_fast && n_waves * AK_NL > nr) n_waves = (nr + AK_NL - 1) / AK_NL;
-            waves_used = std::max(waves_used, n_waves);
             ak_args_t A;
             memset(&A, 0, sizeof A);
             A.P.min_len = prm->min_len; A.P.ext_len = prm->ext_len; A.P.check_k = prm->check_k; A.P.region_dist = prm->region_dist;
@@ -1617,23 +1612,22 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
             A.min_score_of_len = c->ak_minscore.p; A.max_len = (uint32_t)c->max_len + 1; A.read_lo = r0; A.n_reads = nr;
             A.slots = c->ak_slots.p + (k % AK_NSET) * ak_waves * AK_NL; A.waves = c->ak_waves.p + (k % AK_NSET) * ak_waves;
             // records: pinned host memory when host threads read them behind every launch; with the lines ordered on the GPU they are read only
-            // when a sub-batch has hand-backs, and stay in HBM until then (80 bytes per read over PCIe were what finish_wave_kernel waited for)
+            // when a sub-batch has hand-backs, and stay in HBM until then (80 bytes per read over PCIe were what the finish kernels waited for)
             A.recs = (inorder ? c->ak_recs.p : c->h_recs.p) + r0; A.cig_pool = c->h_cig.p + k * cig_per; A.cig_cap = cig_per; A.alt_pool = c->h_alt.p + k * alt_per;
             A.alt_cap = alt_per; A.md_pool = c->h_md.p + k * md_per; A.md_cap = md_per; A.cursors = c->ak_cursors.p + AK_CUR * k;
             if (gpu_text) {
                 A.fmt.rnames = c->ak_rnames.p; A.fmt.rname_off = c->ak_rname_off.p; A.fmt.quals = quals ? c->ak_quals.p : nullptr;
                 A.fmt.snames = I->d_snames.p; A.fmt.sname_off = I->d_sname_off.p; A.fmt.mapq_tab = c->ak_mapq_tab.p; A.fmt.mapq_tab_n = 8192;
                 A.fmt.min_len = (int32_t)prm->min_len; A.fmt.smatch = prm->smatch; A.fmt.smismatch = prm->smismatch;
-                A.fmt.txt_pool = c->ak_txt.p + k * txt_per; A.fmt.txt_cap = (use_fast && nr > 0) ? txt_per / (AF_TXT_SHARDS + 1) : txt_per;
+                A.fmt.txt_pool = c->ak_txt.p + k * txt_per; A.fmt.txt_cap = txt_per / (AF_TXT_SHARDS + 1);
             }
             if (inorder) { A.dev_len = c->ak_dev_len.p + r0 + k; A.dev_off = c->ak_dev_off.p + r0 + k; A.dev_sum = c->ak_dev_sum.p + 160 * k; }
             hipStream_t sx = c->ak_stream[k % AK_NSET];
-            // (the set's buffers are free once its previous sub-batch is through finish_wave_kernel - stream order; align_kernel and the gather of that
+            // (the set's buffers are free once its previous sub-batch is through finish_render_kernel - stream order; align_kernel and the gather of that
             // sub-batch read only per-sub-batch buffers and may still be running on the hand-over stream: a slow hand-over read delays its own
             // sub-batch's block, not the launches behind it)
             HIPCHK(hipEventRecord(c->ak_begin[k], sx));
-            bool done_recorded = false;
-            if (use_fast && nr > 0) {
+            if (nr > 0) {
                 moni_ctx::AfSet& S = c->af[k % AK_NSET];
                 af_args_t G;
                 memset(&G, 0, sizeof G);
@@ -1664,14 +1658,11 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                 if (const char* v = getenv("MONI_AF_DBG")) G.dbg |= (uint32_t)atoi(v) & (64u | 65536u | 131072u);          // any build: 64 the serial anchor sort (cross-check), 65536 every global problem through the full-matrix kernel, 131072 every extension / gap fill through the tile kernels
                 HIPCHK(hipMemsetAsync(S.ctr.p, 0, AF_NCTR * sizeof(uint32_t), sx));
                 // LEVEL 0's instance: the small one, or - reads of more than 200 bases, whose seeds have more occurrences than it holds - the middle one
-                static const int l0_force = getenv("MONI_AF_L0") ? atoi(getenv("MONI_AF_L0")) : -1;          // 0 small, 1 middle
-                const bool l0_mid = l0_force >= 0 ? l0_force == 1 : c->max_len > 200;
+                const bool l0_mid = c->max_len > 200;
                 G.l0_mm = l0_mid ? (uint32_t)af_wave_mid_t::MM : (uint32_t)af_wave_small_t::MM; G.l0_ma = l0_mid ? (uint32_t)af_wave_mid_t::MA : (uint32_t)af_wave_small_t::MA;
-                const bool no_k2 = getenv("MONI_AF_NOPLANK") != nullptr;          // (measurement: the LEVEL-0 instance runs the selection loop and builds the plan itself, as the others do)
-                G.ctab = (no_k2 || l0_mid) ? nullptr : S.ctab.p;
-                // the runs' route (chain_runs_kernel): where the small plain instance chains one read per wavefront and plan_kernel takes the chain table
-                static const int l0_gw = getenv("MONI_AF_GW") ? atoi(getenv("MONI_AF_GW")) : 64;          // lanes of a read in the small instance (below)
-                G.rstage = (G.ctab && af_runs_on() && !(G.dbg & 64) && G.chain_narrow && l0_gw != 16) ? S.rstage.p : nullptr;
+                G.ctab = l0_mid ? nullptr : S.ctab.p;          // the small instance leaves its chains for plan_kernel; the middle one runs the selection loop and builds the plan itself, as the larger ones do
+                // the runs' route (chain_runs_kernel): where the small plain instance chains the read and plan_kernel takes the chain table
+                G.rstage = (G.ctab && af_runs_on() && !(G.dbg & 64) && G.chain_narrow) ? S.rstage.p : nullptr;
 #if defined(AF_PROFILE) || defined(AF_CUTS)
                 if (G.dbg & (4u | 8u | 16u | 32u | 128u | 256u | 512u | 1024u)) G.rstage = nullptr;      // the cut points of a phase split lie in the in-place path: every read stays there
 #endif
@@ -1680,27 +1671,15 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                 hipLaunchKernelGGL(classify_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, sx, G);
                 // MONI_AF_DBG=64, or chaining parameters beyond cc_narrow_ok, launch the general instances, which hold the serial sorts and the 64-bit chaining DP;
                 // the others have no call and no stack in them
-#define AF_LAUNCH_CP(WT, LEVEL, OCC, GW, grid) do { \
-                    if ((G.dbg & 64) || !G.chain_narrow) hipLaunchKernelGGL((chain_plan_kernel<WT, LEVEL, OCC, GW, true>), grid, dim3(64), 0, sx, G); \
-                    else hipLaunchKernelGGL((chain_plan_kernel<WT, LEVEL, OCC, GW, false>), grid, dim3(64), 0, sx, G); } while (0)
-                if (l0_mid) {
-                    const dim3 g1((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * 4 * 4));
-                    AF_LAUNCH_CP(af_wave_mid_t, 0, 4, 64, g1);
-                } else {
-                    // four reads per wavefront (16 lanes each, 4 x 4.6 KB of LDS): 8 wavefronts = 32 reads in flight per CU, as with one read per wavefront at
-                    // 8 waves/SIMD, but the one-lane sections issue a quarter of the instructions.  MONI_AF_GW=64: one read per wavefront (MONI_AF_K1OCC waves/SIMD)
-                    static const int k1occ = getenv("MONI_AF_K1OCC") ? atoi(getenv("MONI_AF_K1OCC")) : (l0_gw == 16 ? 2 : 8);      // one read per wavefront: measured 5, 6, 8 waves/SIMD
-                    const dim3 g1((unsigned)std::min<uint64_t>(l0_gw == 16 ? (nr + 3) / 4 : nr, (uint64_t)n_cu * 4 * k1occ));
-                    if (l0_gw == 16) AF_LAUNCH_CP(af_wave_small_t, 0, 2, 16, g1);
-                    else if (k1occ == 4) AF_LAUNCH_CP(af_wave_small_t, 0, 4, 64, g1);
-                    else if (k1occ == 5) AF_LAUNCH_CP(af_wave_small_t, 0, 5, 64, g1);
-                    else if (k1occ == 8) AF_LAUNCH_CP(af_wave_small_t, 0, 8, 64, g1);
-                    else AF_LAUNCH_CP(af_wave_small_t, 0, 6, 64, g1);
-                }
+                // OCC: the waves per SIMD an instance is compiled for; its grid is what is resident at that occupancy (4 SIMDs per CU)
+#define AF_LAUNCH_CP(WT, LEVEL, OCC, grid) do { \
+                    if ((G.dbg & 64) || !G.chain_narrow) hipLaunchKernelGGL((chain_plan_kernel<WT, LEVEL, OCC, true>), grid, dim3(64), 0, sx, G); \
+                    else hipLaunchKernelGGL((chain_plan_kernel<WT, LEVEL, OCC, false>), grid, dim3(64), 0, sx, G); } while (0)
+                if (l0_mid) AF_LAUNCH_CP(af_wave_mid_t, 0, 4, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * 4 * 4)));
+                else AF_LAUNCH_CP(af_wave_small_t, 0, 8, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * 4 * 8)));          // (measured at 5, 6 and 8 waves/SIMD)
                 if (G.rstage) hipLaunchKernelGGL(chain_runs_kernel, dim3((unsigned)std::min<uint64_t>((nr + 3) / 4, (uint64_t)n_cu * 40)), dim3(64), 0, sx, G);      // feeds big_list: ahead of LEVEL 1
-                AF_LAUNCH_CP(af_wave_t, 1, 3, 64, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * 10)));
-                static const bool no_huge = getenv("MONI_AF_NOHUGE") != nullptr;          // (debugging aid: reads beyond the large instance then go straight to align_kernel)
-                if (!no_huge) AF_LAUNCH_CP(af_wave_huge_t, 2, 1, 64, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu)));      // ~90 KB of LDS per wave: one per CU
+                AF_LAUNCH_CP(af_wave_t, 1, 3, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * 10)));
+                AF_LAUNCH_CP(af_wave_huge_t, 2, 1, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu)));      // ~90 KB of LDS per wave: one per CU
 #undef AF_LAUNCH_CP
                 HIPCHK(hipGetLastError());
                 if (G.ctab) hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, sx, G);
@@ -1712,18 +1691,17 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                 hipLaunchKernelGGL(traceback_kernel, dim3((unsigned)((af_tb_cap + 255) / 256)), dim3(256), 0, sx, G);
                 HIPCHK(hipEventRecord(c->af_ev[3 * k + 2], sx));
                 // the reads the staged kernels handed over: few, but each a long serial job (milliseconds): align_kernel takes them on its own stream
-                // beside finish_wave_kernel, which hands nothing over any more (a line or CIGAR beyond its staging goes to the host pipeline)
+                // beside the finish kernels, which hand nothing over (a line or CIGAR beyond their staging goes to the host pipeline)
                 A.read_list = G.fb_list; A.n_reads_dev = G.fb_n;
                 hipStream_t sf = c->fb_stream[k % AK_NSET];
                 HIPCHK(hipStreamWaitEvent(sf, c->af_ev[3 * k + 2], 0));
                 hipLaunchKernelGGL(align_kernel, dim3((unsigned)ak_waves), dim3(64), 0, sf, A);
-                // the record and the SAM line of every read that stayed on the staged path: one wave per read when the kernel spells the text
-                static const int fin_mult = getenv("MONI_AF_FINGRID") ? atoi(getenv("MONI_AF_FINGRID")) : 96;          // blocks per CU: 4x what is resident (24 by LDS), so that the strided share of a block is short and the tail even (measured 24 .. 768)
-                if (gpu_text && !fin_v1) {          // a lane per read for the serial work (CIGAR, lift, MD / NM, MAPQ -> a recipe), then a wavefront per read for the line
+                // the record and the SAM line of every read that stayed on the staged path
+                constexpr uint64_t FIN_RENDER_BLOCKS_PER_CU = 96;          // 4x what is resident (24 by LDS), so that the strided share of a block is short and the tail even (measured 24 .. 768)
+                if (gpu_text) {          // a lane per read for the serial work (CIGAR, lift, MD / NM, MAPQ -> a recipe), then a wavefront per read for the line
                     hipLaunchKernelGGL(finish_prep_kernel, dim3((unsigned)std::min<uint64_t>((nr + 63) / 64, (uint64_t)n_cu * 32)), dim3(64), 0, sx, G, S.recipes.p);
-                    hipLaunchKernelGGL(finish_render_kernel, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * fin_mult)), dim3(64), 0, sx, G, (const uint32_t*)S.recipes.p);
-                } else if (gpu_text) hipLaunchKernelGGL(finish_wave_kernel, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * fin_mult)), dim3(64), 0, sx, G);
-                else hipLaunchKernelGGL(finish_kernel, dim3((unsigned)std::min<uint64_t>((nr + 63) / 64, af_fin_grid)), dim3(64), 0, sx, G);
+                    hipLaunchKernelGGL(finish_render_kernel, dim3((unsigned)std::min<uint64_t>(nr, (uint64_t)n_cu * FIN_RENDER_BLOCKS_PER_CU)), dim3(64), 0, sx, G, (const uint32_t*)S.recipes.p);
+                } else hipLaunchKernelGGL(finish_kernel, dim3((unsigned)std::min<uint64_t>((nr + 63) / 64, af_fin_grid)), dim3(64), 0, sx, G);
                 HIPCHK(hipMemcpyAsync(c->af_ctr_host.p + AF_NCTR * k, S.ctr.p, AF_NCTR * sizeof(uint32_t), hipMemcpyDeviceToHost, sx));      // (before the set's next sub-batch clears them)
                 HIPCHK(hipEventRecord(c->ak_fin[k], sx));
                 HIPCHK(hipStreamWaitEvent(sf, c->ak_fin[k], 0));
@@ -1739,11 +1717,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
                     HIPCHK(hipMemcpyAsync(c->h_sum.p + 4 * k, c->ak_dev_sum.p + 160 * k + 150, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, sf));
                 }
                 HIPCHK(hipEventRecord(c->ak_done[k], sf));
-                done_recorded = true;
-            } else if (nr > 0) {
-                hipLaunchKernelGGL(align_kernel, dim3((unsigned)n_waves), dim3(64), 0, sx, A);
-            }
-            if (!done_recorded) HIPCHK(hipEventRecord(c->ak_done[k], sx));
+            } else HIPCHK(hipEventRecord(c->ak_done[k], sx));
             HIPCHK(hipGetLastError());
             launched = k + 1;
         }
@@ -1757,18 +1731,18 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
             std::vector<unsigned long long> cur(AK_CUR * n_sub);
             HIPCHK(hipMemcpy(cur.data(), c->ak_cursors.p, cur.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             std::vector<uint32_t> fbn(16 * n_sub, 0);
-            if (use_fast) HIPCHK(hipMemcpy(fbn.data(), c->fb_all.p, fbn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(fbn.data(), c->fb_all.p, fbn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
             for (uint64_t k = 0; k < n_sub; ++k) {
                 const unsigned long long* q = cur.data() + AK_CUR * k;
                 st.dp_tasks += q[2]; st.dp_cells += q[3]; st.dp_reused += q[8]; st.dp_cells_reused += q[9];
-                if (use_fast && sub_lo[k + 1] > sub_lo[k]) {         // HIP-event times of the staged kernels' groups (they overlap with the other stream's: sums, not spans)
+                if (sub_lo[k + 1] > sub_lo[k]) {         // HIP-event times of the staged kernels' groups (they overlap with the other stream's: sums, not spans)
                     float ms = 0;
                     if (hipEventElapsedTime(&ms, c->ak_begin[k], c->af_ev[3 * k]) == hipSuccess) st.t_k_chain += ms / 1e3;
                     if (hipEventElapsedTime(&ms, c->af_ev[3 * k], c->af_ev[3 * k + 1]) == hipSuccess) st.t_k_dp += ms / 1e3;
                     if (hipEventElapsedTime(&ms, c->af_ev[3 * k + 1], c->af_ev[3 * k + 2]) == hipSuccess) st.t_k_select += ms / 1e3;
                     if (hipEventElapsedTime(&ms, c->af_ev[3 * k + 2], c->ak_fin[k]) == hipSuccess) st.t_k_finish += ms / 1e3;
                 }
-                if (use_fast) {         // the staged kernels' own counters
+                {         // the staged kernels' own counters
                     const uint32_t* fc = c->af_ctr_host.p + AF_NCTR * k;
                     unsigned long long cells, rb, cutc, slots; memcpy(&cells, fc + AFC_CELLS, 8); memcpy(&rb, fc + AFC_RBYTES, 8); memcpy(&cutc, fc + AFC_CUTCELLS, 8); memcpy(&slots, fc + AFC_SLOTS, 8);
                     st.dp_cells_cut += cutc; st.dp_slots += slots;
@@ -1797,12 +1771,10 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
         static_assert(AF_WHY_N == 12, "moni_align_stats_t::handover_why");
         for (int x = 0; x < AF_WHY_N; ++x) why_out[x] = why_sum[x];
 #ifdef AF_PROFILE
-        if (use_fast && n_sub) { unsigned long long pf[32]; for (int x = 0; x < (int)std::min<uint64_t>(n_sub, AK_NSET); ++x) { HIPCHK(hipMemcpy(pf, c->af[x].prof.p, sizeof pf, hipMemcpyDeviceToHost));
+        if (n_sub) { unsigned long long pf[32]; for (int x = 0; x < (int)std::min<uint64_t>(n_sub, AK_NSET); ++x) { HIPCHK(hipMemcpy(pf, c->af[x].prof.p, sizeof pf, hipMemcpyDeviceToHost));
             fprintf(stderr, "chain_plan_kernel wave cycles (set %d): load+filter+anchors %.3g, chain %.3g (sort %.3g, dp %.3g, ends+backtrack %.3g), lifts %.3g, plan %.3g, whole read %.3g\n", x,
-                    (double)pf[0], (double)pf[1], (double)pf[5], (double)pf[6], (double)pf[7], (double)pf[2], (double)pf[3], (double)pf[4]);
-            fprintf(stderr, "finish_wave_kernel wave cycles (set %d): stage + stitch + lift %.3g, MD / NM / MAPQ %.3g, segment list %.3g, render %.3g, out %.3g, whole read %.3g\n", x,
-                    (double)pf[16], (double)pf[17], (double)pf[18], (double)pf[19], (double)pf[21], (double)pf[22]); } }
-        if (use_fast && gpu_text && !fin_v1) for (uint64_t k = 0; k < n_sub; ++k) {          // finish_prep_kernel's wavefronts of every launch: when they ran, and what the slowest one held
+                    (double)pf[0], (double)pf[1], (double)pf[5], (double)pf[6], (double)pf[7], (double)pf[2], (double)pf[3], (double)pf[4]); } }
+        if (gpu_text) for (uint64_t k = 0; k < n_sub; ++k) {          // finish_prep_kernel's wavefronts of every launch: when they ran, and what the slowest one held
             const uint64_t nr = sub_lo[k + 1] - sub_lo[k];
             if (!nr) continue;
             const size_t pp_stride = (size_t)AFPP_WAVE * ((sub_reads + 63) / 64 + 1) + (size_t)AFPP_READ * (sub_reads + 1);
@@ -1831,7 +1803,7 @@ static int align_core(moni_ctx* c, const moni_read_batch_t* b, bool resident, bo
 #endif
         double ak_sum_ms = c->dp_kernel_ms_accum;
         if (n_sub) { float ms = 0; if (hipEventElapsedTime(&ms, c->ak_begin[0], c->ak_done[n_sub - 1]) == hipSuccess) c->dp_kernel_ms_accum = ms; }      // launches overlap: report the span
-        if (getenv("MONI_AK_PROFILE")) fprintf(stderr, "align_kernel: %.3f ms span (%.3f ms summed) in %llu launches, %llu waves x %d reads in flight; wave cycles: take+chain %.3g, later drives %.3g, DP %.3g; lane cycles in ac_init: load %.3g sort %.3g chain-dp %.3g backtrack %.3g\n", c->dp_kernel_ms_accum, ak_sum_ms, (unsigned long long)n_sub, (unsigned long long)waves_used, (int)AK_NL, prof[0], prof[1], prof[2], prof[3], prof[4], prof[5], prof[6]);
+        if (getenv("MONI_AK_PROFILE")) fprintf(stderr, "align_kernel: %.3f ms span (%.3f ms summed) in %llu launches, %llu waves x %d reads in flight; wave cycles: take+chain %.3g, later drives %.3g, DP %.3g; lane cycles in ac_init: load %.3g sort %.3g chain-dp %.3g backtrack %.3g\n", c->dp_kernel_ms_accum, ak_sum_ms, (unsigned long long)n_sub, (unsigned long long)ak_waves, (int)AK_NL, prof[0], prof[1], prof[2], prof[3], prof[4], prof[5], prof[6]);
         if (getenv("MONI_AK_PROFILE")) fprintf(stderr, "DP problems run, by live rows min(qlen,tlen) <=16 / <=32 / <=64 / >64: count %.3g %.3g %.3g %.3g, cells %.3g %.3g %.3g %.3g\n",
                                                hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7]);
         if (getenv("MONI_AK_PROFILE")) fprintf(stderr, "wave cycles inside the DP phase: per-read setup %.3g, memo lookups %.3g, DP by live rows <=16 / <=32 / <=64 / >64: %.3g %.3g %.3g %.3g; 1x1 problems answered in closed form: %.3g\n",

@@ -181,8 +181,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OC
         }
         __syncthreads();
         if (!fallback && na > 0) {
-            status = af_chain(G, L, na, avg, af_grp_t<64>(), WT::SEC && X.PP.secondary_chains != 0);
-            status = (uint32_t)__shfl((int)status, 0);
+            status = (uint32_t)__shfl((int)af_chain(G, L, na, avg, WT::SEC && X.PP.secondary_chains != 0), 0);
             __syncthreads();
             if (status == 0xFFu) { fallback = true; chains_ovf = true; status = AF_ST_UNALIGNED; }
             else if (status == AF_ST_CAND) {

@@ -1,11 +1,10 @@
 // pe_lines.hip - the two SAM lines of a pair written on the GPU: what the host finishing (pe_host.hpp: pe_emit_fast) does per pair -
 // per mate the lift-over of position and CIGAR, MD / NM of the lifted and of the unlifted alignment, the single-end MAPQ
 // (aligner_ksw2.hpp:3133-3175, sam.hpp:249-287, mapq.hpp:146-184), then the tail of paired_chain_score (aligner_ksw2.hpp:2200-2288: PNEXT / TLEN /
-// flags / compute_mapq_pe_bwa, or one mate placed by the other), remove_slash_mate, the two lines (sam.hpp:144-188) - in the form of
-// finish_wave_kernel: ONE WAVE PER PAIR, the line listed as segments by lane 0 and rendered by all lanes.  Input: the pair's pe_rec_t with its
-// CIGARs and alternatives in the pools, whoever wrote them (pe_finish_kernel, or pe_align_kernel for the pairs handed over).  Lines that do not
-// fit the staging (CIGAR, MD, segments, line length, more than PEL_MAX_ALT alternatives, a pair the kernels gave up on) are counted in dev_sum[0]:
-// the host then finishes that chunk (pe_host.hpp) - same bytes either way.
+// flags / compute_mapq_pe_bwa, or one mate placed by the other), remove_slash_mate, the two lines (sam.hpp:144-188) - ONE WAVE PER PAIR, the line listed
+// as segments by lane 0 and rendered by all lanes.  Input: the pair's pe_rec_t with its CIGARs and alternatives in the pools, whoever wrote them
+// (pe_finish_kernel, or pe_align_kernel for the pairs handed over).  Lines that do not fit the staging (CIGAR, MD, segments, line length, more than
+// PEL_MAX_ALT alternatives, a pair the kernels gave up on) are counted in dev_sum[0]: the host then finishes that chunk (pe_host.hpp) - same bytes either way.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -220,3 +220,31 @@ def test_pairs_of_more_than_64_anchors_with_secondary_chains():
     assert model.mean == st["ins_mean"] and model.std_dev == st["ins_std_dev"]
     if got != want:
         raise AssertionError("SAM differs at record %d:\n got: %s\nwant: %s" % first_diff(got, want))
+
+
+def test_reads_of_more_anchors_than_the_large_instance_holds(tmp_path, monkeypatch):
+    """a segment in 90 copies: a read of three seeds or more has more than 256 anchors (the large instance holds 256) and fewer than 2048 (the huge one's),
+    so classify_kernel lists it for the huge instance, and no read of the batch is handed to align_kernel for its anchors"""
+    from moni_align_amd import synth
+    rng = np.random.default_rng(11)
+    seg = ACGT[rng.integers(0, 4, size=SEG)]
+    seq = np.concatenate([np.concatenate([seg, ACGT[rng.integers(0, 4, size=GAP)]]) for _ in range(90)])
+    reads = []
+    for k in range(120):
+        p = int(rng.integers(0, SEG - READ))
+        r = _sub(seg[p:p + READ], [int(v) for v in rng.choice(READ, size=1 + k % 4, replace=False)])
+        reads.append(r if rng.random() < 0.5 else synth.revcomp(r[None, :])[0].copy())
+    c = Case(tmp_path, [seq], ["rep90"])
+    try:
+        arr = _arrays(reads)
+        want = oracle_text(c.oracle, arr)
+        counts = np.array([len(a) for a in anchors_of(fetch_seeds(c.ctx, arr))])
+        assert ((counts > 256) & (counts <= 2048)).sum() >= 20 and counts.max() <= 2048, sorted(set(counts.tolist()))
+        got, st = run(c.ctx, arr)
+        same(got, want)
+        assert "anchors" not in st["handover_why"] and "long_read" not in st["handover_why"], st
+        monkeypatch.setenv("MONI_AF_DBG", "64")          # the general form of the huge instance
+        got_serial, _ = run(c.ctx, arr)
+        same(got_serial, want)
+    finally:
+        c.close()

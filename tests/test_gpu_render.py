@@ -1,7 +1,7 @@
 """finish_render_kernel spells a SAM line from the recipe finish_prep_kernel leaves: the line is laid out with one lane per segment, every literal, number
 and sequence name is written by the lane that owns it, and the long pieces (the read's name, SEQ, QUAL, the CIGARs, MD) by all lanes together.  The bytes
-must not show any of that: the SAM text of moni_align_run equals the oracle's byte for byte, and equals what finish_wave_kernel (MONI_AF_FIN_V1, the older
-kernel that does all of it with one wavefront per read) writes, on batches built for the places where the layout takes another path: unaligned records and
+must not show any of that: the SAM text of moni_align_run equals the oracle's byte for byte, on batches built for the places where the layout takes another
+path: unaligned records and
 records without qualities; lines around the 1280 bytes of the LDS staging; sequence names read from HBM (more than AFW_NAMES = 1024 bytes of them, more than
 AFW_NSEQ = 126 sequences); no ZS tag; deletion items in MD; and more alternatives than one pass of the lanes holds segments for (36 + 6 per alternative > 64).
 Every test asserts on the oracle's own text that its batch holds the case it is there for."""
@@ -97,7 +97,7 @@ def medium_env(medium_case):
 
 
 @pytest.mark.parametrize("quals", [True, False])
-def test_mixed_batch_equals_the_oracle_and_the_one_kernel_path(medium_env, monkeypatch, quals):
+def test_mixed_batch_equals_the_oracle(medium_env, quals):
     oracle, ctx, arr = medium_env
     want = oracle_text(oracle, arr, quals)
     lines = want.split(b"\n")[:-1]
@@ -108,9 +108,6 @@ def test_mixed_batch_equals_the_oracle_and_the_one_kernel_path(medium_env, monke
     assert all((l.split(b"\t")[10] == b"*") != quals for l in lines)
     got, st = run(ctx, arr, quals)
     same(got, want)
-    monkeypatch.setenv("MONI_AF_FIN_V1", "1")
-    got_v1, _ = run(ctx, arr, quals)
-    same(got_v1, want)
 
 
 def test_lines_around_the_capacity_of_the_staging(tmp_path):
