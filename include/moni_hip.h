@@ -570,6 +570,47 @@ void moni_bgzf_params_default(moni_bgzf_params_t *p);
 int  moni_bgzf_compress(moni_ctx_t *ctx, const void *text, uint64_t len, const moni_bgzf_params_t *prm,
                         const uint8_t **out, uint64_t *out_len, moni_bgzf_stats_t *stats);
 
+/* ---- BAM output: SAM lines encoded as BAM records and deflated on the GPU -------------- */
+/* The records of SAM specification 4.2 with the bins of 5.3, made from SAM text (records only: every line ends in \n, has 11 or more
+ * tab-separated fields, no @ line) against the dictionary of the header that moni_bam_set_header was given.  The bytes are a function of
+ * (header text, record text, block_size, level) alone.  Integer tags take the smallest type (C S I for values from 0, c s i below); tag
+ * types other than A, i and Z are not produced by this library and make a bad line. */
+typedef struct { uint32_t block_size, level, eof;   /* as in moni_bgzf_params_t: the BAM stream goes through the same blocks */
+                 uint32_t raw;                      /* 1: the BAM bytes themselves, no BGZF (block_size, level and eof are still checked; eof is not applied) */
+                 uint32_t reserved[2]; } moni_bam_params_t;
+typedef struct { uint64_t in_bytes, lines, bam_bytes, out_bytes, blocks, bad_lines, first_bad_line; uint32_t bad_reason, pad;
+                 double t_encode, t_deflate, t_total; } moni_bam_stats_t;      /* HIP-event seconds of the encoder's and the deflater's kernels; host seconds of the call */
+/* why a line is a bad line (moni_bam_stats_t::bad_reason: the reason of line first_bad_line, the lowest bad index) */
+enum { MONI_BAM_OK = 0,
+       MONI_BAM_NEWLINE = 1,   /* the text does not end in \n (first_bad_line: the unterminated line; the other lines are not looked at: bad_lines = 1) */
+       MONI_BAM_AT = 2,        /* a line that begins with @ */
+       MONI_BAM_FIELDS = 3,    /* fewer than 11 fields */
+       MONI_BAM_QNAME = 4,     /* an empty QNAME or one of more than 254 bytes */
+       MONI_BAM_INT = 5,       /* FLAG, POS, MAPQ, PNEXT or TLEN is not -?[0-9]+ or leaves its range (uint16, [0, 2^31), uint8, [0, 2^31), (-2^31, 2^31)) */
+       MONI_BAM_RNAME = 6,     /* RNAME or RNEXT is neither * (= for RNEXT) nor a name of the dictionary */
+       MONI_BAM_CIGAR = 7,     /* not * or ([0-9]+[MIDNSHP=X])+, an op length of 2^28 or more, more than 65535 ops */
+       MONI_BAM_SEQ = 8,       /* an empty SEQ */
+       MONI_BAM_QUAL = 9,      /* QUAL is neither * nor as long as SEQ */
+       MONI_BAM_TAG = 10,      /* a tag that is not XX:T:value, or an A tag whose value is not one byte */
+       MONI_BAM_TAGINT = 11,   /* an i tag whose value is not -?[0-9]+ within [-2^31, 2^32) */
+       MONI_BAM_TAGTYPE = 12,  /* a tag type other than A, i, Z */
+       MONI_BAM_LENGTH = 13 }; /* a line of 2^28 bytes or more */
+void moni_bam_params_default(moni_bam_params_t *p);
+/* Parses the @SQ lines of a SAM header (SN: and LN: of each, in order), keeps the dictionary in the context - on the device too - and returns
+ * the uncompressed BAM header (magic, l_text, the text as given, n_ref, the references) in a buffer of the context: valid until the next
+ * moni_bam_set_header or moni_ctx_destroy on it.  The caller sends it through moni_bgzf_compress as blocks of its own.  A header may be set
+ * again.  MONI_EINVAL: a NULL argument, an @SQ line without SN: or with an LN: outside [1, 2^31), a name of more than 254 bytes, len of 2^31 or more. */
+int  moni_bam_set_header(moni_ctx_t *ctx, const char *sam_header, uint64_t len, const uint8_t **bam_header, uint64_t *bam_header_len);
+/* sam_lines: len bytes of host memory (the context's pinned SAM buffer is the intended caller).  The records stay on the device between the
+ * encoder and the deflater.  *out points into a pinned buffer of the context: valid until the next moni_bam_records, moni_bgzf_compress or
+ * moni_ctx_destroy on this context, not to be freed.  Records may straddle blocks.  As with moni_bgzf_compress, the resident read batch,
+ * moni_last_kernel_ms, moni_last_counters and every result a later *_fetch may want stay as they are.  stats may be NULL.
+ * MONI_EINVAL: a NULL ctx, prm, out or out_len; parameters moni_bgzf_compress refuses, eof or raw above 1, a non-zero reserved; sam_lines NULL
+ * with len > 0; no header set on this context; a bad line - then nothing is written (*out_len = 0) and stats, where given, carry bad_lines,
+ * first_bad_line (0-based, the minimum over all bad lines) and bad_reason.  len 0 gives MONI_OK and no byte (28 with eof and without raw). */
+int  moni_bam_records(moni_ctx_t *ctx, const void *sam_lines, uint64_t len, const moni_bam_params_t *prm,
+                      const uint8_t **out, uint64_t *out_len, moni_bam_stats_t *stats);
+
 /* ---- the reference's on-disk liftidx (<prefix>.ldx: include/aligner/liftidx.hpp:117-143 over include/common/seqidx.hpp:197-238) ---- */
 /* Both layouts load: the current one (u64 w after u) and the older one the reference's fixture data/Chr21.10.ldx has. */
 int moni_ldx_info(const char *path, uint64_t *n_seq, uint64_t *u, uint64_t *w, int *has_w);

@@ -38,6 +38,7 @@ EXPORTS = [
     "moni_approx_params_default", "moni_approx_run", "moni_approx_sizes", "moni_approx_fetch", "moni_approx_batch",
     "moni_mslong_params_default", "moni_ms_long_batch",
     "moni_bgzf_params_default", "moni_bgzf_compress",
+    "moni_bam_params_default", "moni_bam_set_header", "moni_bam_records",
 ]
 
 
@@ -139,6 +140,30 @@ class BgzfParamsC(C.Structure):
 class BgzfStatsC(C.Structure):
     _fields_ = [("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("matches", C.c_uint64),
                 ("literals", C.c_uint64), ("t_kernel", C.c_double), ("t_total", C.c_double)]
+
+
+class BamParamsC(C.Structure):
+    _fields_ = [("block_size", C.c_uint32), ("level", C.c_uint32), ("eof", C.c_uint32), ("raw", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class BamStatsC(C.Structure):
+    _fields_ = [("in_bytes", C.c_uint64), ("lines", C.c_uint64), ("bam_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("blocks", C.c_uint64),
+                ("bad_lines", C.c_uint64), ("first_bad_line", C.c_uint64), ("bad_reason", C.c_uint32), ("pad", C.c_uint32),
+                ("t_encode", C.c_double), ("t_deflate", C.c_double), ("t_total", C.c_double)]
+
+
+# moni_bam_stats_t::bad_reason (include/moni_hip.h: MONI_BAM_*)
+BAM_REASONS = ("OK", "NEWLINE", "AT", "FIELDS", "QNAME", "INT", "RNAME", "CIGAR", "SEQ", "QUAL", "TAG", "TAGINT", "TAGTYPE", "LENGTH")
+
+
+class BamBadLine(ValueError):
+    """moni_bam_records met a bad line and wrote nothing: .stats holds bad_lines, first_bad_line and bad_reason"""
+
+    def __init__(self, stats):
+        self.stats = stats
+        r = stats["bad_reason"]
+        super().__init__("moni_bam_records: %d bad line(s), the first is line %d (%s)" %
+                         (stats["bad_lines"], stats["first_bad_line"], BAM_REASONS[r] if r < len(BAM_REASONS) else r))
 
 
 class DpParamsC(C.Structure):
@@ -300,6 +325,11 @@ def lib():
         L.moni_bgzf_params_default.restype = None
         L.moni_bgzf_compress.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BgzfParamsC), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                          C.POINTER(BgzfStatsC)]
+        L.moni_bam_params_default.argtypes = [C.POINTER(BamParamsC)]
+        L.moni_bam_params_default.restype = None
+        L.moni_bam_set_header.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.moni_bam_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BamParamsC), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                       C.POINTER(BamStatsC)]
         _lib = L
     return _lib
 
@@ -724,6 +754,29 @@ class Ctx:
         _chk(self._L.moni_bgzf_compress(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(p), C.byref(out), C.byref(n), C.byref(st)),
              "moni_bgzf_compress")
         return C.string_at(out.value, n.value) if n.value else b"", {k: getattr(st, k) for k, _ in BgzfStatsC._fields_}
+
+    def bam_set_header(self, text) -> bytes:
+        """moni_bam_set_header: the dictionary of the @SQ lines of `text` (bytes or str) for this context's bam_records; returns the uncompressed
+        BAM header."""
+        t = text.encode() if isinstance(text, str) else bytes(text)
+        out, n = C.c_void_p(), C.c_uint64()
+        _chk(self._L.moni_bam_set_header(self._h, t, len(t), C.byref(out), C.byref(n)), "moni_bam_set_header")
+        return C.string_at(out.value, n.value)
+
+    def bam_records(self, data, block_size: int = 65280, level: int = 1, eof: bool = False, raw: bool = False):
+        """moni_bam_records: the SAM lines `data` (bytes, or a uint8 array) as BAM records in BGZF blocks, or with raw the records themselves.
+        Returns (bytes, stats: the fields of moni_bam_stats_t); raises BamBadLine, with the stats, where a line is a bad line."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        p = BamParamsC()
+        self._L.moni_bam_params_default(C.byref(p))
+        p.block_size, p.level, p.eof, p.raw = block_size, level, 1 if eof else 0, 1 if raw else 0
+        out, n, st = C.c_void_p(), C.c_uint64(), BamStatsC()
+        rc = self._L.moni_bam_records(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(p), C.byref(out), C.byref(n), C.byref(st))
+        stats = {k: getattr(st, k) for k, _ in BamStatsC._fields_ if k != "pad"}
+        if rc == -22 and st.bad_lines:
+            raise BamBadLine(stats)
+        _chk(rc, "moni_bam_records")
+        return C.string_at(out.value, n.value) if n.value else b"", stats
 
     def _locate_params(self, strands: int, max_occ: int) -> "LocateParamsC":
         p = LocateParamsC()

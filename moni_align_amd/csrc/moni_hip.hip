@@ -48,6 +48,7 @@
 #include "approx_kernels.hip"
 #include "mslong_kernels.hip"
 #include "bgzf_kernels.hip"
+#include "bam_kernels.hip"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "moni_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return MONI_ENODEV; } } while (0)
 
@@ -248,6 +249,11 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
         DBuf<uint8_t> text, out; DBuf<uint32_t> staging, tok; DBuf<uint64_t> len, off, pos; DBuf<unsigned long long> counters; HBuf<unsigned long long> h_sum;
         HBuf<uint8_t> h_out; Event e0, e1;
     } bz;
+    struct BamBufs {        // BAM output (bam_api.inc): the text, the newline counts per tile and their scan, the lines' starts, the records' sizes and offsets, the records and
+                            // their pinned copy (raw); the dictionary of the header that was set, on the device and as the kernels take it; grow-only
+        DBuf<uint8_t> text, out, names; DBuf<uint64_t> tile_cnt, tile_pos, starts, size, off; DBuf<bam_ref_t> refs; DBuf<uint32_t> slots; DBuf<unsigned long long> ctr;
+        HBuf<unsigned long long> h_sum; HBuf<uint8_t> h_out; std::vector<uint8_t> header; bam_dict_t dict = {}; bool has_header = false; Event e0, e1;
+    } bam;
     int n_cu_cached = 0, pe_occ_cached = 0;         // hipGetDeviceProperties / the occupancy query take a millisecond each: asked once per context
 };
 
@@ -2097,5 +2103,6 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "approx_api.inc"
 #include "mslong_api.inc"
 #include "bgzf_api.inc"
+#include "bam_api.inc"
 
 }  // extern "C"

@@ -88,6 +88,30 @@ static void bgzf_blocks(moni_ctx_t* c, const char* text, uint64_t len, bool eof,
     if (rc) die("moni_bgzf_compress failed (" + std::to_string(rc) + ")");
     *z = (const char*)o;
 }
+// --bam: `len` bytes of SAM lines as BAM records in BGZF blocks (moni_bam_records, against the header bam_header_blocks set on this context), in the
+// context's pinned buffer until its next call
+static void bam_blocks(moni_ctx_t* c, const char* text, uint64_t len, const char** z, uint64_t* zl) {
+    moni_bam_params_t bp; moni_bam_params_default(&bp);
+    const uint8_t* o = nullptr;
+    moni_bam_stats_t st;
+    const int rc = moni_bam_records(c, text, len, &bp, &o, zl, &st);
+    if (rc == MONI_EINVAL && st.bad_lines)
+        die("moni_bam_records: " + std::to_string(st.bad_lines) + " line(s) of a batch cannot be written as BAM records; the first is its line " + std::to_string(st.first_bad_line) +
+            " (reason " + std::to_string(st.bad_reason) + " of MONI_BAM_*)");
+    if (rc) die("moni_bam_records failed (" + std::to_string(rc) + ")");
+    *z = (const char*)o;
+}
+// --bam: the SAM header becomes the dictionary of every context that will encode records; bh: the BAM header, in cs[0]'s buffer
+static void bam_set_headers(const std::vector<moni_ctx_t*>& cs, const char* h, uint64_t hl, const uint8_t** bh, uint64_t* bhl) {
+    for (size_t k = cs.size(); k-- > 0;)
+        if (moni_bam_set_header(cs[k], h, hl, bh, bhl)) die("moni_bam_set_header failed: the SAM header's @SQ lines do not make a BAM dictionary");
+}
+// ... and the BAM header as BGZF blocks of its own, in cs[0]'s pinned buffer until its next call
+static void bam_header_blocks(const std::vector<moni_ctx_t*>& cs, const char* h, uint64_t hl, const char** z, uint64_t* zl) {
+    const uint8_t* bh = nullptr; uint64_t bhl = 0;
+    bam_set_headers(cs, h, hl, &bh, &bhl);
+    bgzf_blocks(cs[0], (const char*)bh, bhl, false, z, zl);
+}
 
 struct Batch {
     std::vector<uint8_t> seq, qual, names;
@@ -235,6 +259,8 @@ struct Args {
     bool dry_write = false;     // --dry-run-write: no GPU, but the single-end front end's batching runs - ranges, workers of all (absent) GPUs, blocks placed in input order - with placeholder records
     moni_pe_params_t PE;               // -d, -D (paired-end)
     bool find_orphan = true;           // -u switches orphan recovery off
+    bool bam = false;                  // --bam: the SAM lines as BAM records in BGZF blocks in <out>.bam, encoded and deflated on the GPU by the context that aligned them (moni_bam_records)
+    bool blocks() const { return bgzf || bam; }          // the output is a sequence of BGZF blocks
     bool bgzf = false;                 // --bgzf: the SAM text as BGZF blocks in <out>.gz, deflated on the GPU by the context that aligned it (moni_bgzf_compress)
 };
 
@@ -251,6 +277,7 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--dry-run-write")) { a.dry_run = true; a.dry_write = true; continue; }
         if (!strcmp(argv[i], "--ctx-per-gpu") && i + 1 < argc) { a.ctx_per_gpu = std::max(1, atoi(argv[++i])); continue; }
         if (!strcmp(argv[i], "--bgzf")) { a.bgzf = true; continue; }
+        if (!strcmp(argv[i], "--bam")) { a.bam = true; continue; }
         if (!strcmp(argv[i], "--ms")) { a.legacy_ms = true; continue; }
         if (!strcmp(argv[i], "--mems")) { a.legacy_mems = true; continue; }
         if (!strcmp(argv[i], "--split")) { a.split = true; continue; }
@@ -282,9 +309,10 @@ static void parse(int argc, char** argv, Args& a) {
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
                               "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n"
-                              "  --bgzf: the SAM output (single end, -1 / -2, -m, --extend) as blocked gzip in <output>.gz, compressed on the GPU; samtools, htslib and bgzip -d read it as SAM\n";
+                              "  --bgzf: the SAM output (single end, -1 / -2, -m, --extend) as blocked gzip in <output>.gz, compressed on the GPU; samtools, htslib and bgzip -d read it as SAM\n"
+                              "  --bam: the SAM output (the same four modes) as BAM in <output>.bam (a trailing .sam becomes .bam): header and records encoded and compressed on the GPU, unsorted, no index\n";
     int c;
     char* s;
     optind = 1;
@@ -566,7 +594,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         const size_t n = read_pairs(r1, r2, (size_t)-1, b);
         printf("dry-run: pairs=%zu bases=%zu min_len=%u filter_dir=%u dir_thr=%.1f find_orphan=%u b=%zu threads=%zu gpus=%d out=%s first=%.*s second=%.*s%s\n", n, b.seq.size(),
                a.P.min_len, a.PE.filter_dir, a.PE.dir_thr, a.PE.find_orphan, a.b, a.th, a.gpus, sam_filename.c_str(), n ? (int)b.name_off[1] : 0,
-               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", a.bgzf ? " bgzf=1" : "");
+               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", a.bgzf ? " bgzf=1" : a.bam ? " bam=1" : "");
         return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
@@ -584,11 +612,16 @@ static int run_paired(Args& a, const std::string& sam_filename) {
     const auto t0 = std::chrono::steady_clock::now();
     FILE* out = fopen(sam_filename.c_str(), "w");
     if (!out) die("open() file " + sam_filename + " failed");
-    // --bgzf: every piece of text goes through moni_bgzf_compress on the context that made it, and its blocks take the text's place
+    // --bgzf: every piece of text goes through moni_bgzf_compress on the context that made it, and its blocks take the text's place; --bam: through moni_bam_records
     auto put_text = [&](moni_ctx_t* C, const char* p, uint64_t n) {
-        if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(C, p, n, false, &z, &zl); put(z, zl, out); } else put(p, n, out);
+        if (a.blocks()) { const char* z; uint64_t zl; if (a.bam) bam_blocks(C, p, n, &z, &zl); else bgzf_blocks(C, p, n, false, &z, &zl); put(z, zl, out); } else put(p, n, out);
     };
-    { char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header"); put_text(ctx[0], h, hl); moni_free(h); }
+    std::string header_text;          // --bam: for the workers' contexts, which are made below
+    {
+        char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
+        if (a.bam) { const char* z; uint64_t zl; header_text.assign(h, hl); bam_header_blocks(ctx, h, hl, &z, &zl); put(z, zl, out); } else put_text(ctx[0], h, hl);
+        moni_free(h);
+    }
     // -c: <sam>.csv, one line per pair (aligner_ksw2.hpp:911-914; header of aligner::to_csv, :3230-3234); the blocks of the batches are kept and written in input order at the end
     FILE* out2 = nullptr;
     std::map<size_t, std::string> csv_blocks;
@@ -662,6 +695,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         if (k == 0) wctx[(size_t)g * per_gpu] = ctx[g];
         else if (moni_ctx_create(idx[g], &wctx[(size_t)g * per_gpu + k])) die("cannot create a context on GPU " + std::to_string(g));
     }
+    if (a.bam) { const uint8_t* bh; uint64_t bhl; bam_set_headers(wctx, header_text.data(), header_text.size(), &bh, &bhl); }          // the dictionary alone: the header is in the file
     if (fflush(out) != 0) die("short write to the output file");
     const uint64_t off0 = (uint64_t)ftello(out);
     const int fd = fileno(out);
@@ -734,7 +768,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
                 n_al = st.aligned;
             }
             char* const lib_sam = sam;          // (what moni_free takes back in the -m path)
-            if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(C, sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
+            if (a.blocks()) { const char* z; uint64_t zl; if (a.bam) bam_blocks(C, sam, len, &z, &zl); else bgzf_blocks(C, sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
             uint64_t at = 0;
             const double x2 = now();
             {
@@ -777,7 +811,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
              std::to_string(sl) + ", waiting for the block's place " + std::to_string(sw) + ", file writes " + std::to_string(sr));
     }
     if (fseeko(out, (off_t)off_upto, SEEK_SET) != 0) die("seek in the output file failed");
-    if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
+    if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
     for (int g = 0; g < a.gpus; ++g) for (int k = 1; k < per_gpu; ++k) moni_ctx_destroy(wctx[(size_t)g * per_gpu + k]);
     close_out(out);
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1116,6 +1150,19 @@ int main(int argc, char** argv) {
         if (a.loci) die("--bgzf cannot be combined with --loci");
         if (a.approx) die("--bgzf cannot be combined with --approx");
     }
+    if (a.bam) {             // BAM output: the modes that write SAM, and one container
+        if (a.bgzf) die("--bam cannot be combined with --bgzf");
+        if (a.csv) die("--bam cannot be combined with -c");
+        if (a.dry_write) die("--bam cannot be combined with --dry-run-write");
+        if (a.legacy_ms) die("--bam cannot be combined with --ms");
+        if (a.legacy_mems) die("--bam cannot be combined with --mems");
+        if (a.pseudo_ms) die("--bam cannot be combined with --pseudo-ms");
+        if (a.screen) die("--bam cannot be combined with --screen");
+        if (a.locate) die("--bam cannot be combined with --locate");
+        if (a.seq_count) die("--bam cannot be combined with --seq-count");
+        if (a.loci) die("--bam cannot be combined with --loci");
+        if (a.approx) die("--bam cannot be combined with --approx");
+    }
     if (!paired && a.patterns.empty()) die("no reads given (-p)");
     std::string fn = a.filename;
     std::vector<char> tmp(fn.begin(), fn.end()); tmp.push_back(0);
@@ -1123,6 +1170,10 @@ int main(int argc, char** argv) {
     std::string sam_filename = (paired ? a.mate1 : a.patterns) + "_" + base_name + "_" + std::to_string(a.P.min_len) + ".sam";   // align_full_ksw2.cpp:347-353
     if (!a.output.empty()) sam_filename = a.output;
     if (a.bgzf) sam_filename += ".gz";
+    if (a.bam) {             // a trailing .sam becomes .bam
+        if (sam_filename.size() >= 4 && !sam_filename.compare(sam_filename.size() - 4, 4, ".sam")) sam_filename.resize(sam_filename.size() - 4);
+        sam_filename += ".bam";
+    }
     if (paired) return run_paired(a, sam_filename);
     const bool legacy = a.legacy_ms || a.legacy_mems;
     const Mode* M = nullptr;          // the mode that runs; none: plain alignment
@@ -1145,7 +1196,7 @@ int main(int argc, char** argv) {
         }
         printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), a.bgzf ? " bgzf=1" : "");
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), a.bgzf ? " bgzf=1" : a.bam ? " bam=1" : "");
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
@@ -1181,6 +1232,7 @@ int main(int argc, char** argv) {
             char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
             const char* hz = h; uint64_t hzl = hl;
             if (a.bgzf) bgzf_blocks(ctx[0], h, hl, false, &hz, &hzl);          // the header as blocks of its own, before the workers take the contexts
+            if (a.bam) bam_header_blocks(ctx, h, hl, &hz, &hzl);               // ... as a BAM header, and every context learns its dictionary
             pwrite_all(fd, hz, hzl, 0); hdr_len = hzl; moni_free(h);
         }
         std::mutex mu; std::condition_variable cv;
@@ -1217,7 +1269,7 @@ int main(int argc, char** argv) {
                     moni_read_batch_t rb{B.seq.p, B.off.data(), (uint64_t)B.n};
                     if (moni_align_stream(ctx[w], &rb, B.names.p, B.name_off.data(), fq ? B.qual.p : nullptr, &a.P, &sam, &len, &st)) die("moni_align_stream failed");
                     // --bgzf: the range's text from the context's pinned buffer through the same context; its blocks take the text's place below
-                    if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[w], sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
+                    if (a.blocks()) { const char* z; uint64_t zl; if (a.bam) bam_blocks(ctx[w], sam, len, &z, &zl); else bgzf_blocks(ctx[w], sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
                 }
                 double x2 = now(); t_lib[w] += x2 - x1;
                 uint64_t at;
@@ -1248,7 +1300,7 @@ int main(int argc, char** argv) {
         std::vector<std::thread> th;
         for (size_t w = 0; w < ctx.size(); ++w) th.emplace_back(worker, (int)w);
         for (auto& t : th) t.join();
-        if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); pwrite_all(fd, z, zl, off_upto); }          // the end-of-file block
+        if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); pwrite_all(fd, z, zl, off_upto); }          // the end-of-file block
         if (::close(fd) != 0) die("close() of the output file failed");
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         info("Number of aligned reads: " + std::to_string(aligned.load()) + "/" + std::to_string(processed.load()));
@@ -1272,7 +1324,8 @@ int main(int argc, char** argv) {
         out = fopen(sam_filename.c_str(), "w");
         if (!out) die("open() file " + sam_filename + " failed");
         char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
-        if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], h, hl, false, &z, &zl); put(z, zl, out); } else put(h, hl, out);
+        if (a.bam) { const char* z; uint64_t zl; bam_header_blocks(ctx, h, hl, &z, &zl); put(z, zl, out); }
+        else if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], h, hl, false, &z, &zl); put(z, zl, out); } else put(h, hl, out);
         moni_free(h);
         if (a.csv) {          // -c: <sam>.csv (align_reads_dispatcher.hpp:302,334-339), header of aligner::to_csv (aligner_ksw2.hpp:3230-3234)
             out2 = fopen((sam_filename + ".csv").c_str(), "w");
@@ -1367,9 +1420,9 @@ int main(int argc, char** argv) {
             Done d;
             const double a0 = now();
             const size_t n_al = (M ? M->run : run_align)(C, b, rb, it.first, a, seq_names, d);
-            if (a.bgzf) {          // the batch's text through this worker's context; a copy of the blocks waits for the writer (the pinned buffer is the context's next call's)
+            if (a.blocks()) {          // the batch's text through this worker's context; a copy of the blocks waits for the writer (the pinned buffer is the context's next call's)
                 const char* z; uint64_t zl;
-                bgzf_blocks(C, d.a, d.la, false, &z, &zl);
+                if (a.bam) bam_blocks(C, d.a, d.la, &z, &zl); else bgzf_blocks(C, d.a, d.la, false, &z, &zl);
                 moni_free(d.a);
                 d.a = (char*)malloc(zl + 1); if (!d.a) die("out of memory");
                 memcpy(d.a, z, zl); d.la = zl;
@@ -1391,7 +1444,7 @@ int main(int argc, char** argv) {
     for (auto& t : th) t.join();
     { std::lock_guard<std::mutex> lk(mu_out); workers_done = true; cv_out.notify_all(); }
     writer.join();
-    if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
+    if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
     close_out(out);
     close_out(out2);
     delete zrd;
