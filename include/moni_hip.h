@@ -611,6 +611,46 @@ int  moni_bam_set_header(moni_ctx_t *ctx, const char *sam_header, uint64_t len, 
 int  moni_bam_records(moni_ctx_t *ctx, const void *sam_lines, uint64_t len, const moni_bam_params_t *prm,
                       const uint8_t **out, uint64_t *out_len, moni_bam_stats_t *stats);
 
+/* ---- BGZF input: blocked gzip inflated on the GPU --------------------------------------- */
+/* Input is a concatenation of BGZF members (SAM specification 4.1: what bgzip, unaligned BAM and moni_bgzf_compress write): gzip members
+ * with the `BC` extra subfield - anywhere in the extra field -, each at most 64 KB and inflating to at most 64 KB, with any number of
+ * DEFLATE blocks of any BTYPE (RFC 1951 whole).  Members are independent; one wavefront inflates one. */
+typedef struct { uint32_t check_crc;          /* verify CRC-32 of every member; default 1 */
+                 uint32_t reserved[3]; } moni_inflate_params_t;
+typedef struct { uint64_t in_bytes, out_bytes, blocks, bad_blocks, first_bad_block;
+                 uint32_t bad_reason, pad;
+                 uint64_t stored, fixed, dynamic;      /* DEFLATE blocks seen, by BTYPE */
+                 double t_kernel, t_total; } moni_inflate_stats_t;      /* HIP-event seconds of the kernel; host seconds with the transfers */
+/* why a member is bad (moni_inflate_stats_t::bad_reason: of member first_bad_block, the lowest bad index): the first failure in the order
+ * a sequential reader of that member meets them */
+enum { MONI_INF_OK = 0,
+       MONI_INF_HEADER,        /* not a BGZF member: ID1 ID2 CM FLG, no BC subfield, a BSIZE that leaves no room for header and trailer */
+       MONI_INF_BTYPE,         /* BTYPE 11 */
+       MONI_INF_STORED_LEN,    /* LEN and NLEN of a stored block disagree */
+       MONI_INF_CODE_LENGTHS,  /* more than 286 / 30 codes, an over-subscribed or incomplete set of lengths (but no distance code at all, or one code
+                                  of length 1), a repeat with nothing before it or past the last length, no end-of-block code */
+       MONI_INF_BAD_SYMBOL,    /* bits that are no code, literal/length symbol 286 / 287, distance symbol 30 / 31 */
+       MONI_INF_DISTANCE,      /* a match reaches before the member's first byte */
+       MONI_INF_OVERRUN,       /* more output than ISIZE (or than 65536 bytes) */
+       MONI_INF_TRUNCATED,     /* the payload ends inside a block; as a header reason: len ends inside a member */
+       MONI_INF_TRAILING,      /* whole bytes between the last block and the trailer */
+       MONI_INF_ISIZE,         /* fewer bytes than ISIZE */
+       MONI_INF_CRC };
+void moni_inflate_params_default(moni_inflate_params_t *p);
+/* Host only: hops over the members of data[0, len) by BSIZE.  *n_blocks members lie wholly within len and take *used bytes (what is left
+ * is the start of a member: carry it over to the next chunk); *out_bytes is the sum of their ISIZE.  Any of the three may be NULL.
+ * MONI_EINVAL: data NULL with len > 0, or a member that is not BGZF - the three then describe the members before it. */
+int  moni_bgzf_scan(const void *data, uint64_t len, uint64_t *n_blocks, uint64_t *used, uint64_t *out_bytes);
+/* blocks: len bytes of host memory, whole members only (len = *used of moni_bgzf_scan).  *out points into a pinned buffer of the context
+ * that belongs to this call alone: valid until the next moni_bgzf_inflate or moni_ctx_destroy on this context, not to be freed; a pointer
+ * moni_bgzf_compress or moni_bam_records returned stays valid.  The resident read batch, moni_last_kernel_ms, moni_last_counters and
+ * every result a later *_fetch may want stay as they are.  ISIZE may be 0 (the end-of-file block) and up to 65536.  stats may be NULL.
+ * MONI_EINVAL: a NULL ctx, prm, out or out_len; check_crc above 1, a non-zero reserved; blocks NULL with len > 0; a bad member - then
+ * *out_len = 0 and stats, where given, carry bad_blocks, first_bad_block (0-based, the lowest) and bad_reason.  len 0 gives MONI_OK, no
+ * byte, and launches nothing. */
+int  moni_bgzf_inflate(moni_ctx_t *ctx, const void *blocks, uint64_t len, const moni_inflate_params_t *prm,
+                       const uint8_t **out, uint64_t *out_len, moni_inflate_stats_t *stats);
+
 /* ---- the reference's on-disk liftidx (<prefix>.ldx: include/aligner/liftidx.hpp:117-143 over include/common/seqidx.hpp:197-238) ---- */
 /* Both layouts load: the current one (u64 w after u) and the older one the reference's fixture data/Chr21.10.ldx has. */
 int moni_ldx_info(const char *path, uint64_t *n_seq, uint64_t *u, uint64_t *w, int *has_w);

@@ -39,7 +39,16 @@ EXPORTS = [
     "moni_mslong_params_default", "moni_ms_long_batch",
     "moni_bgzf_params_default", "moni_bgzf_compress",
     "moni_bam_params_default", "moni_bam_set_header", "moni_bam_records",
+    "moni_inflate_params_default", "moni_bgzf_scan", "moni_bgzf_inflate",
 ]
+
+
+def bgzf_scan(data):
+    """moni_bgzf_scan (host only): (return code, members wholly within `data`, the bytes they take, the sum of their ISIZE)"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    n, used, ob = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = lib().moni_bgzf_scan(buf.ctypes.data if buf.size else None, buf.size, C.byref(n), C.byref(used), C.byref(ob))
+    return rc, n.value, used.value, ob.value
 
 
 class FlatIndexC(C.Structure):
@@ -140,6 +149,19 @@ class BgzfParamsC(C.Structure):
 class BgzfStatsC(C.Structure):
     _fields_ = [("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("matches", C.c_uint64),
                 ("literals", C.c_uint64), ("t_kernel", C.c_double), ("t_total", C.c_double)]
+
+
+class InflateParamsC(C.Structure):
+    _fields_ = [("check_crc", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class InflateStatsC(C.Structure):
+    _fields_ = [("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("blocks", C.c_uint64), ("bad_blocks", C.c_uint64), ("first_bad_block", C.c_uint64),
+                ("bad_reason", C.c_uint32), ("pad", C.c_uint32), ("stored", C.c_uint64), ("fixed", C.c_uint64), ("dynamic", C.c_uint64),
+                ("t_kernel", C.c_double), ("t_total", C.c_double)]
+
+
+INF_REASONS = ("OK", "HEADER", "BTYPE", "STORED_LEN", "CODE_LENGTHS", "BAD_SYMBOL", "DISTANCE", "OVERRUN", "TRUNCATED", "TRAILING", "ISIZE", "CRC")
 
 
 class BamParamsC(C.Structure):
@@ -330,6 +352,11 @@ def lib():
         L.moni_bam_set_header.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_bam_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BamParamsC), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                        C.POINTER(BamStatsC)]
+        L.moni_inflate_params_default.argtypes = [C.POINTER(InflateParamsC)]
+        L.moni_inflate_params_default.restype = None
+        L.moni_bgzf_scan.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.moni_bgzf_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(InflateParamsC), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                        C.POINTER(InflateStatsC)]
         _lib = L
     return _lib
 
@@ -754,6 +781,21 @@ class Ctx:
         _chk(self._L.moni_bgzf_compress(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(p), C.byref(out), C.byref(n), C.byref(st)),
              "moni_bgzf_compress")
         return C.string_at(out.value, n.value) if n.value else b"", {k: getattr(st, k) for k, _ in BgzfStatsC._fields_}
+
+    def bgzf_inflate(self, data, check_crc: bool = True, reserved: int = 0, rc_only: bool = False):
+        """moni_bgzf_inflate: the text of `data` (bytes, or a uint8 array: whole BGZF members).  Returns (bytes, stats: the fields of
+        moni_inflate_stats_t); with rc_only (the return code, out_len, stats), raising nothing."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        p = InflateParamsC()
+        self._L.moni_inflate_params_default(C.byref(p))
+        p.check_crc, p.reserved[0] = 1 if check_crc else 0, reserved
+        out, n, st = C.c_void_p(), C.c_uint64(), InflateStatsC()
+        rc = self._L.moni_bgzf_inflate(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(p), C.byref(out), C.byref(n), C.byref(st))
+        stats = {k: getattr(st, k) for k, _ in InflateStatsC._fields_}
+        if rc_only:
+            return rc, n.value, stats
+        _chk(rc, "moni_bgzf_inflate")
+        return C.string_at(out.value, n.value) if n.value else b"", stats
 
     def bam_set_header(self, text) -> bytes:
         """moni_bam_set_header: the dictionary of the @SQ lines of `text` (bytes or str) for this context's bam_records; returns the uncompressed

@@ -49,6 +49,7 @@
 #include "mslong_kernels.hip"
 #include "bgzf_kernels.hip"
 #include "bam_kernels.hip"
+#include "inflate_kernels.hip"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "moni_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return MONI_ENODEV; } } while (0)
 
@@ -254,6 +255,10 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
         DBuf<uint8_t> text, out, names; DBuf<uint64_t> tile_cnt, tile_pos, starts, size, off; DBuf<bam_ref_t> refs; DBuf<uint32_t> slots; DBuf<unsigned long long> ctr;
         HBuf<unsigned long long> h_sum; HBuf<uint8_t> h_out; std::vector<uint8_t> header; bam_dict_t dict = {}; bool has_header = false; Event e0, e1;
     } bam;
+    struct InflateBufs {    // BGZF input (inflate_api.inc): the members and their table, the text and its pinned copy, a status per member; grow-only
+        DBuf<uint8_t> in, out; DBuf<infl_member_t> mem; DBuf<uint32_t> status; DBuf<unsigned long long> counters;
+        HBuf<infl_member_t> h_mem; HBuf<uint32_t> h_status; HBuf<unsigned long long> h_ctr; HBuf<uint8_t> h_out; Event e0, e1;
+    } inf;
     int n_cu_cached = 0, pe_occ_cached = 0;         // hipGetDeviceProperties / the occupancy query take a millisecond each: asked once per context
 };
 
@@ -2104,5 +2109,6 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "mslong_api.inc"
 #include "bgzf_api.inc"
 #include "bam_api.inc"
+#include "inflate_api.inc"
 
 }  // extern "C"

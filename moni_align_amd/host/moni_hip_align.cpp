@@ -16,7 +16,10 @@
 // place in the output file, again in parallel slices.  A block's place is known as soon as the earlier ranges have reported their
 // lengths, so parsing, GPU work and file writes of different ranges overlap and nothing is copied twice.  gzip input, -m and the legacy
 // modes take the older path: a reader thread parses ahead into a bounded queue, two workers per GPU, a writer thread with a bounded
-// in-order window.  -m writes the report-MEMs records (aligner_ksw2.hpp:346-373);
+// in-order window.  BGZF input (blocked gzip: bgzip, this program's own --bgzf) of single-end and paired alignment is inflated on the GPU
+// (BgzfInput below: a thread per input file with a context of its own inflates --inflate-blocks members at a time, in file order, and hands
+// record-aligned text to the same workers, which parse it as if it were a range of a mapped plain file); --host-inflate, plain gzip, -m, -c,
+// --extend, the legacy and pattern-query modes and FASTA with wrapped lines stay on the older path.  -m writes the report-MEMs records (aligner_ksw2.hpp:346-373);
 // --ms / --mems write the legacy `moni ms` / `moni mems` text outputs (src/matching_statistics.cpp:520-610, src/mems.cpp:520-600).
 // --ms / --mems --split [--seg-len N] [--overlap N] take patterns of genome length (a chromosome, an assembly) through moni_ms_long_batch: every pattern
 // is cut into segments of N bases that are walked side by side, and batches are sized by bases, not by reads.  .lengths and the (offset,length) pairs
@@ -56,6 +59,7 @@
 #include <unistd.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cerrno>
 
@@ -255,6 +259,8 @@ struct Args {
     int gpus = 1;
     size_t gpu_batch = 1048576;
     int ctx_per_gpu = 3;               // streaming path: contexts (ranges in flight) per GPU
+    bool host_inflate = false;         // --host-inflate: BGZF input through zlib on the host (the record-by-record Reader), as plain gzip goes
+    size_t inflate_blocks = 4096;      // --inflate-blocks: BGZF members per moni_bgzf_inflate call (4096: about 256 MB of text)
     bool dry_run = false;
     bool dry_write = false;     // --dry-run-write: no GPU, but the single-end front end's batching runs - ranges, workers of all (absent) GPUs, blocks placed in input order - with placeholder records
     moni_pe_params_t PE;               // -d, -D (paired-end)
@@ -277,6 +283,8 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--dry-run-write")) { a.dry_run = true; a.dry_write = true; continue; }
         if (!strcmp(argv[i], "--ctx-per-gpu") && i + 1 < argc) { a.ctx_per_gpu = std::max(1, atoi(argv[++i])); continue; }
         if (!strcmp(argv[i], "--bgzf")) { a.bgzf = true; continue; }
+        if (!strcmp(argv[i], "--host-inflate")) { a.host_inflate = true; continue; }
+        if (!strcmp(argv[i], "--inflate-blocks") && i + 1 < argc) { a.inflate_blocks = std::max<size_t>(1, strtoull(argv[++i], nullptr, 10)); continue; }
         if (!strcmp(argv[i], "--bam")) { a.bam = true; continue; }
         if (!strcmp(argv[i], "--ms")) { a.legacy_ms = true; continue; }
         if (!strcmp(argv[i], "--mems")) { a.legacy_mems = true; continue; }
@@ -309,9 +317,11 @@ static void parse(int argc, char** argv, Args& a) {
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--host-inflate] [--inflate-blocks N] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
                               "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n"
                               "  --bgzf: the SAM output (single end, -1 / -2, -m, --extend) as blocked gzip in <output>.gz, compressed on the GPU; samtools, htslib and bgzip -d read it as SAM\n"
+                              "  --host-inflate: BGZF (blocked gzip) input of single-end and -1 / -2 alignment is inflated on the GPU; this option sends it through zlib on the host, as plain gzip, -m, -c, --extend, the legacy and pattern-query modes and FASTA with wrapped lines always go\n"
+                              "  --inflate-blocks N: BGZF members inflated per call (4096, about 256 MB of text)\n"
                               "  --bam: the SAM output (the same four modes) as BAM in <output>.bam (a trailing .sam becomes .bam): header and records encoded and compressed on the GPU, unsorted, no index\n";
     int c;
     char* s;
@@ -529,14 +539,213 @@ static size_t read_pairs_fast(const char* base[2], const char* end[2], size_t at
 
 }  // namespace fastpath
 
+// ---- BGZF input: inflated on the GPU -----------------------------------------------------------------------------------------------------
+// A file of BGZF members throughout (moni_bgzf_scan takes all of it) whose text starts with a one-line FASTQ / FASTA record - the condition
+// MappedReader::open applies, on the leading members inflated with zlib.  A thread with a context of its own (it never aligns, so it never makes the
+// large first-call allocations) inflates `blocks` members per call in file order, puts the unfinished record of the chunk before in front, cuts
+// behind the last whole record - it counts newlines; it knows the line phase because it works in order - and queues the record-aligned text.
+struct TextChunk { size_t id = 0; char* p = nullptr; size_t n = 0, cap = 0; };          // p: malloc'ed; the taker gives it back with recycle()
+struct BgzfInput {
+    std::string path;
+    const uint8_t* z = nullptr; size_t zn = 0; int fd = -1;
+    bool fq = false;
+    std::vector<uint64_t> cut;          // where the chunks start in the file, and its end
+    moni_ctx_t* ctx = nullptr;
+    std::thread th; std::mutex mu; std::condition_variable cv_put, cv_get; std::deque<TextChunk> q; bool done = false;
+    std::vector<TextChunk> pool;          // buffers that came back: a fresh 256 MB block costs its page faults, about twice the copy into it
+    double t_inflate = 0, t_cut = 0, t_full = 0;          // seconds in moni_bgzf_inflate, in copying + cutting, waiting for room in the queue
+
+    static size_t member_bytes(const uint8_t* h) {          // of a member the scan has accepted
+        const uint32_t xlen = (uint32_t)h[10] | ((uint32_t)h[11] << 8);
+        for (uint32_t x = 0; x + 4 <= xlen;) {
+            const uint32_t slen = (uint32_t)h[12 + x + 2] | ((uint32_t)h[12 + x + 3] << 8);
+            if (h[12 + x] == 'B' && h[12 + x + 1] == 'C' && slen == 2) return (size_t)((uint32_t)h[12 + x + 4] | ((uint32_t)h[12 + x + 5] << 8)) + 1;
+            x += 4 + slen;
+        }
+        return 0;
+    }
+    void close() { if (z) munmap((void*)z, zn); z = nullptr; if (fd >= 0) ::close(fd); fd = -1; }
+    bool open(const std::string& file) {
+        path = file;
+        fd = ::open(file.c_str(), O_RDONLY);
+        if (fd < 0) return false;
+        struct stat st;
+        if (fstat(fd, &st) != 0 || st.st_size < 28) { close(); return false; }
+        zn = (size_t)st.st_size;
+        void* m = mmap(nullptr, zn, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m == MAP_FAILED) { z = nullptr; close(); return false; }
+        z = (const uint8_t*)m;
+        uint64_t nb = 0, used = 0, text = 0;
+        if (z[0] != 0x1f || z[1] != 0x8b || moni_bgzf_scan(z, zn, &nb, &used, &text) != MONI_OK || used != zn || !nb || !text) { close(); return false; }
+        // the first record, from the leading members (at most 64 KB of text), through zlib
+        std::vector<char> head(65536);
+        size_t hn = 0, at = 0;
+        auto first_record = [&]() -> int {          // 1: a one-line record, 0: not one, -1: not yet whole
+            const char* p = head.data();
+            if (!hn) return -1;
+            if (p[0] != '@' && p[0] != '>') return 0;
+            const char* l1 = (const char*)memchr(p, '\n', hn);
+            if (!l1) return -1;
+            const char* l2 = (const char*)memchr(l1 + 1, '\n', hn - (size_t)(l1 + 1 - p));
+            if (!l2) return -1;
+            if (l2 + 1 >= p + hn) return p[0] == '>' && at >= zn ? 1 : -1;          // (a FASTA file of one record)
+            return l2[1] == (p[0] == '@' ? '+' : '>') ? 1 : 0;          // FASTA: a third line that is no header is a wrapped sequence
+        };
+        int ok = -1;
+        while (ok < 0 && at < zn && hn < head.size()) {
+            const size_t mb = member_bytes(z + at);
+            z_stream zs; memset(&zs, 0, sizeof zs);
+            if (inflateInit2(&zs, 15 + 16) != Z_OK) break;
+            zs.next_in = const_cast<Bytef*>(z + at); zs.avail_in = (uInt)mb;
+            zs.next_out = (Bytef*)head.data() + hn; zs.avail_out = (uInt)(head.size() - hn);
+            const int rc = inflate(&zs, Z_FINISH);
+            hn += zs.total_out;
+            inflateEnd(&zs);
+            if (rc != Z_STREAM_END && rc != Z_BUF_ERROR && rc != Z_OK) break;
+            at += mb;
+            ok = first_record();
+        }
+        if (ok < 0 && at >= zn) ok = first_record();          // the text ends here
+        if (ok != 1) { close(); return false; }
+        fq = head[0] == '@';
+        return true;
+    }
+    size_t n_chunks() const { return cut.size() - 1; }
+    // the chunks of `blocks` members; the thread starts
+    void start(moni_index_t* idx, size_t blocks) {
+        cut.assign(1, 0);
+        size_t k = 0;
+        for (uint64_t at = 0; at < zn;) { at += member_bytes(z + at); if (++k == blocks || at >= zn) { cut.push_back(at); k = 0; } }
+        if (moni_ctx_create(idx, &ctx)) die("cannot create the inflater's context");
+        th = std::thread([this] { run(); });
+    }
+    // the end of the last whole record of text[0, n), which holds `lines` newlines: behind the last one whose number is a multiple of `per`
+    static size_t record_end(const char* text, size_t n, size_t lines, size_t per) {
+        size_t skip = lines % per;
+        const char* e = text + n;
+        while (true) {
+            const char* nl = (const char*)memrchr(text, '\n', (size_t)(e - text));
+            if (!nl) return 0;
+            if (!skip) return (size_t)(nl + 1 - text);
+            --skip; e = nl;
+        }
+    }
+    // a buffer of at least `need` bytes: one that came back, or a new one
+    TextChunk buffer(size_t need) {
+        TextChunk c;
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            for (size_t i = 0; i < pool.size(); ++i) if (pool[i].cap >= need) { c = pool[i]; pool.erase(pool.begin() + i); return c; }
+            if (!pool.empty()) { free(pool.back().p); pool.pop_back(); }
+        }
+        c.cap = need + need / 8 + 64;
+        c.p = (char*)malloc(c.cap);
+        if (!c.p) die("out of memory");
+        return c;
+    }
+    void recycle(TextChunk& c) {
+        if (!c.p) return;
+        std::lock_guard<std::mutex> lk(mu);
+        if (pool.size() < 4) pool.push_back(c); else free(c.p);
+        c = TextChunk();
+    }
+    void run() {
+        auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        moni_inflate_params_t ip; moni_inflate_params_default(&ip);
+        std::vector<char> carry;
+        for (size_t id = 0; id + 1 < cut.size(); ++id) {
+            const uint8_t* out = nullptr; uint64_t ol = 0;
+            moni_inflate_stats_t st;
+            const double x0 = now();
+            const int rc = moni_bgzf_inflate(ctx, z + cut[id], cut[id + 1] - cut[id], &ip, &out, &ol, &st);
+            if (rc == MONI_EINVAL && st.bad_blocks) die(path + ": BGZF member " + std::to_string(st.first_bad_block) + " of chunk " + std::to_string(id) + " is damaged (reason " + std::to_string(st.bad_reason) + ")");
+            if (rc) die("moni_bgzf_inflate failed (" + std::to_string(rc) + ")");
+            const double x1 = now();
+            const size_t total = carry.size() + (size_t)ol;
+            TextChunk c = buffer(total + 1);
+            c.id = id;
+            if (!carry.empty()) memcpy(c.p, carry.data(), carry.size());
+            // the text out of the pinned buffer and its newlines, by a few threads side by side
+            const int T = 8;
+            size_t cnt[T];
+            char* dst = c.p + carry.size();
+            auto part = [&](int i) {
+                const size_t lo = (size_t)ol / T * i, hi = i + 1 == T ? (size_t)ol : (size_t)ol / T * (i + 1);
+                if (hi > lo) memcpy(dst + lo, out + lo, hi - lo);
+                cnt[i] = (size_t)std::count(dst + lo, dst + hi, '\n');
+            };
+            { std::vector<std::thread> t; for (int i = 1; i < T; ++i) t.emplace_back(part, i); part(0); for (auto& x : t) x.join(); }
+            size_t lines = (size_t)std::count(carry.begin(), carry.end(), '\n');
+            for (int i = 0; i < T; ++i) lines += cnt[i];
+            c.n = id + 2 == cut.size() ? total : record_end(c.p, total, lines, fq ? 4 : 2);
+            carry.assign(c.p + c.n, c.p + total);
+            const double x2 = now();
+            std::unique_lock<std::mutex> lk(mu);
+            cv_put.wait(lk, [&] { return q.size() < 2; });
+            q.push_back(c);
+            cv_get.notify_one();
+            t_inflate += x1 - x0; t_cut += x2 - x1; t_full += now() - x2;
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        done = true;
+        cv_get.notify_all();
+    }
+    // the next chunk, in file order; false behind the last
+    bool next(TextChunk& c) {
+        std::unique_lock<std::mutex> lk(mu);
+        cv_get.wait(lk, [&] { return !q.empty() || done; });
+        if (q.empty()) return false;
+        c = q.front(); q.pop_front();
+        cv_put.notify_one();
+        return true;
+    }
+    // the thread has delivered its last chunk: its context goes (before the index does), its times are said
+    void finish() {
+        if (th.joinable()) th.join();
+        if (ctx) moni_ctx_destroy(ctx);
+        ctx = nullptr;
+        fprintf(stderr, "[INFO] BGZF input %s: %zu chunks; inflater thread seconds: moni_bgzf_inflate %.3f, copy + cut %.3f, waiting for room in the queue %.3f\n", path.c_str(), n_chunks(), t_inflate, t_cut, t_full);
+    }
+    ~BgzfInput() {
+        if (th.joinable()) th.join();
+        for (TextChunk& c : q) free(c.p);
+        for (TextChunk& c : pool) free(c.p);
+        if (ctx) moni_ctx_destroy(ctx);
+        close();
+    }
+};
+
 // ---- paired-end (-1 / -2): st_align's paired loop (align_reads_dispatcher.hpp:356-389) over the C ABI ----------------------------------
 // Learn the insert-size model on batches of -b pairs until it is complete (or the input ends), align those batches, then the rest (in
 // larger batches: with the model fixed every pair is independent).  -u switches orphan recovery off.
 struct AnyReader {
     MappedReader m; Reader* z = nullptr; bool mapped = false;
-    explicit AnyReader(const std::string& path) { mapped = m.open(path); if (!mapped) z = new Reader(path); }
-    ~AnyReader() { delete z; }
-    bool next(Batch& b) { return mapped ? m.next(b) : z->next(b); }
+    BgzfInput* bz = nullptr; TextChunk cur;          // BGZF input inflated on the GPU: m is a view of the current chunk
+    explicit AnyReader(const std::string& path, bool gpu_inflate = false) {
+        if (gpu_inflate) { bz = new BgzfInput(); if (!bz->open(path)) { delete bz; bz = nullptr; } }
+        if (!bz) { mapped = m.open(path); if (!mapped) z = new Reader(path); }
+    }
+    ~AnyReader() { if (bz) { m.p = nullptr; free(cur.p); delete bz; } delete z; }          // (free: the pool may be gone with bz's thread)
+    bool fastq_view() const { return bz ? bz->fq : mapped && m.p[m.at < m.n ? m.at : 0] == '@'; }
+    // the next chunk becomes the view; false behind the last
+    bool refill() {
+        bz->recycle(cur); m.p = nullptr; m.n = m.at = 0;
+        if (!bz->next(cur)) return false;
+        m.p = cur.p; m.n = cur.n;
+        return true;
+    }
+    // the view stands on a record (chunks are record-aligned); false at the end of the input
+    bool more() {
+        while (true) {
+            while (m.p && m.at < m.n && (m.p[m.at] == '\n' || m.p[m.at] == '\r')) ++m.at;
+            if (m.p && m.at < m.n) return true;
+            if (!bz || !refill()) return false;
+        }
+    }
+    bool next(Batch& b) {
+        if (bz) return more() && m.next(b);
+        return mapped ? m.next(b) : z->next(b);
+    }
 };
 static size_t read_pairs(AnyReader& r1, AnyReader& r2, size_t n_pairs, Batch& b) {
     size_t n = 0;
@@ -588,13 +797,16 @@ static int run_paired(Args& a, const std::string& sam_filename) {
     a.PE.find_orphan = a.find_orphan ? 1 : 0;            // -u switches orphan recovery off (align_full_ksw2.cpp:248-250)
     a.PE.secondary_chains = a.secondary ? 1 : 0;         // -Z: find_chains_secondary (the second track of the chaining, on the staged paired kernels)
     info("Output file: " + sam_filename);
-    AnyReader r1(a.mate1), r2(a.mate2);
+    const bool gpu_inflate = !a.host_inflate && !a.report_mems && !a.csv && !a.dry_run;
+    AnyReader r1(a.mate1, gpu_inflate), r2(a.mate2, gpu_inflate);
     if (a.dry_run) {
+        bool bz_in = false;          // counting stays on the host; the word says what the run would do
+        if (!a.host_inflate && !a.report_mems && !a.csv) { BgzfInput p1, p2; bz_in = p1.open(a.mate1) || p2.open(a.mate2); }
         Batch b;
         const size_t n = read_pairs(r1, r2, (size_t)-1, b);
-        printf("dry-run: pairs=%zu bases=%zu min_len=%u filter_dir=%u dir_thr=%.1f find_orphan=%u b=%zu threads=%zu gpus=%d out=%s first=%.*s second=%.*s%s\n", n, b.seq.size(),
+        printf("dry-run: pairs=%zu bases=%zu min_len=%u filter_dir=%u dir_thr=%.1f find_orphan=%u b=%zu threads=%zu gpus=%d out=%s first=%.*s second=%.*s%s%s\n", n, b.seq.size(),
                a.P.min_len, a.PE.filter_dir, a.PE.dir_thr, a.PE.find_orphan, a.b, a.th, a.gpus, sam_filename.c_str(), n ? (int)b.name_off[1] : 0,
-               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", a.bgzf ? " bgzf=1" : a.bam ? " bam=1" : "");
+               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", a.bgzf ? " bgzf=1" : a.bam ? " bam=1" : "", bz_in ? " input=bgzf" : "");
         return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
@@ -609,6 +821,8 @@ static int run_paired(Args& a, const std::string& sam_filename) {
             die("cannot load " + idx_path + " nor " + ms_path + " + " + ldx_path + " (reader of the reference's files: layout unverified against a real `moni build` output) on GPU " + std::to_string(g) + " (moni-hip has no CPU path)");
         if (moni_ctx_create(idx[g], &ctx[g])) die("cannot create a context on GPU " + std::to_string(g));
     }
+    if (r1.bz) r1.bz->start(idx[0], a.inflate_blocks);
+    if (r2.bz) r2.bz->start(idx[0], a.inflate_blocks);
     const auto t0 = std::chrono::steady_clock::now();
     FILE* out = fopen(sam_filename.c_str(), "w");
     if (!out) die("open() file " + sam_filename + " failed");
@@ -701,7 +915,8 @@ static int run_paired(Args& a, const std::string& sam_filename) {
     const int fd = fileno(out);
     // a batch for the workers: the slow reader's Batch, or the fast reader's PairBatch (both mate files mapped four-line FASTQ)
     struct Item { size_t id; Batch* b; fastpath::PairBatch* f; };
-    const bool fast_reader = r1.mapped && r2.mapped && r1.m.p[r1.m.at < r1.m.n ? r1.m.at : 0] == '@' && r2.m.p[r2.m.at < r2.m.n ? r2.m.at : 0] == '@' && getenv("MONI_CLI_SLOW_READER") == nullptr;
+    const bool fast_reader = r1.fastq_view() && r2.fastq_view() && getenv("MONI_CLI_SLOW_READER") == nullptr;
+    const bool chunked = r1.bz || r2.bz;          // a view is a chunk of inflated text, not the whole file: a batch ends where a chunk does
     std::mutex mu_q, mu_o;
     std::condition_variable cv_put, cv_get, cv_o;
     std::deque<Item> queue;
@@ -720,7 +935,20 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         while (true) {
             Batch* b = nullptr; fastpath::PairBatch* f = nullptr;
             const double r0 = now();
-            if (fast_reader) { f = new fastpath::PairBatch(); if (!fastpath::read_pairs_fast(fbase, fend, fat, pairs_per_batch, 2 * P, pb, *f)) { delete f; break; } }
+            size_t want = pairs_per_batch;
+            if (fast_reader && chunked) {
+                const bool m1 = r1.more(), m2 = r2.more();
+                if (m1 != m2) die("the mate files have different numbers of records");
+                if (!m1) break;
+                fbase[0] = r1.m.p; fbase[1] = r2.m.p; fend[0] = r1.m.p + r1.m.n; fend[1] = r2.m.p + r2.m.n; fat[0] = r1.m.at; fat[1] = r2.m.at;
+                for (int k = 0; k < 2; ++k) { size_t got = 0; fastpath::skip_records(fbase[k] + fat[k], fend[k], want, 2 * P, got); want = std::min(want, got); }
+                if (!want) die("the mate files are not four-line FASTQ throughout (blank or wrapped lines): use --host-inflate to take the record-by-record reader");
+            }
+            if (fast_reader) {
+                f = new fastpath::PairBatch();
+                if (!fastpath::read_pairs_fast(fbase, fend, fat, want, 2 * P, pb, *f)) { delete f; break; }
+                if (chunked) { r1.m.at = fat[0]; r2.m.at = fat[1]; }
+            }
             else { b = new Batch(); if (!read_pairs_par(r1, r2, pairs_per_batch, *b, P)) { delete b; break; } }
             t_read += now() - r0;
             std::unique_lock<std::mutex> lk(mu_q);
@@ -810,6 +1038,8 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         info("Stage seconds: reading + interleaving the mate files " + std::to_string(t_read) + " (one reader thread, two parsers); summed over " + std::to_string(wctx.size()) + " workers: library calls " +
              std::to_string(sl) + ", waiting for the block's place " + std::to_string(sw) + ", file writes " + std::to_string(sr));
     }
+    if (r1.bz) r1.bz->finish();
+    if (r2.bz) r2.bz->finish();
     if (fseeko(out, (off_t)off_upto, SEEK_SET) != 0) die("seek in the output file failed");
     if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
     for (int g = 0; g < a.gpus; ++g) for (int k = 1; k < per_gpu; ++k) moni_ctx_destroy(wctx[(size_t)g * per_gpu + k]);
@@ -1180,6 +1410,8 @@ int main(int argc, char** argv) {
     for (const Mode& m : MODES) if (a.*m.set) { M = &m; break; }
     if (M && M->suffix && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate / .seqcount)
     info("Output file: " + sam_filename);
+    BgzfInput bzin;          // BGZF input of plain alignment: inflated on the GPU; counting (--dry-run) stays with the Reader
+    const bool bz = !a.host_inflate && !M && getenv("MONI_CLI_QUEUE_PATH") == nullptr && bzin.open(a.patterns);
     MappedReader mrd;
     const bool mapped = mrd.open(a.patterns);
     Reader* zrd = mapped ? nullptr : new Reader(a.patterns);
@@ -1194,13 +1426,13 @@ int main(int argc, char** argv) {
             if (M->id == O_APPROX) mode += " k=" + std::to_string(a.approx_k);
             if (M->strands) mode += (M->strands == S_ONE ? !a.one_strand : a.both_strands) ? " strands=2" : " strands=1";
         }
-        printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s%s\n", n, bases, a.P.min_len,
+        printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s%s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), a.bgzf ? " bgzf=1" : a.bam ? " bam=1" : "");
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), a.bgzf ? " bgzf=1" : a.bam ? " bam=1" : "", bz ? " input=bgzf" : "");
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
-    const bool fast = mapped && !M && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
+    const bool fast = (mapped || bz) && !M && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
     const int per_gpu = legacy ? 1 : (fast ? a.ctx_per_gpu : 2);                      // contexts (batches in flight) per GPU
     std::vector<moni_index_t*> idx(a.gpus, nullptr);
     std::vector<moni_ctx_t*> ctx((size_t)a.gpus * per_gpu, nullptr);
@@ -1218,13 +1450,14 @@ int main(int argc, char** argv) {
         const auto t0 = std::chrono::steady_clock::now();
         auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const char* base = mrd.p; const char* end = mrd.p + mrd.n;
-        const bool fq = base[0] == '@';
-        // record-aligned ranges of about gpu_batch reads (the first record's size is the estimate)
-        const char* r1 = base; for (int k = 0; k < (fq ? 4 : 2); ++k) r1 = next_line(r1, end);
+        const bool fq = bz ? bzin.fq : base[0] == '@';
+        // record-aligned ranges of about gpu_batch reads (the first record's size is the estimate); BGZF input: a range is a chunk of the inflater's
+        const char* r1 = base; for (int k = 0; k < (fq ? 4 : 2) && !bz; ++k) r1 = next_line(r1, end);
         const size_t rec_bytes = std::max<size_t>((size_t)(r1 - base), 8), chunk_bytes = std::max<size_t>(rec_bytes * a.gpu_batch, 1 << 16);
         std::vector<const char*> cuts(1, base);
-        while (cuts.back() < end) { const char* nx = (size_t)(end - cuts.back()) <= chunk_bytes + chunk_bytes / 4 ? end : align_record(cuts.back() + chunk_bytes, base, end, fq); if (nx <= cuts.back()) nx = end; cuts.push_back(nx); }
-        const size_t n_chunks = cuts.size() - 1;
+        if (bz) bzin.start(idx[0], a.inflate_blocks);
+        while (!bz && cuts.back() < end) { const char* nx = (size_t)(end - cuts.back()) <= chunk_bytes + chunk_bytes / 4 ? end : align_record(cuts.back() + chunk_bytes, base, end, fq); if (nx <= cuts.back()) nx = end; cuts.push_back(nx); }
+        const size_t n_chunks = bz ? bzin.n_chunks() : cuts.size() - 1;
         const int fd = ::open(sam_filename.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (fd < 0) die("open() file " + sam_filename + " failed");
         uint64_t hdr_len = 0;
@@ -1246,10 +1479,20 @@ int main(int argc, char** argv) {
         auto worker = [&](int w) {
             ParsedBatch B;
             while (true) {
-                const size_t id = next_chunk.fetch_add(1);
-                if (id >= n_chunks) return;
+                size_t id;
+                TextChunk tc;
                 double x0 = now();
-                parse_range(cuts[id], cuts[id + 1], base, end, fq, P, B);
+                if (bz) {
+                    if (!bzin.next(tc)) return;
+                    id = tc.id;
+                    x0 = now();
+                    parse_range(tc.p, tc.p + tc.n, tc.p, tc.p + tc.n, fq, P, B);
+                    bzin.recycle(tc);
+                } else {
+                    id = next_chunk.fetch_add(1);
+                    if (id >= n_chunks) return;
+                    parse_range(cuts[id], cuts[id + 1], base, end, fq, P, B);
+                }
                 double x1 = now(); t_parse[w] += x1 - x0;
                 char* sam = nullptr; uint64_t len = 0;
                 moni_align_stats_t st; memset(&st, 0, sizeof st);
@@ -1300,6 +1543,7 @@ int main(int argc, char** argv) {
         std::vector<std::thread> th;
         for (size_t w = 0; w < ctx.size(); ++w) th.emplace_back(worker, (int)w);
         for (auto& t : th) t.join();
+        if (bz) bzin.finish();
         if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); pwrite_all(fd, z, zl, off_upto); }          // the end-of-file block
         if (::close(fd) != 0) die("close() of the output file failed");
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
