@@ -611,6 +611,62 @@ int  moni_bam_set_header(moni_ctx_t *ctx, const char *sam_header, uint64_t len, 
 int  moni_bam_records(moni_ctx_t *ctx, const void *sam_lines, uint64_t len, const moni_bam_params_t *prm,
                       const uint8_t **out, uint64_t *out_len, moni_bam_stats_t *stats);
 
+/* ---- coordinate-sorted, indexed BAM: records sorted on the GPU -------------------------- */
+/* The order is samtools sort's: by reference (unplaced records last), by position, forward strand before reverse; ties keep input order.
+ * As one key, with n_ref of the header set on the context:
+ *     key = (refID < 0 ? n_ref : refID) << 33 | (uint64)(pos + 1) << 1 | (flag >> 4 & 1) */
+typedef struct { int32_t ref_id, pos, end;       /* end: pos + the M/D/N/=/X lengths, at least pos + 1 (the reflen rule of the record's bin) */
+                 uint32_t bin_flag;              /* bin << 16 | flag, as in the record */
+                 uint64_t off; } moni_bam_ent_t; /* where the record begins in the sorted, uncompressed stream of its call */
+typedef struct { uint64_t in_bytes, records, bam_bytes, out_bytes, blocks, bad_records, first_bad_record; uint32_t bad_reason, pad;
+                 double t_encode,                /* moni_bam_sorted_run: the encoder's kernels (HIP-event seconds, as the next four) */
+                        t_key, t_sort, t_gather, t_deflate, t_total; } moni_bam_sort_stats_t;      /* t_total: host seconds of the call */
+/* why a record is a bad record (moni_bam_sort_stats_t::bad_reason: of record first_bad_record, the lowest bad index).  The checks run in the order
+ * OFFSET, fewer than 36 bytes (SHORT), SIZE, SHORT, NAME, REF, POS, and the first that fails is the record's reason */
+enum { MONI_BAMSORT_OK = 0,
+       MONI_BAMSORT_OFFSET = 1,  /* offs[i] >= offs[i + 1], or offs[i + 1] > len */
+       MONI_BAMSORT_SHORT = 2,   /* fewer bytes than 36 + l_read_name + 4 * n_cigar_op */
+       MONI_BAMSORT_SIZE = 3,    /* 4 + block_size is not offs[i + 1] - offs[i] */
+       MONI_BAMSORT_NAME = 4,    /* l_read_name 0 */
+       MONI_BAMSORT_REF = 5,     /* refID outside [-1, n_ref) */
+       MONI_BAMSORT_POS = 6,     /* pos outside [-1, 2^31 - 1) */
+       MONI_BAMSORT_LENGTH = 7 };/* offs[n] is not len (first_bad_record: n; the records are not looked at) */
+/* moni_bam_records with raw = 1, then the records - still on the device - in coordinate order.  *records (*records_len bytes), *keys (n,
+ * ascending) and *offs (n + 1: where every record begins, then *records_len) point into pinned buffers of the context that belong to
+ * moni_bam_sorted_run and moni_bam_sort alone: valid until the next of those two or moni_ctx_destroy on this context.  Everything else is as
+ * for moni_bam_records: the bad-line rules (stats->bad_records, first_bad_record and bad_reason then carry the line's MONI_BAM_* figures),
+ * the header, and what stays undisturbed.  len 0 gives *n 0.  stats may be NULL. */
+int  moni_bam_sorted_run(moni_ctx_t *ctx, const void *sam_lines, uint64_t len, const uint8_t **records, uint64_t *records_len,
+                         const uint64_t **keys, const uint64_t **offs, uint64_t *n, moni_bam_sort_stats_t *stats);
+/* records: len bytes of host memory, n raw BAM records in any order, record i at offs[i] .. offs[i + 1] (offs: n + 1 entries).  They are
+ * sorted stably by key on the device and leave through the BGZF blocks of prm (*out as for moni_bam_records) or, with raw, as they are
+ * (*out then is the pinned buffer of moni_bam_sorted_run's records).  *ents: n entries in sorted order, pinned, valid as *records above.
+ * MONI_EINVAL: a NULL argument but stats (records and offs may be NULL with n 0 and len 0), parameters moni_bam_records refuses, no header
+ * set, offs[n] != len, n of 2^32 or more, a bad record - then nothing is written (*out_len = 0) and stats, where given, carry bad_records,
+ * first_bad_record and bad_reason. */
+int  moni_bam_sort(moni_ctx_t *ctx, const void *records, uint64_t len, const uint64_t *offs, uint64_t n, const moni_bam_params_t *prm,
+                   const uint8_t **out, uint64_t *out_len, const moni_bam_ent_t **ents, moni_bam_sort_stats_t *stats);
+
+/* Host only, no context, no GPU.  Runs r = 0 .. n_runs - 1, each sorted by key: keys[r][0, n[r]) ascending, offs[r][0, n[r]] the records'
+ * offsets in the run.  The merged order - by (key, run, index) - is cut into chunks of at most chunk_bytes (a record larger than that is a
+ * chunk of its own); a chunk is one contiguous slice of every run, and its slices, concatenated in run order and sorted stably by key, are
+ * that part of the merged order.  Chunk k takes records cuts[k * n_runs + r] .. cuts[(k + 1) * n_runs + r] of run r. */
+typedef struct { uint64_t n_chunks, n_runs; uint64_t *cuts; /* (n_chunks + 1) * n_runs */ } moni_bam_plan_t;
+int  moni_bam_merge_plan(const uint64_t *const *keys, const uint64_t *n, const uint64_t *const *offs, uint64_t n_runs, uint64_t chunk_bytes,
+                         moni_bam_plan_t **plan);
+void moni_bam_plan_free(moni_bam_plan_t *plan);
+/* Host only: the .bai index (SAM specification 5.2) of a coordinate-sorted BAM written as chunks of BGZF blocks.  moni_bai_add takes the
+ * chunks in file order: ents[n] as moni_bam_sort gave them, the chunk's uncompressed bytes, the block_size it was deflated with, the
+ * compressed size of each of its n_blocks blocks and the file offset of the first.  The chunks follow one another in the file; eof_off
+ * (where the end-of-file block begins) must be where the last one ended.  *bytes: the index, in the builder until moni_bai_destroy.
+ * MONI_EINVAL: records out of order, a ref_id outside [-1, n_ref), offsets or blocks that do not fit chunk_len, a gap between chunks. */
+typedef struct moni_bai moni_bai_t;
+moni_bai_t *moni_bai_create(uint32_t n_ref);
+int  moni_bai_add(moni_bai_t *b, const moni_bam_ent_t *ents, uint64_t n, uint64_t chunk_len, uint32_t block_size, const uint32_t *csizes,
+                  uint64_t n_blocks, uint64_t file_off);
+int  moni_bai_finish(moni_bai_t *b, uint64_t eof_off, const uint8_t **bytes, uint64_t *len);
+void moni_bai_destroy(moni_bai_t *b);
+
 /* ---- BGZF input: blocked gzip inflated on the GPU --------------------------------------- */
 /* Input is a concatenation of BGZF members (SAM specification 4.1: what bgzip, unaligned BAM and moni_bgzf_compress write): gzip members
  * with the `BC` extra subfield - anywhere in the extra field -, each at most 64 KB and inflating to at most 64 KB, with any number of

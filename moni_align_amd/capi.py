@@ -39,6 +39,8 @@ EXPORTS = [
     "moni_mslong_params_default", "moni_ms_long_batch",
     "moni_bgzf_params_default", "moni_bgzf_compress",
     "moni_bam_params_default", "moni_bam_set_header", "moni_bam_records",
+    "moni_bam_sorted_run", "moni_bam_sort", "moni_bam_merge_plan", "moni_bam_plan_free",
+    "moni_bai_create", "moni_bai_add", "moni_bai_finish", "moni_bai_destroy",
     "moni_inflate_params_default", "moni_bgzf_scan", "moni_bgzf_inflate",
 ]
 
@@ -186,6 +188,82 @@ class BamBadLine(ValueError):
         r = stats["bad_reason"]
         super().__init__("moni_bam_records: %d bad line(s), the first is line %d (%s)" %
                          (stats["bad_lines"], stats["first_bad_line"], BAM_REASONS[r] if r < len(BAM_REASONS) else r))
+
+
+class BamSortStatsC(C.Structure):
+    _fields_ = [("in_bytes", C.c_uint64), ("records", C.c_uint64), ("bam_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("blocks", C.c_uint64),
+                ("bad_records", C.c_uint64), ("first_bad_record", C.c_uint64), ("bad_reason", C.c_uint32), ("pad", C.c_uint32),
+                ("t_encode", C.c_double), ("t_key", C.c_double), ("t_sort", C.c_double), ("t_gather", C.c_double), ("t_deflate", C.c_double),
+                ("t_total", C.c_double)]
+
+
+class BamPlanC(C.Structure):
+    _fields_ = [("n_chunks", C.c_uint64), ("n_runs", C.c_uint64), ("cuts", C.POINTER(C.c_uint64))]
+
+
+# moni_bam_ent_t: an index entry of a sorted record
+BAM_ENT_DTYPE = np.dtype([("ref_id", np.int32), ("pos", np.int32), ("end", np.int32), ("bin_flag", np.uint32), ("off", np.uint64)])
+# moni_bam_sort_stats_t::bad_reason (include/moni_hip.h: MONI_BAMSORT_*)
+BAMSORT_REASONS = ("OK", "OFFSET", "SHORT", "SIZE", "NAME", "REF", "POS", "LENGTH")
+
+
+class BamBadRecord(ValueError):
+    """moni_bam_sort met a bad record and wrote nothing: .stats holds bad_records, first_bad_record and bad_reason"""
+
+    def __init__(self, stats):
+        self.stats = stats
+        r = stats["bad_reason"]
+        super().__init__("moni_bam_sort: %d bad record(s), the first is record %d (%s)" %
+                         (stats["bad_records"], stats["first_bad_record"], BAMSORT_REASONS[r] if r < len(BAMSORT_REASONS) else r))
+
+
+def bam_merge_plan(keys, offs, chunk_bytes: int) -> np.ndarray:
+    """moni_bam_merge_plan (host only): runs r with keys[r] (ascending uint64) and offs[r] (len(keys[r]) + 1 offsets) -> cuts[n_chunks + 1, n_runs]:
+    chunk k takes records cuts[k, r] .. cuts[k + 1, r] of run r."""
+    L = lib()
+    R = len(keys)
+    ks = [np.ascontiguousarray(k, dtype=np.uint64) for k in keys]
+    os_ = [np.ascontiguousarray(o, dtype=np.uint64) for o in offs]
+    if any(len(o) != len(k) + 1 for k, o in zip(ks, os_)) or len(os_) != R:
+        raise ValueError("bam_merge_plan: a run's offsets are one more than its keys")
+    kp = (C.c_void_p * max(R, 1))(*[k.ctypes.data for k in ks])
+    op = (C.c_void_p * max(R, 1))(*[o.ctypes.data for o in os_])
+    n = np.array([len(k) for k in ks], dtype=np.uint64)
+    plan = C.POINTER(BamPlanC)()
+    _chk(L.moni_bam_merge_plan(kp, n.ctypes.data if R else None, op, R, chunk_bytes, C.byref(plan)), "moni_bam_merge_plan")
+    try:
+        nc = int(plan.contents.n_chunks)
+        return np.ctypeslib.as_array(plan.contents.cuts, shape=((nc + 1) * R,)).reshape(nc + 1, R).copy() if R else np.zeros((1, 0), np.uint64)
+    finally:
+        L.moni_bam_plan_free(plan)
+
+
+class BaiBuilder:
+    """moni_bai_* (host only): the .bai of a coordinate-sorted BAM written as chunks of BGZF blocks, fed in file order"""
+
+    def __init__(self, n_ref: int):
+        self._L = lib()
+        self._h = self._L.moni_bai_create(n_ref)
+        if not self._h:
+            raise MemoryError("moni_bai_create")
+
+    def add(self, ents, chunk_len: int, block_size: int, csizes, file_off: int):
+        e = np.ascontiguousarray(ents, dtype=BAM_ENT_DTYPE)
+        cs = np.ascontiguousarray(csizes, dtype=np.uint32)
+        _chk(self._L.moni_bai_add(self._h, e.ctypes.data if e.size else None, e.size, chunk_len, block_size, cs.ctypes.data if cs.size else None, cs.size,
+                                  file_off), "moni_bai_add")
+
+    def finish(self, eof_off: int) -> bytes:
+        out, n = C.c_void_p(), C.c_uint64()
+        _chk(self._L.moni_bai_finish(self._h, eof_off, C.byref(out), C.byref(n)), "moni_bai_finish")
+        return C.string_at(out.value, n.value)
+
+    def close(self):
+        if self._h:
+            self._L.moni_bai_destroy(self._h)
+            self._h = None
+
+    __del__ = close
 
 
 class DpParamsC(C.Structure):
@@ -352,6 +430,19 @@ def lib():
         L.moni_bam_set_header.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.moni_bam_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BamParamsC), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                        C.POINTER(BamStatsC)]
+        L.moni_bam_sorted_run.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(BamSortStatsC)]
+        L.moni_bam_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(BamParamsC), C.POINTER(C.c_void_p),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(BamSortStatsC)]
+        L.moni_bam_merge_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(BamPlanC))]
+        L.moni_bam_plan_free.argtypes = [C.POINTER(BamPlanC)]
+        L.moni_bam_plan_free.restype = None
+        L.moni_bai_create.argtypes = [C.c_uint32]
+        L.moni_bai_create.restype = C.c_void_p
+        L.moni_bai_add.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]
+        L.moni_bai_finish.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.moni_bai_destroy.argtypes = [C.c_void_p]
+        L.moni_bai_destroy.restype = None
         L.moni_inflate_params_default.argtypes = [C.POINTER(InflateParamsC)]
         L.moni_inflate_params_default.restype = None
         L.moni_bgzf_scan.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -819,6 +910,40 @@ class Ctx:
             raise BamBadLine(stats)
         _chk(rc, "moni_bam_records")
         return C.string_at(out.value, n.value) if n.value else b"", stats
+
+    def bam_sorted_run(self, data):
+        """moni_bam_sorted_run: the SAM lines `data` as raw BAM records in coordinate order.  Returns (records: bytes, keys[n] ascending,
+        offs[n + 1], stats: the fields of moni_bam_sort_stats_t); raises BamBadLine, with the encoder's figures, where a line is a bad line."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        rec, rl, keys, offs, n, st = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_void_p(), C.c_uint64(), BamSortStatsC()
+        rc = self._L.moni_bam_sorted_run(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(rec), C.byref(rl), C.byref(keys), C.byref(offs),
+                                         C.byref(n), C.byref(st))
+        stats = {k: getattr(st, k) for k, _ in BamSortStatsC._fields_ if k != "pad"}
+        if rc == -22 and st.bad_records:
+            raise BamBadLine(dict(bad_lines=st.bad_records, first_bad_line=st.first_bad_record, bad_reason=st.bad_reason))
+        _chk(rc, "moni_bam_sorted_run")
+        k = np.frombuffer(C.string_at(keys.value, 8 * n.value), dtype=np.uint64) if n.value else np.zeros(0, np.uint64)
+        o = np.frombuffer(C.string_at(offs.value, 8 * (n.value + 1)), dtype=np.uint64)
+        return C.string_at(rec.value, rl.value) if rl.value else b"", k, o, stats
+
+    def bam_sort(self, records, offs, block_size: int = 65280, level: int = 1, eof: bool = False, raw: bool = False):
+        """moni_bam_sort: raw BAM records (bytes or a uint8 array; record i at offs[i] .. offs[i + 1]) sorted stably by coordinate and deflated, or
+        with raw as they are.  Returns (bytes, ents: BAM_ENT_DTYPE[n] in sorted order, stats); raises BamBadRecord, with the stats, on a bad record."""
+        buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray, memoryview)) else np.ascontiguousarray(records, dtype=np.uint8)
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = max(len(o) - 1, 0)
+        p = BamParamsC()
+        self._L.moni_bam_params_default(C.byref(p))
+        p.block_size, p.level, p.eof, p.raw = block_size, level, 1 if eof else 0, 1 if raw else 0
+        out, ol, ents, st = C.c_void_p(), C.c_uint64(), C.c_void_p(), BamSortStatsC()
+        rc = self._L.moni_bam_sort(self._h, buf.ctypes.data if buf.size else None, buf.size, o.ctypes.data if o.size else None, n, C.byref(p), C.byref(out),
+                                   C.byref(ol), C.byref(ents), C.byref(st))
+        stats = {k: getattr(st, k) for k, _ in BamSortStatsC._fields_ if k != "pad"}
+        if rc == -22 and st.bad_records:
+            raise BamBadRecord(stats)
+        _chk(rc, "moni_bam_sort")
+        e = np.frombuffer(C.string_at(ents.value, BAM_ENT_DTYPE.itemsize * n), dtype=BAM_ENT_DTYPE) if n else np.zeros(0, BAM_ENT_DTYPE)
+        return C.string_at(out.value, ol.value) if ol.value else b"", e, stats
 
     def _locate_params(self, strands: int, max_occ: int) -> "LocateParamsC":
         p = LocateParamsC()

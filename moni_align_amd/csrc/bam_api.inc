@@ -30,26 +30,21 @@ int moni_bam_set_header(moni_ctx_t* c, const char* sam_header, uint64_t len, con
     return MONI_OK;
 }
 
-int moni_bam_records(moni_ctx_t* c, const void* sam_lines, uint64_t len, const moni_bam_params_t* prm, const uint8_t** out, uint64_t* out_len,
-                     moni_bam_stats_t* stats) {
-    if (!c || !prm || !out || !out_len || (!sam_lines && len)) return MONI_EINVAL;
-    const moni_bgzf_params_t zp = {prm->block_size, prm->level, prm->raw ? 0u : prm->eof, 0u};
-    if (!bgzf_params_ok(zp) || prm->eof > 1u || prm->raw > 1u || prm->reserved[0] || prm->reserved[1] || !c->bam.has_header) return MONI_EINVAL;
-    const auto t0 = std::chrono::steady_clock::now();
+// The encoder's passes over `len` bytes of SAM lines: *n_lines records of *total bytes in all stay on the device, in B.out at the offsets B.off
+// (n_lines + 1 entries); the write pass is launched, not waited for.  st: in_bytes, lines, the bad lines; t_encode is the caller's to read from
+// B.e0 / B.e1 once the stream has been synchronised.  MONI_EINVAL with st.bad_lines set: a bad line, nothing was written.
+static int bam_encode_device(moni_ctx_t* c, const void* sam_lines, uint64_t len, uint64_t* n_lines_out, uint64_t* total_out, moni_bam_stats_t& st) {
     HIPCHK(hipSetDevice(c->idx->device));
     auto& B = c->bam;
     const uint8_t* text = static_cast<const uint8_t*>(sam_lines);
-    moni_bam_stats_t st;
     memset(&st, 0, sizeof st);
     st.in_bytes = len;
-    *out_len = 0;
+    *n_lines_out = 0; *total_out = 0;
     int rc;
     if ((rc = B.h_sum.ensure(8)) || (rc = B.ctr.ensure(2)) || (rc = B.h_out.ensure(1))) return rc;
     if (len && text[len - 1] != '\n') {          // the one check that needs no parse: the index of the unterminated line is the number of \n before it
         for (const uint8_t* p = text; (p = static_cast<const uint8_t*>(memchr(p, '\n', (size_t)(text + len - p)))) != nullptr; ++p) ++st.first_bad_line;
         st.bad_lines = 1; st.bad_reason = MONI_BAM_NEWLINE;
-        st.t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (stats) *stats = st;
         return MONI_EINVAL;
     }
     uint64_t total = 0;
@@ -88,8 +83,6 @@ int moni_bam_records(moni_ctx_t* c, const void* sam_lines, uint64_t len, const m
         st.lines = n_lines;
         if (B.h_sum.p[1]) {
             st.bad_lines = B.h_sum.p[1]; st.first_bad_line = B.h_sum.p[2] >> 8; st.bad_reason = (uint32_t)(B.h_sum.p[2] & 0xFFu);
-            st.t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (stats) *stats = st;
             return MONI_EINVAL;
         }
         total = B.h_sum.p[0];
@@ -100,8 +93,31 @@ int moni_bam_records(moni_ctx_t* c, const void* sam_lines, uint64_t len, const m
         hipLaunchKernelGGL(bam_write_kernel, grid(n_lines), dim3(BAM_T), 0, c->stream, G);
         HIPCHK(hipEventRecord(B.e1, c->stream));
         HIPCHK(hipGetLastError());
+        *n_lines_out = st.lines;
     }
     st.bam_bytes = total;
+    *total_out = total;
+    return MONI_OK;
+}
+
+int moni_bam_records(moni_ctx_t* c, const void* sam_lines, uint64_t len, const moni_bam_params_t* prm, const uint8_t** out, uint64_t* out_len,
+                     moni_bam_stats_t* stats) {
+    if (!c || !prm || !out || !out_len || (!sam_lines && len)) return MONI_EINVAL;
+    const moni_bgzf_params_t zp = {prm->block_size, prm->level, prm->raw ? 0u : prm->eof, 0u};
+    if (!bgzf_params_ok(zp) || prm->eof > 1u || prm->raw > 1u || prm->reserved[0] || prm->reserved[1] || !c->bam.has_header) return MONI_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto& B = c->bam;
+    moni_bam_stats_t st;
+    *out_len = 0;
+    uint64_t n_lines = 0, total = 0;
+    int rc = bam_encode_device(c, sam_lines, len, &n_lines, &total, st);
+    if (rc) {
+        if (rc == MONI_EINVAL && st.bad_lines) {
+            st.t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            if (stats) *stats = st;
+        }
+        return rc;
+    }
     if (prm->raw) {
         if ((rc = B.h_out.ensure(total + 1))) return rc;
         if (total) HIPCHK(hipMemcpyAsync(B.h_out.p, B.out.p, total, hipMemcpyDeviceToHost, c->stream));

@@ -49,6 +49,8 @@
 #include "mslong_kernels.hip"
 #include "bgzf_kernels.hip"
 #include "bam_kernels.hip"
+#include "bam_sort_kernels.hip"
+#include "bam_index.hpp"
 #include "inflate_kernels.hip"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "moni_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return MONI_ENODEV; } } while (0)
@@ -255,6 +257,12 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
         DBuf<uint8_t> text, out, names; DBuf<uint64_t> tile_cnt, tile_pos, starts, size, off; DBuf<bam_ref_t> refs; DBuf<uint32_t> slots; DBuf<unsigned long long> ctr;
         HBuf<unsigned long long> h_sum; HBuf<uint8_t> h_out; std::vector<uint8_t> header; bam_dict_t dict = {}; bool has_header = false; Event e0, e1;
     } bam;
+    struct BamSortBufs {    // sorted BAM output (bam_sort_api.inc): moni_bam_sort's records and offsets as given, keys and record indices before and behind the sort, the
+                            // entries' fields in input order, the sorted sizes and offsets, the sorted records and entries, and what goes back pinned; grow-only
+        DBuf<uint8_t> in, out, sort_tmp; DBuf<uint64_t> in_off, key[2], size, out_off; DBuf<uint32_t> idx[2]; DBuf<bam_pre_t> pre; DBuf<moni_bam_ent_t> ents;
+        DBuf<unsigned long long> ctr; HBuf<unsigned long long> h_sum; HBuf<uint8_t> h_rec; HBuf<uint64_t> h_key, h_off; HBuf<moni_bam_ent_t> h_ents;
+        Event e0, e1, e2, e3, e4;
+    } bsort;
     struct InflateBufs {    // BGZF input (inflate_api.inc): the members and their table, the text and its pinned copy, a status per member; grow-only
         DBuf<uint8_t> in, out; DBuf<infl_member_t> mem; DBuf<uint32_t> status; DBuf<unsigned long long> counters;
         HBuf<infl_member_t> h_mem; HBuf<uint32_t> h_status; HBuf<unsigned long long> h_ctr; HBuf<uint8_t> h_out; Event e0, e1;
@@ -2109,6 +2117,7 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "mslong_api.inc"
 #include "bgzf_api.inc"
 #include "bam_api.inc"
+#include "bam_sort_api.inc"
 #include "inflate_api.inc"
 
 }  // extern "C"

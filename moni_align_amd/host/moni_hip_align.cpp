@@ -117,6 +117,134 @@ static void bam_header_blocks(const std::vector<moni_ctx_t*>& cs, const char* h,
     bgzf_blocks(cs[0], (const char*)bh, bhl, false, z, zl);
 }
 
+
+// ---- --bam --sort: coordinate-sorted, indexed BAM -----------------------------------------------------------------------
+// Phase 1: every batch's SAM text becomes a sorted run (moni_bam_sorted_run on the context that aligned it); the run's records go to a temporary
+// file beside the output - unlinked as soon as it is open -, its keys and offsets stay in memory, 16 bytes a read.  Phase 2, behind the last
+// batch: moni_bam_merge_plan cuts the merged order into chunks, one contiguous slice of every run each; the contexts take the chunks in turn -
+// pread the slices, moni_bam_sort, the blocks at their place in the file - and moni_bai_add sees them in chunk order.
+static std::string sorted_header(const char* h, uint64_t hl, bool sort) {
+    std::string t(h, hl);
+    const size_t at = sort ? t.find("SO:unknown") : std::string::npos;
+    if (at != std::string::npos && t.compare(0, 3, "@HD") == 0 && at < t.find('\n')) t.replace(at, 10, "SO:coordinate");
+    return t;
+}
+struct SortedBam {
+    struct Run { uint64_t at = 0; std::vector<uint64_t> keys, offs{0}; };
+    int tmp_fd = -1;
+    uint64_t chunk_bytes = 0;
+    uint32_t n_ref = 0;
+    std::string bai_path;
+    std::atomic<uint64_t> tmp_len{0};
+    std::mutex mu;
+    std::map<size_t, Run> runs;
+
+    void open(const std::string& out_path, uint64_t chunk, const std::string& header) {
+        chunk_bytes = chunk; bai_path = out_path + ".bai";
+        for (size_t at = 0; at < header.size(); at = header.find('\n', at) == std::string::npos ? header.size() : header.find('\n', at) + 1)
+            if (!header.compare(at, 4, "@SQ\t")) ++n_ref;
+        std::string t = out_path + ".sort.XXXXXX";
+        tmp_fd = mkstemp(&t[0]);
+        if (tmp_fd < 0) die("cannot create a temporary file beside " + out_path);
+        unlink(t.c_str());          // a crash leaves nothing behind
+    }
+    // run `id` (the batch's number in the input): the SAM lines through moni_bam_sorted_run on context c
+    void add_run(moni_ctx_t* c, size_t id, const char* sam, uint64_t len) {
+        const uint8_t* rec; const uint64_t* keys; const uint64_t* offs; uint64_t rl, n;
+        moni_bam_sort_stats_t st;
+        const int rc = moni_bam_sorted_run(c, sam, len, &rec, &rl, &keys, &offs, &n, &st);
+        if (rc == MONI_EINVAL && st.bad_records)
+            die("moni_bam_sorted_run: " + std::to_string(st.bad_records) + " line(s) of a batch cannot be written as BAM records; the first is its line " +
+                std::to_string(st.first_bad_record) + " (reason " + std::to_string(st.bad_reason) + " of MONI_BAM_*)");
+        if (rc) die("moni_bam_sorted_run failed (" + std::to_string(rc) + ")");
+        Run r;
+        r.at = tmp_len.fetch_add(rl);
+        r.keys.assign(keys, keys + n); r.offs.assign(offs, offs + n + 1);
+        for (uint64_t done = 0; done < rl;) {
+            const ssize_t w = pwrite(tmp_fd, rec + done, rl - done, (off_t)(r.at + done));
+            if (w <= 0) die("short write to the sort's temporary file");
+            done += (uint64_t)w;
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        runs[id] = std::move(r);
+    }
+    // the chunks behind `at` in fd, then the index; returns where the end-of-file block goes
+    uint64_t finish(const std::vector<moni_ctx_t*>& cs, int fd, uint64_t at) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const size_t R = runs.empty() ? 0 : runs.rbegin()->first + 1;
+        std::vector<Run*> run(R, nullptr);
+        Run none;
+        for (size_t r = 0; r < R; ++r) run[r] = runs.count(r) ? &runs[r] : &none;          // a number no batch took: an empty run
+        std::vector<const uint64_t*> kp(R), op(R);
+        std::vector<uint64_t> nn(R);
+        for (size_t r = 0; r < R; ++r) { kp[r] = run[r]->keys.data(); op[r] = run[r]->offs.data(); nn[r] = run[r]->keys.size(); }
+        moni_bam_plan_t* plan = nullptr;
+        if (moni_bam_merge_plan(kp.data(), nn.data(), op.data(), R, chunk_bytes, &plan)) die("moni_bam_merge_plan failed");
+        moni_bai_t* bai = moni_bai_create(n_ref);
+        if (!bai) die("out of memory");
+        moni_bam_params_t bp; moni_bam_params_default(&bp);
+        std::atomic<uint64_t> next{0};
+        std::mutex mo; std::condition_variable cv;
+        uint64_t upto = 0, off_upto = at;
+        auto worker = [&](moni_ctx_t* c) {
+            std::vector<uint8_t> buf; std::vector<uint64_t> offs; std::vector<uint32_t> cs_;
+            for (uint64_t k; (k = next.fetch_add(1)) < plan->n_chunks;) {
+                const uint64_t* lo = plan->cuts + k * R; const uint64_t* hi = lo + R;
+                uint64_t bytes = 0, n = 0;
+                for (size_t r = 0; r < R; ++r) { bytes += run[r]->offs[hi[r]] - run[r]->offs[lo[r]]; n += hi[r] - lo[r]; }
+                buf.resize(bytes); offs.assign(1, 0);
+                for (size_t r = 0; r < R; ++r) {
+                    const uint64_t a0 = run[r]->offs[lo[r]], a1 = run[r]->offs[hi[r]], base = offs.back();
+                    for (uint64_t done = 0; done < a1 - a0;) {
+                        const ssize_t g = pread(tmp_fd, buf.data() + base + done, a1 - a0 - done, (off_t)(run[r]->at + a0 + done));
+                        if (g <= 0) die("short read from the sort's temporary file");
+                        done += (uint64_t)g;
+                    }
+                    for (uint64_t i = lo[r]; i < hi[r]; ++i) offs.push_back(base + run[r]->offs[i + 1] - a0);
+                }
+                const uint8_t* z; uint64_t zl; const moni_bam_ent_t* ents; moni_bam_sort_stats_t st;
+                const int rc = moni_bam_sort(c, buf.data(), bytes, offs.data(), n, &bp, &z, &zl, &ents, &st);
+                if (rc) die("moni_bam_sort failed (" + std::to_string(rc) + ")");
+                cs_.clear();
+                for (uint64_t p = 0; p < zl;) { const uint32_t b = (uint32_t)z[p + 16] + ((uint32_t)z[p + 17] << 8) + 1u; cs_.push_back(b); p += b; }
+                uint64_t mine;
+                {
+                    std::unique_lock<std::mutex> lk(mo);
+                    cv.wait(lk, [&] { return upto == k; });
+                    mine = off_upto;
+                    if (moni_bai_add(bai, ents, n, bytes, bp.block_size, cs_.data(), cs_.size(), mine)) die("moni_bai_add failed: the chunks are not in coordinate order");
+                    off_upto += zl; ++upto;
+                    cv.notify_all();
+                }
+                for (uint64_t done = 0; done < zl;) {
+                    const ssize_t w = pwrite(fd, z + done, zl - done, (off_t)(mine + done));
+                    if (w <= 0) die("short write to the output file");
+                    done += (uint64_t)w;
+                }
+            }
+        };
+        std::vector<std::thread> th;
+        for (size_t w = 1; w < cs.size(); ++w) th.emplace_back(worker, cs[w]);
+        worker(cs[0]);
+        for (auto& t : th) t.join();
+        const uint8_t* ib; uint64_t il;
+        if (moni_bai_finish(bai, off_upto, &ib, &il)) die("moni_bai_finish failed");
+        FILE* f = fopen(bai_path.c_str(), "w");
+        if (!f) die("open() file " + bai_path + " failed");
+        put(ib, il, f);
+        close_out(f);
+        moni_bai_destroy(bai);
+        const uint64_t n_chunks = plan->n_chunks;
+        moni_bam_plan_free(plan);
+        ::close(tmp_fd); tmp_fd = -1;
+        uint64_t n_rec = 0;
+        for (size_t r = 0; r < R; ++r) n_rec += nn[r];
+        info("Sorted output: " + std::to_string(n_rec) + " records in " + std::to_string(R) + " runs (" + std::to_string(tmp_len.load()) + " bytes) merged as " + std::to_string(n_chunks) +
+             " chunks over " + std::to_string(cs.size()) + " contexts in " + std::to_string(std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()) + " s; index: " + bai_path);
+        return off_upto;
+    }
+};
+
 struct Batch {
     std::vector<uint8_t> seq, qual, names;
     std::vector<uint64_t> off{0}, name_off{0};
@@ -266,6 +394,8 @@ struct Args {
     moni_pe_params_t PE;               // -d, -D (paired-end)
     bool find_orphan = true;           // -u switches orphan recovery off
     bool bam = false;                  // --bam: the SAM lines as BAM records in BGZF blocks in <out>.bam, encoded and deflated on the GPU by the context that aligned them (moni_bam_records)
+    bool sort = false;                 // --sort (with --bam): the records in coordinate order, with <out>.bam.bai beside them
+    uint64_t sort_chunk = 256ull << 20; bool sort_chunk_set = false;      // --sort-chunk: uncompressed bytes of a chunk of the merge
     bool blocks() const { return bgzf || bam; }          // the output is a sequence of BGZF blocks
     bool bgzf = false;                 // --bgzf: the SAM text as BGZF blocks in <out>.gz, deflated on the GPU by the context that aligned it (moni_bgzf_compress)
 };
@@ -286,6 +416,8 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--host-inflate")) { a.host_inflate = true; continue; }
         if (!strcmp(argv[i], "--inflate-blocks") && i + 1 < argc) { a.inflate_blocks = std::max<size_t>(1, strtoull(argv[++i], nullptr, 10)); continue; }
         if (!strcmp(argv[i], "--bam")) { a.bam = true; continue; }
+        if (!strcmp(argv[i], "--sort")) { a.sort = true; continue; }
+        if (!strcmp(argv[i], "--sort-chunk") && i + 1 < argc) { a.sort_chunk = strtoull(argv[++i], nullptr, 10); a.sort_chunk_set = true; continue; }
         if (!strcmp(argv[i], "--ms")) { a.legacy_ms = true; continue; }
         if (!strcmp(argv[i], "--mems")) { a.legacy_mems = true; continue; }
         if (!strcmp(argv[i], "--split")) { a.split = true; continue; }
@@ -317,12 +449,14 @@ static void parse(int argc, char** argv, Args& a) {
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--host-inflate] [--inflate-blocks N] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--sort [--sort-chunk BYTES]] [--host-inflate] [--inflate-blocks N] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
                               "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n"
                               "  --bgzf: the SAM output (single end, -1 / -2, -m, --extend) as blocked gzip in <output>.gz, compressed on the GPU; samtools, htslib and bgzip -d read it as SAM\n"
                               "  --host-inflate: BGZF (blocked gzip) input of single-end and -1 / -2 alignment is inflated on the GPU; this option sends it through zlib on the host, as plain gzip, -m, -c, --extend, the legacy and pattern-query modes and FASTA with wrapped lines always go\n"
                               "  --inflate-blocks N: BGZF members inflated per call (4096, about 256 MB of text)\n"
-                              "  --bam: the SAM output (the same four modes) as BAM in <output>.bam (a trailing .sam becomes .bam): header and records encoded and compressed on the GPU, unsorted, no index\n";
+                              "  --bam: the SAM output (the same four modes) as BAM in <output>.bam (a trailing .sam becomes .bam): header and records encoded and compressed on the GPU, unsorted, no index\n"
+                              "  --sort: with --bam, the records in coordinate order (samtools sort's: reference, position, forward strand first; ties keep input order) under @HD SO:coordinate, and the index in <output>.bam.bai; sorted on the GPU, merged through a temporary file beside the output\n"
+                              "  --sort-chunk BYTES: uncompressed bytes of the records sorted and compressed per call in the merge (268435456; at least 65536)\n";
     int c;
     char* s;
     optind = 1;
@@ -806,7 +940,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         const size_t n = read_pairs(r1, r2, (size_t)-1, b);
         printf("dry-run: pairs=%zu bases=%zu min_len=%u filter_dir=%u dir_thr=%.1f find_orphan=%u b=%zu threads=%zu gpus=%d out=%s first=%.*s second=%.*s%s%s\n", n, b.seq.size(),
                a.P.min_len, a.PE.filter_dir, a.PE.dir_thr, a.PE.find_orphan, a.b, a.th, a.gpus, sam_filename.c_str(), n ? (int)b.name_off[1] : 0,
-               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", a.bgzf ? " bgzf=1" : a.bam ? " bam=1" : "", bz_in ? " input=bgzf" : "");
+               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", a.bgzf ? " bgzf=1" : a.bam ? (a.sort ? " bam=1 sort=1" : " bam=1") : "", bz_in ? " input=bgzf" : "");
         return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
@@ -833,9 +967,11 @@ static int run_paired(Args& a, const std::string& sam_filename) {
     std::string header_text;          // --bam: for the workers' contexts, which are made below
     {
         char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
-        if (a.bam) { const char* z; uint64_t zl; header_text.assign(h, hl); bam_header_blocks(ctx, h, hl, &z, &zl); put(z, zl, out); } else put_text(ctx[0], h, hl);
+        if (a.bam) { const char* z; uint64_t zl; header_text = sorted_header(h, hl, a.sort); bam_header_blocks(ctx, header_text.data(), header_text.size(), &z, &zl); put(z, zl, out); } else put_text(ctx[0], h, hl);
         moni_free(h);
     }
+    SortedBam sorted;          // --sort: the learning batches are run 0, the workers' batches follow
+    if (a.sort) sorted.open(sam_filename, a.sort_chunk, header_text);
     // -c: <sam>.csv, one line per pair (aligner_ksw2.hpp:911-914; header of aligner::to_csv, :3230-3234); the blocks of the batches are kept and written in input order at the end
     FILE* out2 = nullptr;
     std::map<size_t, std::string> csv_blocks;
@@ -895,7 +1031,8 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         if (all.n()) {
             char* sam = nullptr; uint64_t len = 0, n_al = 0;
             align_one(0, all, &sam, &len, &n_al);
-            put_text(ctx[0], sam, len); moni_free(sam);
+            if (a.sort) sorted.add_run(ctx[0], 0, sam, len); else put_text(ctx[0], sam, len);
+            moni_free(sam);
             if (out2) put(csv_first.data(), csv_first.size(), out2);
             processed += all.n() / 2; aligned += n_al;
         }
@@ -996,7 +1133,8 @@ static int run_paired(Args& a, const std::string& sam_filename) {
                 n_al = st.aligned;
             }
             char* const lib_sam = sam;          // (what moni_free takes back in the -m path)
-            if (a.blocks()) { const char* z; uint64_t zl; if (a.bam) bam_blocks(C, sam, len, &z, &zl); else bgzf_blocks(C, sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
+            if (a.sort) { sorted.add_run(C, it.id + 1, sam, len); len = 0; }          // nothing goes to the output before the merge
+            else if (a.blocks()) { const char* z; uint64_t zl; if (a.bam) bam_blocks(C, sam, len, &z, &zl); else bgzf_blocks(C, sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
             uint64_t at = 0;
             const double x2 = now();
             {
@@ -1040,6 +1178,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
     }
     if (r1.bz) r1.bz->finish();
     if (r2.bz) r2.bz->finish();
+    if (a.sort) off_upto = sorted.finish(wctx, fd, off_upto);
     if (fseeko(out, (off_t)off_upto, SEEK_SET) != 0) die("seek in the output file failed");
     if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
     for (int g = 0; g < a.gpus; ++g) for (int k = 1; k < per_gpu; ++k) moni_ctx_destroy(wctx[(size_t)g * per_gpu + k]);
@@ -1380,6 +1519,21 @@ int main(int argc, char** argv) {
         if (a.loci) die("--bgzf cannot be combined with --loci");
         if (a.approx) die("--bgzf cannot be combined with --approx");
     }
+    if (a.sort) {            // sorted BAM: what --bam takes, and --bam itself
+        if (!a.bam) die("--sort belongs to --bam");
+        if (a.bgzf) die("--sort cannot be combined with --bgzf");
+        if (a.csv) die("--sort cannot be combined with -c");
+        if (a.dry_write) die("--sort cannot be combined with --dry-run-write");
+        if (a.legacy_ms) die("--sort cannot be combined with --ms");
+        if (a.legacy_mems) die("--sort cannot be combined with --mems");
+        if (a.pseudo_ms) die("--sort cannot be combined with --pseudo-ms");
+        if (a.screen) die("--sort cannot be combined with --screen");
+        if (a.locate) die("--sort cannot be combined with --locate");
+        if (a.seq_count) die("--sort cannot be combined with --seq-count");
+        if (a.loci) die("--sort cannot be combined with --loci");
+        if (a.approx) die("--sort cannot be combined with --approx");
+        if (a.sort_chunk < 65536) die("--sort-chunk takes at least 65536 bytes");
+    } else if (a.sort_chunk_set) die("--sort-chunk belongs to --sort");
     if (a.bam) {             // BAM output: the modes that write SAM, and one container
         if (a.bgzf) die("--bam cannot be combined with --bgzf");
         if (a.csv) die("--bam cannot be combined with -c");
@@ -1428,7 +1582,7 @@ int main(int argc, char** argv) {
         }
         printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s%s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), a.bgzf ? " bgzf=1" : a.bam ? " bam=1" : "", bz ? " input=bgzf" : "");
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), a.bgzf ? " bgzf=1" : a.bam ? (a.sort ? " bam=1 sort=1" : " bam=1") : "", bz ? " input=bgzf" : "");
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
@@ -1460,12 +1614,15 @@ int main(int argc, char** argv) {
         const size_t n_chunks = bz ? bzin.n_chunks() : cuts.size() - 1;
         const int fd = ::open(sam_filename.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (fd < 0) die("open() file " + sam_filename + " failed");
+        SortedBam sorted;          // --sort: a range is a run
         uint64_t hdr_len = 0;
         if (!a.dry_write) {
             char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
             const char* hz = h; uint64_t hzl = hl;
             if (a.bgzf) bgzf_blocks(ctx[0], h, hl, false, &hz, &hzl);          // the header as blocks of its own, before the workers take the contexts
-            if (a.bam) bam_header_blocks(ctx, h, hl, &hz, &hzl);               // ... as a BAM header, and every context learns its dictionary
+            const std::string bh = sorted_header(h, hl, a.sort);
+            if (a.bam) bam_header_blocks(ctx, bh.data(), bh.size(), &hz, &hzl);               // ... as a BAM header, and every context learns its dictionary
+            if (a.sort) sorted.open(sam_filename, a.sort_chunk, bh);
             pwrite_all(fd, hz, hzl, 0); hdr_len = hzl; moni_free(h);
         }
         std::mutex mu; std::condition_variable cv;
@@ -1512,7 +1669,8 @@ int main(int argc, char** argv) {
                     moni_read_batch_t rb{B.seq.p, B.off.data(), (uint64_t)B.n};
                     if (moni_align_stream(ctx[w], &rb, B.names.p, B.name_off.data(), fq ? B.qual.p : nullptr, &a.P, &sam, &len, &st)) die("moni_align_stream failed");
                     // --bgzf: the range's text from the context's pinned buffer through the same context; its blocks take the text's place below
-                    if (a.blocks()) { const char* z; uint64_t zl; if (a.bam) bam_blocks(ctx[w], sam, len, &z, &zl); else bgzf_blocks(ctx[w], sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
+                    if (a.sort) { sorted.add_run(ctx[w], id, sam, len); len = 0; }          // nothing goes to the output before the merge
+                    else if (a.blocks()) { const char* z; uint64_t zl; if (a.bam) bam_blocks(ctx[w], sam, len, &z, &zl); else bgzf_blocks(ctx[w], sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
                 }
                 double x2 = now(); t_lib[w] += x2 - x1;
                 uint64_t at;
@@ -1544,6 +1702,7 @@ int main(int argc, char** argv) {
         for (size_t w = 0; w < ctx.size(); ++w) th.emplace_back(worker, (int)w);
         for (auto& t : th) t.join();
         if (bz) bzin.finish();
+        if (a.sort) off_upto = sorted.finish(ctx, fd, off_upto);
         if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); pwrite_all(fd, z, zl, off_upto); }          // the end-of-file block
         if (::close(fd) != 0) die("close() of the output file failed");
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1560,6 +1719,7 @@ int main(int argc, char** argv) {
     }
     if (a.dry_write) return 0;
     FILE* out = nullptr; FILE* out2 = nullptr;
+    SortedBam sorted;          // --sort: a batch is a run
     if (M && M->suffix) {
         out = fopen((sam_filename + M->suffix).c_str(), "w");
         if (M->suffix2) out2 = fopen((sam_filename + M->suffix2).c_str(), "w");
@@ -1568,7 +1728,7 @@ int main(int argc, char** argv) {
         out = fopen(sam_filename.c_str(), "w");
         if (!out) die("open() file " + sam_filename + " failed");
         char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
-        if (a.bam) { const char* z; uint64_t zl; bam_header_blocks(ctx, h, hl, &z, &zl); put(z, zl, out); }
+        if (a.bam) { const char* z; uint64_t zl; const std::string bh = sorted_header(h, hl, a.sort); bam_header_blocks(ctx, bh.data(), bh.size(), &z, &zl); put(z, zl, out); if (a.sort) sorted.open(sam_filename, a.sort_chunk, bh); }
         else if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], h, hl, false, &z, &zl); put(z, zl, out); } else put(h, hl, out);
         moni_free(h);
         if (a.csv) {          // -c: <sam>.csv (align_reads_dispatcher.hpp:302,334-339), header of aligner::to_csv (aligner_ksw2.hpp:3230-3234)
@@ -1664,7 +1824,8 @@ int main(int argc, char** argv) {
             Done d;
             const double a0 = now();
             const size_t n_al = (M ? M->run : run_align)(C, b, rb, it.first, a, seq_names, d);
-            if (a.blocks()) {          // the batch's text through this worker's context; a copy of the blocks waits for the writer (the pinned buffer is the context's next call's)
+            if (a.sort) { sorted.add_run(C, it.id, d.a, d.la); moni_free(d.a); d.a = nullptr; d.la = 0; }          // nothing goes to the output before the merge
+            else if (a.blocks()) {          // the batch's text through this worker's context; a copy of the blocks waits for the writer (the pinned buffer is the context's next call's)
                 const char* z; uint64_t zl;
                 if (a.bam) bam_blocks(C, d.a, d.la, &z, &zl); else bgzf_blocks(C, d.a, d.la, false, &z, &zl);
                 moni_free(d.a);
@@ -1688,6 +1849,11 @@ int main(int argc, char** argv) {
     for (auto& t : th) t.join();
     { std::lock_guard<std::mutex> lk(mu_out); workers_done = true; cv_out.notify_all(); }
     writer.join();
+    if (a.sort) {
+        if (fflush(out) != 0) die("short write to the output file");
+        const uint64_t end = sorted.finish(ctx, fileno(out), (uint64_t)ftello(out));
+        if (fseeko(out, (off_t)end, SEEK_SET) != 0) die("seek in the output file failed");
+    }
     if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
     close_out(out);
     close_out(out2);
