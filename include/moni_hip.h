@@ -630,7 +630,12 @@ enum { MONI_BAMSORT_OK = 0,
        MONI_BAMSORT_NAME = 4,    /* l_read_name 0 */
        MONI_BAMSORT_REF = 5,     /* refID outside [-1, n_ref) */
        MONI_BAMSORT_POS = 6,     /* pos outside [-1, 2^31 - 1) */
-       MONI_BAMSORT_LENGTH = 7 };/* offs[n] is not len (first_bad_record: n; the records are not looked at) */
+       MONI_BAMSORT_LENGTH = 7,  /* offs[n] is not len (first_bad_record: n; the records are not looked at) */
+       /* moni_bam_sorted_run_dup alone, on records that passed the checks above (SEQ before CLIP; MATE: of the pair's first record) */
+       MONI_BAMSORT_SEQ = 8,     /* fewer bytes than 36 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq */
+       MONI_BAMSORT_CLIP = 9,    /* the unclipped 5' end of a mapped, primary record outside [-2^31, 3 * 2^31) */
+       MONI_BAMSORT_MATE = 10 }; /* paired: records 2p, 2p + 1 do not carry one name, or one with flag & 1 does not carry 0x40 (2p) / 0x80 (2p + 1) alone,
+                                  * or n is odd (then record n - 1).  A record without flag & 1 is not asked for its read's bit. */
 /* moni_bam_records with raw = 1, then the records - still on the device - in coordinate order.  *records (*records_len bytes), *keys (n,
  * ascending) and *offs (n + 1: where every record begins, then *records_len) point into pinned buffers of the context that belong to
  * moni_bam_sorted_run and moni_bam_sort alone: valid until the next of those two or moni_ctx_destroy on this context.  Everything else is as
@@ -646,6 +651,42 @@ int  moni_bam_sorted_run(moni_ctx_t *ctx, const void *sam_lines, uint64_t len, c
  * first_bad_record and bad_reason. */
 int  moni_bam_sort(moni_ctx_t *ctx, const void *records, uint64_t len, const uint64_t *offs, uint64_t n, const moni_bam_params_t *prm,
                    const uint8_t **out, uint64_t *out_len, const moni_bam_ent_t **ents, moni_bam_sort_stats_t *stats);
+
+/* ---- duplicate marking of the sorted output ---------------------------------------------- */
+/* Picard's rule without optical duplicates or UMIs.  A record takes part if flag & 0x904 == 0.  Its unclipped 5' end u5 is pos minus the
+ * leading S/H lengths (forward) or pos + reflen - 1 plus the trailing S/H lengths (reverse); its end code is
+ *     e = (refID < 0 ? n_ref : refID) << 34 | (uint64)(u5 + 2^31) << 1 | (flag >> 4 & 1)
+ * and its score the sum of its base qualities of 15 and more (a byte of 0xFF counts 0; the sum saturates at 2^31 - 1).
+ * An entry is a pair (both mates take part and carry flag & 1: k1 <= k2 their end codes; kind 1, or 3 when the strands are equal and the
+ * mate with the smaller code - at a tie read 1 - is read 2; score: the sum of the two) or a fragment (k1 = e, k2 = 0, kind 0).
+ * idx: the records' places in the sorted run, idx[1] = 0xFFFFFFFF for a fragment. */
+typedef struct { uint64_t k1, k2; uint32_t score, kind; uint32_t idx[2]; } moni_bam_dup_t;
+typedef struct { moni_bam_sort_stats_t run;      /* as moni_bam_sorted_run fills it; the bad-record fields also carry SEQ, CLIP and MATE */
+                 uint64_t entries, pairs, fragments;
+                 uint32_t bad_is_record, pad;    /* 1: run's bad_* fields speak of a record (MONI_BAMSORT_*, input order), not of a line (MONI_BAM_*) */
+                 double t_sig, t_entry; } moni_bam_run_dup_stats_t;    /* HIP-event seconds: the signature kernel; the unit, scan and entry passes */
+typedef struct { uint64_t entries, pairs, dup_pairs, fragments, dup_fragments, marked_records, bad_entries, first_bad_entry;
+                 double t_sort, t_flag, t_total; } moni_bam_dup_stats_t;   /* the sort passes, the other kernels (HIP-event seconds); host seconds */
+/* moni_bam_sorted_run, byte for byte, and the run's entries in input order: with paired = 1 records 2p and 2p + 1 of the lines are the two
+ * mates of a pair, with paired = 0 every record stands alone.  *dups (*n_dups entries) is a pinned buffer of the context, valid as *records.
+ * MONI_EINVAL in addition: a NULL dups, n_dups; paired above 1; a bad record by MONI_BAMSORT_SEQ, CLIP or MATE - then nothing is written
+ * (*n = *n_dups = 0) and stats->run carries bad_records, first_bad_record (in input order) and bad_reason. */
+int  moni_bam_sorted_run_dup(moni_ctx_t *ctx, const void *sam_lines, uint64_t len, uint32_t paired, const uint8_t **records, uint64_t *records_len,
+                             const uint64_t **keys, const uint64_t **offs, uint64_t *n, const moni_bam_dup_t **dups, uint64_t *n_dups,
+                             moni_bam_run_dup_stats_t *stats);
+/* The entries of all runs, in run order (that is input order): dups[r][0, n_dups[r]) of a run of n_records[r] records.  Pairs with equal
+ * (k1, k2, kind): the highest score stays, at a tie the earliest; the records of the others are duplicates.  Fragments whose e is an end of a
+ * pair are duplicates; among the fragments of an e without one the best stays.  marks[r][0, n_records[r]) - the caller's - is written whole:
+ * 1 for a duplicate, else 0, by the record's place in its sorted run.  The entries must be of the header set on this context.
+ * MONI_EINVAL: a NULL argument but stats (the arrays may be NULL with n_runs 0), no header set, an idx at or above n_records[r] (but a
+ * fragment's idx[1]), a kind other than 0, 1, 3 - then no mark is written and stats carry bad_entries and first_bad_entry (counted over all
+ * runs).  MONI_ERANGE: 2^31 entries or 2^32 - 1 records and more. */
+int  moni_bam_dup_resolve(moni_ctx_t *ctx, const moni_bam_dup_t *const *dups, const uint64_t *n_dups, const uint64_t *n_records, uint64_t n_runs,
+                          uint8_t *const *marks, moni_bam_dup_stats_t *stats);
+/* moni_bam_sort with marks[n] beside the input records: record i with marks[i] != 0 gets flag |= 0x400 on the device, before its key and
+ * its entry are made.  marks NULL: moni_bam_sort. */
+int  moni_bam_sort_marked(moni_ctx_t *ctx, const void *records, uint64_t len, const uint64_t *offs, uint64_t n, const uint8_t *marks,
+                          const moni_bam_params_t *prm, const uint8_t **out, uint64_t *out_len, const moni_bam_ent_t **ents, moni_bam_sort_stats_t *stats);
 
 /* Host only, no context, no GPU.  Runs r = 0 .. n_runs - 1, each sorted by key: keys[r][0, n[r]) ascending, offs[r][0, n[r]] the records'
  * offsets in the run.  The merged order - by (key, run, index) - is cut into chunks of at most chunk_bytes (a record larger than that is a

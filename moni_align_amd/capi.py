@@ -40,6 +40,7 @@ EXPORTS = [
     "moni_bgzf_params_default", "moni_bgzf_compress",
     "moni_bam_params_default", "moni_bam_set_header", "moni_bam_records",
     "moni_bam_sorted_run", "moni_bam_sort", "moni_bam_merge_plan", "moni_bam_plan_free",
+    "moni_bam_sorted_run_dup", "moni_bam_dup_resolve", "moni_bam_sort_marked",
     "moni_bai_create", "moni_bai_add", "moni_bai_finish", "moni_bai_destroy",
     "moni_inflate_params_default", "moni_bgzf_scan", "moni_bgzf_inflate",
 ]
@@ -204,7 +205,28 @@ class BamPlanC(C.Structure):
 # moni_bam_ent_t: an index entry of a sorted record
 BAM_ENT_DTYPE = np.dtype([("ref_id", np.int32), ("pos", np.int32), ("end", np.int32), ("bin_flag", np.uint32), ("off", np.uint64)])
 # moni_bam_sort_stats_t::bad_reason (include/moni_hip.h: MONI_BAMSORT_*)
-BAMSORT_REASONS = ("OK", "OFFSET", "SHORT", "SIZE", "NAME", "REF", "POS", "LENGTH")
+BAMSORT_REASONS = ("OK", "OFFSET", "SHORT", "SIZE", "NAME", "REF", "POS", "LENGTH", "SEQ", "CLIP", "MATE")
+# moni_bam_dup_t: an entry of duplicate marking
+BAM_DUP_DTYPE = np.dtype([("k1", np.uint64), ("k2", np.uint64), ("score", np.uint32), ("kind", np.uint32), ("idx", np.uint32, (2,))])
+
+
+class BamRunDupStatsC(C.Structure):
+    _fields_ = [("run", BamSortStatsC), ("entries", C.c_uint64), ("pairs", C.c_uint64), ("fragments", C.c_uint64), ("bad_is_record", C.c_uint32), ("pad", C.c_uint32),
+                ("t_sig", C.c_double), ("t_entry", C.c_double)]
+
+
+class BamDupStatsC(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("pairs", C.c_uint64), ("dup_pairs", C.c_uint64), ("fragments", C.c_uint64), ("dup_fragments", C.c_uint64),
+                ("marked_records", C.c_uint64), ("bad_entries", C.c_uint64), ("first_bad_entry", C.c_uint64),
+                ("t_sort", C.c_double), ("t_flag", C.c_double), ("t_total", C.c_double)]
+
+
+class BamBadEntry(ValueError):
+    """moni_bam_dup_resolve met an entry outside its run and wrote no mark: .stats holds bad_entries and first_bad_entry"""
+
+    def __init__(self, stats):
+        self.stats = stats
+        super().__init__("moni_bam_dup_resolve: %d bad entr(ies), the first is entry %d" % (stats["bad_entries"], stats["first_bad_entry"]))
 
 
 class BamBadRecord(ValueError):
@@ -434,6 +456,11 @@ def lib():
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(BamSortStatsC)]
         L.moni_bam_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(BamParamsC), C.POINTER(C.c_void_p),
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(BamSortStatsC)]
+        L.moni_bam_sorted_run_dup.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(BamRunDupStatsC)]
+        L.moni_bam_dup_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(BamDupStatsC)]
+        L.moni_bam_sort_marked.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(BamParamsC), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(BamSortStatsC)]
         L.moni_bam_merge_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(BamPlanC))]
         L.moni_bam_plan_free.argtypes = [C.POINTER(BamPlanC)]
         L.moni_bam_plan_free.restype = None
@@ -942,6 +969,67 @@ class Ctx:
         if rc == -22 and st.bad_records:
             raise BamBadRecord(stats)
         _chk(rc, "moni_bam_sort")
+        e = np.frombuffer(C.string_at(ents.value, BAM_ENT_DTYPE.itemsize * n), dtype=BAM_ENT_DTYPE) if n else np.zeros(0, BAM_ENT_DTYPE)
+        return C.string_at(out.value, ol.value) if ol.value else b"", e, stats
+
+    def bam_sorted_run_dup(self, data, paired):
+        """moni_bam_sorted_run_dup: bam_sorted_run's four results, then the run's entries (BAM_DUP_DTYPE, input order) and the call's stats
+        (those of the run, then entries, pairs, fragments, t_sig, t_entry).  Raises BamBadLine for a bad line, BamBadRecord for a record that
+        duplicate marking refuses (SEQ, CLIP, MATE)."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        rec, rl, keys, offs, n, st = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_void_p(), C.c_uint64(), BamRunDupStatsC()
+        dups, nd = C.c_void_p(), C.c_uint64()
+        rc = self._L.moni_bam_sorted_run_dup(self._h, buf.ctypes.data if buf.size else None, buf.size, int(paired), C.byref(rec), C.byref(rl), C.byref(keys),
+                                             C.byref(offs), C.byref(n), C.byref(dups), C.byref(nd), C.byref(st))
+        stats = {k: getattr(st.run, k) for k, _ in BamSortStatsC._fields_ if k != "pad"}
+        stats.update({k: getattr(st, k) for k, _ in BamRunDupStatsC._fields_ if k not in ("run", "pad")})
+        if rc == -22 and st.run.bad_records:
+            if st.bad_is_record:
+                raise BamBadRecord(stats)
+            raise BamBadLine(dict(bad_lines=st.run.bad_records, first_bad_line=st.run.first_bad_record, bad_reason=st.run.bad_reason))
+        _chk(rc, "moni_bam_sorted_run_dup")
+        k = np.frombuffer(C.string_at(keys.value, 8 * n.value), dtype=np.uint64) if n.value else np.zeros(0, np.uint64)
+        o = np.frombuffer(C.string_at(offs.value, 8 * (n.value + 1)), dtype=np.uint64)
+        d = np.frombuffer(C.string_at(dups.value, BAM_DUP_DTYPE.itemsize * nd.value), dtype=BAM_DUP_DTYPE) if nd.value else np.zeros(0, BAM_DUP_DTYPE)
+        return C.string_at(rec.value, rl.value) if rl.value else b"", k, o, d, stats
+
+    def bam_dup_resolve(self, dups, n_records):
+        """moni_bam_dup_resolve: dups[r] the entries of run r (BAM_DUP_DTYPE), n_records[r] its records.  Returns ([marks of run r: uint8], stats);
+        raises BamBadEntry where an entry points outside its run."""
+        R = len(dups)
+        ds = [np.ascontiguousarray(d, dtype=BAM_DUP_DTYPE) for d in dups]
+        nd = np.array([len(d) for d in ds], dtype=np.uint64)
+        nr = np.array([int(x) for x in n_records], dtype=np.uint64)
+        marks = [np.full(int(x), 0xEE, dtype=np.uint8) for x in nr]
+        dp = (C.c_void_p * max(R, 1))(*[d.ctypes.data if d.size else None for d in ds])
+        mp = (C.c_void_p * max(R, 1))(*[m.ctypes.data if m.size else None for m in marks])
+        st = BamDupStatsC()
+        rc = self._L.moni_bam_dup_resolve(self._h, dp if R else None, nd.ctypes.data if R else None, nr.ctypes.data if R else None, R, mp if R else None, C.byref(st))
+        stats = {k: getattr(st, k) for k, _ in BamDupStatsC._fields_}
+        if rc == -22 and st.bad_entries:
+            raise BamBadEntry(stats)
+        _chk(rc, "moni_bam_dup_resolve")
+        return marks, stats
+
+    def bam_sort_marked(self, records, offs, marks, block_size: int = 65280, level: int = 1, eof: bool = False, raw: bool = False):
+        """moni_bam_sort_marked: bam_sort with marks[n] (uint8, or None) beside the input records: a marked record leaves with flag | 0x400"""
+        buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray, memoryview)) else np.ascontiguousarray(records, dtype=np.uint8)
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = max(len(o) - 1, 0)
+        m = None if marks is None else np.ascontiguousarray(marks, dtype=np.uint8)
+        if m is not None and m.size != n:
+            raise ValueError("bam_sort_marked: one mark per record")
+        p = BamParamsC()
+        self._L.moni_bam_params_default(C.byref(p))
+        p.block_size, p.level, p.eof, p.raw = block_size, level, 1 if eof else 0, 1 if raw else 0
+        out, ol, ents, st = C.c_void_p(), C.c_uint64(), C.c_void_p(), BamSortStatsC()
+        rc = self._L.moni_bam_sort_marked(self._h, buf.ctypes.data if buf.size else None, buf.size, o.ctypes.data if o.size else None, n,
+                                          m.ctypes.data if m is not None and m.size else (None if m is None or n else m.ctypes.data), C.byref(p), C.byref(out),
+                                          C.byref(ol), C.byref(ents), C.byref(st))
+        stats = {k: getattr(st, k) for k, _ in BamSortStatsC._fields_ if k != "pad"}
+        if rc == -22 and st.bad_records:
+            raise BamBadRecord(stats)
+        _chk(rc, "moni_bam_sort_marked")
         e = np.frombuffer(C.string_at(ents.value, BAM_ENT_DTYPE.itemsize * n), dtype=BAM_ENT_DTYPE) if n else np.zeros(0, BAM_ENT_DTYPE)
         return C.string_at(out.value, ol.value) if ol.value else b"", e, stats
 

@@ -65,8 +65,13 @@ static int bam_sort_device(moni_ctx_t* c, const uint8_t* rec, uint64_t len, cons
     return MONI_OK;
 }
 
-int moni_bam_sorted_run(moni_ctx_t* c, const void* sam_lines, uint64_t len, const uint8_t** records, uint64_t* records_len, const uint64_t** keys,
-                        const uint64_t** offs, uint64_t* n, moni_bam_sort_stats_t* stats) {
+// duplicate marking (bam_dup_api.inc): the entries of the run that bam_sort_device has just sorted, and the marks of moni_bam_sort_marked
+static int bam_dup_device(moni_ctx_t* c, const uint8_t* rec, uint64_t len, const uint64_t* off, uint64_t n, uint32_t paired, moni_bam_run_dup_stats_t& ds);
+static int bam_setdup_device(moni_ctx_t* c, uint8_t* rec, uint64_t len, const uint64_t* off, uint64_t n, const uint8_t* marks);
+
+// moni_bam_sorted_run; with ds, moni_bam_sorted_run_dup: the entries stay in moni_ctx::bdup.h_ent, ds->entries of them
+static int bam_sorted_run_core(moni_ctx_t* c, const void* sam_lines, uint64_t len, const uint8_t** records, uint64_t* records_len, const uint64_t** keys,
+                               const uint64_t** offs, uint64_t* n, moni_bam_sort_stats_t* stats, uint32_t paired, moni_bam_run_dup_stats_t* ds) {
     if (!c || !records || !records_len || !keys || !offs || !n || (!sam_lines && len) || !c->bam.has_header) return MONI_EINVAL;
     const auto t0 = std::chrono::steady_clock::now();
     auto& B = c->bsort;
@@ -91,6 +96,10 @@ int moni_bam_sorted_run(moni_ctx_t* c, const void* sam_lines, uint64_t len, cons
         HIPCHK(hipEventElapsedTime(&ms, c->bam.e0, c->bam.e1));
         st.t_encode = ms * 1e-3;
     }
+    if (rc == MONI_OK && ds) {          // a bad record here: its figures, and nothing goes back
+        rc = bam_dup_device(c, c->bam.out.p, enc_bytes, c->bam.off.p, n_rec, paired, *ds);
+        if (rc == MONI_EINVAL && ds->run.bad_records) { st.bad_records = ds->run.bad_records; st.first_bad_record = ds->run.first_bad_record; st.bad_reason = ds->run.bad_reason; }
+    }
     if (rc == MONI_OK) rc = B.h_rec.ensure(total + 1);
     if (rc == MONI_OK) rc = B.h_key.ensure(n_rec + 1);
     if (rc == MONI_OK) rc = B.h_off.ensure(n_rec + 1);
@@ -109,8 +118,14 @@ int moni_bam_sorted_run(moni_ctx_t* c, const void* sam_lines, uint64_t len, cons
     return rc;
 }
 
-int moni_bam_sort(moni_ctx_t* c, const void* records, uint64_t len, const uint64_t* offs, uint64_t n, const moni_bam_params_t* prm, const uint8_t** out,
-                  uint64_t* out_len, const moni_bam_ent_t** ents, moni_bam_sort_stats_t* stats) {
+int moni_bam_sorted_run(moni_ctx_t* c, const void* sam_lines, uint64_t len, const uint8_t** records, uint64_t* records_len, const uint64_t** keys,
+                        const uint64_t** offs, uint64_t* n, moni_bam_sort_stats_t* stats) {
+    return bam_sorted_run_core(c, sam_lines, len, records, records_len, keys, offs, n, stats, 0u, nullptr);
+}
+
+// moni_bam_sort; with marks, moni_bam_sort_marked
+static int bam_sort_core(moni_ctx_t* c, const void* records, uint64_t len, const uint64_t* offs, uint64_t n, const uint8_t* marks, const moni_bam_params_t* prm,
+                         const uint8_t** out, uint64_t* out_len, const moni_bam_ent_t** ents, moni_bam_sort_stats_t* stats) {
     if (!c || !prm || !out || !out_len || !ents || (!records && len) || (!offs && n)) return MONI_EINVAL;
     const moni_bgzf_params_t zp = {prm->block_size, prm->level, prm->raw ? 0u : prm->eof, 0u};
     if (!bgzf_params_ok(zp) || prm->eof > 1u || prm->raw > 1u || prm->reserved[0] || prm->reserved[1] || !c->bam.has_header) return MONI_EINVAL;
@@ -127,7 +142,8 @@ int moni_bam_sort(moni_ctx_t* c, const void* records, uint64_t len, const uint64
     else if ((rc = B.in.ensure(len + 8)) == MONI_OK && (rc = B.in_off.ensure(n + 1)) == MONI_OK && (rc = B.h_ents.ensure(n + 1)) == MONI_OK && n) {
         HIPCHK(hipMemcpyAsync(B.in.p, records, len, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(B.in_off.p, offs, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        rc = bam_sort_device(c, B.in.p, len, B.in_off.p, n, &total, st);
+        if (marks) rc = bam_setdup_device(c, B.in.p, len, B.in_off.p, n, marks);
+        if (rc == MONI_OK) rc = bam_sort_device(c, B.in.p, len, B.in_off.p, n, &total, st);
     }
     if (rc == MONI_OK) {
         if (n) HIPCHK(hipMemcpyAsync(B.h_ents.p, B.ents.p, n * sizeof(moni_bam_ent_t), hipMemcpyDeviceToHost, c->stream));
@@ -148,6 +164,11 @@ int moni_bam_sort(moni_ctx_t* c, const void* records, uint64_t len, const uint64
     st.t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;
     return rc;
+}
+
+int moni_bam_sort(moni_ctx_t* c, const void* records, uint64_t len, const uint64_t* offs, uint64_t n, const moni_bam_params_t* prm, const uint8_t** out,
+                  uint64_t* out_len, const moni_bam_ent_t** ents, moni_bam_sort_stats_t* stats) {
+    return bam_sort_core(c, records, len, offs, n, nullptr, prm, out, out_len, ents, stats);
 }
 
 // ---- host only: the merge plan and the .bai builder (bam_index.hpp) ----

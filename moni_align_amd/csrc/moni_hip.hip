@@ -50,6 +50,7 @@
 #include "bgzf_kernels.hip"
 #include "bam_kernels.hip"
 #include "bam_sort_kernels.hip"
+#include "bam_dup_kernels.hip"
 #include "bam_index.hpp"
 #include "inflate_kernels.hip"
 
@@ -263,6 +264,14 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
         DBuf<unsigned long long> ctr; HBuf<unsigned long long> h_sum; HBuf<uint8_t> h_rec; HBuf<uint64_t> h_key, h_off; HBuf<moni_bam_ent_t> h_ents;
         Event e0, e1, e2, e3, e4;
     } bsort;
+    struct BamDupBufs {     // duplicate marking (bam_dup_api.inc).  A run: the records' signatures, their places in the sorted run, the units' entry counts and their scan,
+                            // the entries and their pinned copy.  The resolve: all entries, where the runs' entries and marks begin, the records' places among all
+                            // marks, the first keys and the elements of both sorts, the keys and elements between the passes, the marks.  moni_bam_sort_marked: its marks.
+        DBuf<bam_dupsig_t> sig; DBuf<uint32_t> where; DBuf<uint64_t> cnt, pos; DBuf<moni_bam_dup_t> ent; HBuf<moni_bam_dup_t> h_ent;
+        DBuf<moni_bam_dup_t> all; DBuf<uint64_t> base, pkey, ekey, key[2]; DBuf<uint32_t> at, pidx, eidx, idx[2]; DBuf<uint8_t> marks, sort_tmp, marks_in;
+        DBuf<unsigned long long> ctr; HBuf<unsigned long long> h_ctr;
+        Event e0, e1, e2, e3, e4;
+    } bdup;
     struct InflateBufs {    // BGZF input (inflate_api.inc): the members and their table, the text and its pinned copy, a status per member; grow-only
         DBuf<uint8_t> in, out; DBuf<infl_member_t> mem; DBuf<uint32_t> status; DBuf<unsigned long long> counters;
         HBuf<infl_member_t> h_mem; HBuf<uint32_t> h_status; HBuf<unsigned long long> h_ctr; HBuf<uint8_t> h_out; Event e0, e1;
@@ -2118,6 +2127,7 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "bgzf_api.inc"
 #include "bam_api.inc"
 #include "bam_sort_api.inc"
+#include "bam_dup_api.inc"
 #include "inflate_api.inc"
 
 }  // extern "C"

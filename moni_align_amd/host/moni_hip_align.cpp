@@ -130,7 +130,10 @@ static std::string sorted_header(const char* h, uint64_t hl, bool sort) {
     return t;
 }
 struct SortedBam {
-    struct Run { uint64_t at = 0; std::vector<uint64_t> keys, offs{0}; };
+    struct Run { uint64_t at = 0; std::vector<uint64_t> keys, offs{0}; std::vector<moni_bam_dup_t> dups; std::vector<uint8_t> marks; };
+    bool mark = false;              // --mark-dup: the runs keep their entries, 32 bytes a pair or fragment; the marks, a byte a record, come between the phases
+    uint32_t paired = 0;            // the records of a run are mates two by two
+    uint64_t mark_max_entries = 1ull << 29;          // about 80 GB of the device's memory at 150 bytes an entry; the library's own limit is 2^31 - 1
     int tmp_fd = -1;
     uint64_t chunk_bytes = 0;
     uint32_t n_ref = 0;
@@ -150,9 +153,15 @@ struct SortedBam {
     }
     // run `id` (the batch's number in the input): the SAM lines through moni_bam_sorted_run on context c
     void add_run(moni_ctx_t* c, size_t id, const char* sam, uint64_t len) {
-        const uint8_t* rec; const uint64_t* keys; const uint64_t* offs; uint64_t rl, n;
-        moni_bam_sort_stats_t st;
-        const int rc = moni_bam_sorted_run(c, sam, len, &rec, &rl, &keys, &offs, &n, &st);
+        const uint8_t* rec; const uint64_t* keys; const uint64_t* offs; uint64_t rl, n, nd = 0;
+        const moni_bam_dup_t* dups = nullptr;
+        moni_bam_run_dup_stats_t ds;
+        memset(&ds, 0, sizeof ds);
+        const int rc = mark ? moni_bam_sorted_run_dup(c, sam, len, paired, &rec, &rl, &keys, &offs, &n, &dups, &nd, &ds) : moni_bam_sorted_run(c, sam, len, &rec, &rl, &keys, &offs, &n, &ds.run);
+        const moni_bam_sort_stats_t& st = ds.run;
+        if (rc == MONI_EINVAL && st.bad_records && ds.bad_is_record)
+            die("moni_bam_sorted_run_dup: " + std::to_string(st.bad_records) + " record(s) of a batch cannot be marked; the first is its record " +
+                std::to_string(st.first_bad_record) + " (reason " + std::to_string(st.bad_reason) + " of MONI_BAMSORT_*)");
         if (rc == MONI_EINVAL && st.bad_records)
             die("moni_bam_sorted_run: " + std::to_string(st.bad_records) + " line(s) of a batch cannot be written as BAM records; the first is its line " +
                 std::to_string(st.first_bad_record) + " (reason " + std::to_string(st.bad_reason) + " of MONI_BAM_*)");
@@ -160,6 +169,7 @@ struct SortedBam {
         Run r;
         r.at = tmp_len.fetch_add(rl);
         r.keys.assign(keys, keys + n); r.offs.assign(offs, offs + n + 1);
+        if (nd) r.dups.assign(dups, dups + nd);
         for (uint64_t done = 0; done < rl;) {
             const ssize_t w = pwrite(tmp_fd, rec + done, rl - done, (off_t)(r.at + done));
             if (w <= 0) die("short write to the sort's temporary file");
@@ -167,6 +177,29 @@ struct SortedBam {
         }
         std::lock_guard<std::mutex> lk(mu);
         runs[id] = std::move(r);
+    }
+    // --mark-dup, between the phases: one context resolves the entries of all runs; every run gets its marks, a byte a record in sorted order.
+    // On the device the resolve holds 124 bytes an entry (the entries, the keys and elements of its sorts before and behind a pass - of twice as
+    // many ends as entries -, the records' places), a byte a record and the radix sort's own space: about 150 bytes an entry.  More than
+    // mark_max_entries is refused here; a device that has less free memory makes moni_bam_dup_resolve return MONI_ENOMEM.
+    void resolve(moni_ctx_t* c, const std::vector<Run*>& run) {
+        const size_t R = run.size();
+        std::vector<const moni_bam_dup_t*> dp(R); std::vector<uint8_t*> mp(R); std::vector<uint64_t> nd(R), nr(R);
+        uint64_t entries = 0, records = 0;
+        for (size_t r = 0; r < R; ++r) {
+            run[r]->marks.assign(run[r]->keys.size(), 0);
+            dp[r] = run[r]->dups.data(); mp[r] = run[r]->marks.data(); nd[r] = run[r]->dups.size(); nr[r] = run[r]->keys.size();
+            entries += nd[r]; records += nr[r];
+        }
+        if (entries > mark_max_entries || records >= 0xFFFFFFFFull)
+            die("--mark-dup: " + std::to_string(entries) + " pairs and fragments in " + std::to_string(records) + " records are more than one GPU resolves (" +
+                std::to_string(mark_max_entries) + " entries, 2^32 - 2 records); split the input");
+        moni_bam_dup_stats_t st;
+        const int rc = moni_bam_dup_resolve(c, dp.data(), nd.data(), nr.data(), R, mp.data(), &st);
+        if (rc) die("moni_bam_dup_resolve failed (" + std::to_string(rc) + ")");
+        for (size_t r = 0; r < R; ++r) std::vector<moni_bam_dup_t>().swap(run[r]->dups);
+        info("Duplicates: " + std::to_string(st.dup_pairs) + " of " + std::to_string(st.pairs) + " pairs, " + std::to_string(st.dup_fragments) + " of " + std::to_string(st.fragments) +
+             " fragments, " + std::to_string(st.marked_records) + " records marked");
     }
     // the chunks behind `at` in fd, then the index; returns where the end-of-file block goes
     uint64_t finish(const std::vector<moni_ctx_t*>& cs, int fd, uint64_t at) {
@@ -178,6 +211,7 @@ struct SortedBam {
         std::vector<const uint64_t*> kp(R), op(R);
         std::vector<uint64_t> nn(R);
         for (size_t r = 0; r < R; ++r) { kp[r] = run[r]->keys.data(); op[r] = run[r]->offs.data(); nn[r] = run[r]->keys.size(); }
+        if (mark) resolve(cs[0], run);
         moni_bam_plan_t* plan = nullptr;
         if (moni_bam_merge_plan(kp.data(), nn.data(), op.data(), R, chunk_bytes, &plan)) die("moni_bam_merge_plan failed");
         moni_bai_t* bai = moni_bai_create(n_ref);
@@ -187,12 +221,12 @@ struct SortedBam {
         std::mutex mo; std::condition_variable cv;
         uint64_t upto = 0, off_upto = at;
         auto worker = [&](moni_ctx_t* c) {
-            std::vector<uint8_t> buf; std::vector<uint64_t> offs; std::vector<uint32_t> cs_;
+            std::vector<uint8_t> buf, mk; std::vector<uint64_t> offs; std::vector<uint32_t> cs_;
             for (uint64_t k; (k = next.fetch_add(1)) < plan->n_chunks;) {
                 const uint64_t* lo = plan->cuts + k * R; const uint64_t* hi = lo + R;
                 uint64_t bytes = 0, n = 0;
                 for (size_t r = 0; r < R; ++r) { bytes += run[r]->offs[hi[r]] - run[r]->offs[lo[r]]; n += hi[r] - lo[r]; }
-                buf.resize(bytes); offs.assign(1, 0);
+                buf.resize(bytes); offs.assign(1, 0); mk.clear();
                 for (size_t r = 0; r < R; ++r) {
                     const uint64_t a0 = run[r]->offs[lo[r]], a1 = run[r]->offs[hi[r]], base = offs.back();
                     for (uint64_t done = 0; done < a1 - a0;) {
@@ -201,9 +235,10 @@ struct SortedBam {
                         done += (uint64_t)g;
                     }
                     for (uint64_t i = lo[r]; i < hi[r]; ++i) offs.push_back(base + run[r]->offs[i + 1] - a0);
+                    if (mark) mk.insert(mk.end(), run[r]->marks.begin() + (ptrdiff_t)lo[r], run[r]->marks.begin() + (ptrdiff_t)hi[r]);
                 }
                 const uint8_t* z; uint64_t zl; const moni_bam_ent_t* ents; moni_bam_sort_stats_t st;
-                const int rc = moni_bam_sort(c, buf.data(), bytes, offs.data(), n, &bp, &z, &zl, &ents, &st);
+                const int rc = moni_bam_sort_marked(c, buf.data(), bytes, offs.data(), n, mark ? mk.data() : nullptr, &bp, &z, &zl, &ents, &st);
                 if (rc) die("moni_bam_sort failed (" + std::to_string(rc) + ")");
                 cs_.clear();
                 for (uint64_t p = 0; p < zl;) { const uint32_t b = (uint32_t)z[p + 16] + ((uint32_t)z[p + 17] << 8) + 1u; cs_.push_back(b); p += b; }
@@ -396,6 +431,7 @@ struct Args {
     bool bam = false;                  // --bam: the SAM lines as BAM records in BGZF blocks in <out>.bam, encoded and deflated on the GPU by the context that aligned them (moni_bam_records)
     bool sort = false;                 // --sort (with --bam): the records in coordinate order, with <out>.bam.bai beside them
     uint64_t sort_chunk = 256ull << 20; bool sort_chunk_set = false;      // --sort-chunk: uncompressed bytes of a chunk of the merge
+    bool mark_dup = false;             // --mark-dup (with --sort): duplicates flagged 0x400 on the GPU between the two phases of the sort
     bool blocks() const { return bgzf || bam; }          // the output is a sequence of BGZF blocks
     bool bgzf = false;                 // --bgzf: the SAM text as BGZF blocks in <out>.gz, deflated on the GPU by the context that aligned it (moni_bgzf_compress)
 };
@@ -417,6 +453,7 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--inflate-blocks") && i + 1 < argc) { a.inflate_blocks = std::max<size_t>(1, strtoull(argv[++i], nullptr, 10)); continue; }
         if (!strcmp(argv[i], "--bam")) { a.bam = true; continue; }
         if (!strcmp(argv[i], "--sort")) { a.sort = true; continue; }
+        if (!strcmp(argv[i], "--mark-dup")) { a.mark_dup = true; continue; }
         if (!strcmp(argv[i], "--sort-chunk") && i + 1 < argc) { a.sort_chunk = strtoull(argv[++i], nullptr, 10); a.sort_chunk_set = true; continue; }
         if (!strcmp(argv[i], "--ms")) { a.legacy_ms = true; continue; }
         if (!strcmp(argv[i], "--mems")) { a.legacy_mems = true; continue; }
@@ -449,14 +486,15 @@ static void parse(int argc, char** argv, Args& a) {
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--sort [--sort-chunk BYTES]] [--host-inflate] [--inflate-blocks N] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--sort [--sort-chunk BYTES]] [--mark-dup] [--host-inflate] [--inflate-blocks N] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
                               "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n"
                               "  --bgzf: the SAM output (single end, -1 / -2, -m, --extend) as blocked gzip in <output>.gz, compressed on the GPU; samtools, htslib and bgzip -d read it as SAM\n"
                               "  --host-inflate: BGZF (blocked gzip) input of single-end and -1 / -2 alignment is inflated on the GPU; this option sends it through zlib on the host, as plain gzip, -m, -c, --extend, the legacy and pattern-query modes and FASTA with wrapped lines always go\n"
                               "  --inflate-blocks N: BGZF members inflated per call (4096, about 256 MB of text)\n"
                               "  --bam: the SAM output (the same four modes) as BAM in <output>.bam (a trailing .sam becomes .bam): header and records encoded and compressed on the GPU, unsorted, no index\n"
                               "  --sort: with --bam, the records in coordinate order (samtools sort's: reference, position, forward strand first; ties keep input order) under @HD SO:coordinate, and the index in <output>.bam.bai; sorted on the GPU, merged through a temporary file beside the output\n"
-                              "  --sort-chunk BYTES: uncompressed bytes of the records sorted and compressed per call in the merge (268435456; at least 65536)\n";
+                              "  --sort-chunk BYTES: uncompressed bytes of the records sorted and compressed per call in the merge (268435456; at least 65536)\n"
+                              "  --mark-dup: with --sort (single end and -1 / -2), duplicates get flag 0x400 (Picard's rule on unclipped 5' ends, strands and the sum of base qualities of 15 and more; no optical duplicates, no UMIs): signatures on the GPU while a batch's records are still there, one resolve over all batches between the two phases of the sort, the flags set as the chunks are merged\n";
     int c;
     char* s;
     optind = 1;
@@ -940,7 +978,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         const size_t n = read_pairs(r1, r2, (size_t)-1, b);
         printf("dry-run: pairs=%zu bases=%zu min_len=%u filter_dir=%u dir_thr=%.1f find_orphan=%u b=%zu threads=%zu gpus=%d out=%s first=%.*s second=%.*s%s%s\n", n, b.seq.size(),
                a.P.min_len, a.PE.filter_dir, a.PE.dir_thr, a.PE.find_orphan, a.b, a.th, a.gpus, sam_filename.c_str(), n ? (int)b.name_off[1] : 0,
-               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", a.bgzf ? " bgzf=1" : a.bam ? (a.sort ? " bam=1 sort=1" : " bam=1") : "", bz_in ? " input=bgzf" : "");
+               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", a.bgzf ? " bgzf=1" : a.bam ? (a.sort ? (a.mark_dup ? " bam=1 sort=1 markdup=1" : " bam=1 sort=1") : " bam=1") : "", bz_in ? " input=bgzf" : "");
         return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
@@ -971,7 +1009,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         moni_free(h);
     }
     SortedBam sorted;          // --sort: the learning batches are run 0, the workers' batches follow
-    if (a.sort) sorted.open(sam_filename, a.sort_chunk, header_text);
+    if (a.sort) { sorted.mark = a.mark_dup; sorted.paired = 1; sorted.open(sam_filename, a.sort_chunk, header_text); }
     // -c: <sam>.csv, one line per pair (aligner_ksw2.hpp:911-914; header of aligner::to_csv, :3230-3234); the blocks of the batches are kept and written in input order at the end
     FILE* out2 = nullptr;
     std::map<size_t, std::string> csv_blocks;
@@ -1534,6 +1572,11 @@ int main(int argc, char** argv) {
         if (a.approx) die("--sort cannot be combined with --approx");
         if (a.sort_chunk < 65536) die("--sort-chunk takes at least 65536 bytes");
     } else if (a.sort_chunk_set) die("--sort-chunk belongs to --sort");
+    if (a.mark_dup) {        // duplicate marking: a decision over the whole input, so it lives between the two phases of the sort; one record per read
+        if (!a.sort) die("--mark-dup belongs to --sort");
+        if (a.extend) die("--mark-dup cannot be combined with --extend");
+        if (a.report_mems) die("--mark-dup cannot be combined with -m");
+    }
     if (a.bam) {             // BAM output: the modes that write SAM, and one container
         if (a.bgzf) die("--bam cannot be combined with --bgzf");
         if (a.csv) die("--bam cannot be combined with -c");
@@ -1582,7 +1625,7 @@ int main(int argc, char** argv) {
         }
         printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s%s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), a.bgzf ? " bgzf=1" : a.bam ? (a.sort ? " bam=1 sort=1" : " bam=1") : "", bz ? " input=bgzf" : "");
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), a.bgzf ? " bgzf=1" : a.bam ? (a.sort ? (a.mark_dup ? " bam=1 sort=1 markdup=1" : " bam=1 sort=1") : " bam=1") : "", bz ? " input=bgzf" : "");
         if (!a.dry_write || !mapped) return 0;
     }
     const std::string idx_path = a.filename + ".mfi";
@@ -1622,7 +1665,7 @@ int main(int argc, char** argv) {
             if (a.bgzf) bgzf_blocks(ctx[0], h, hl, false, &hz, &hzl);          // the header as blocks of its own, before the workers take the contexts
             const std::string bh = sorted_header(h, hl, a.sort);
             if (a.bam) bam_header_blocks(ctx, bh.data(), bh.size(), &hz, &hzl);               // ... as a BAM header, and every context learns its dictionary
-            if (a.sort) sorted.open(sam_filename, a.sort_chunk, bh);
+            if (a.sort) { sorted.mark = a.mark_dup; sorted.open(sam_filename, a.sort_chunk, bh); }
             pwrite_all(fd, hz, hzl, 0); hdr_len = hzl; moni_free(h);
         }
         std::mutex mu; std::condition_variable cv;
@@ -1728,7 +1771,7 @@ int main(int argc, char** argv) {
         out = fopen(sam_filename.c_str(), "w");
         if (!out) die("open() file " + sam_filename + " failed");
         char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
-        if (a.bam) { const char* z; uint64_t zl; const std::string bh = sorted_header(h, hl, a.sort); bam_header_blocks(ctx, bh.data(), bh.size(), &z, &zl); put(z, zl, out); if (a.sort) sorted.open(sam_filename, a.sort_chunk, bh); }
+        if (a.bam) { const char* z; uint64_t zl; const std::string bh = sorted_header(h, hl, a.sort); bam_header_blocks(ctx, bh.data(), bh.size(), &z, &zl); put(z, zl, out); if (a.sort) { sorted.mark = a.mark_dup; sorted.open(sam_filename, a.sort_chunk, bh); } }
         else if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], h, hl, false, &z, &zl); put(z, zl, out); } else put(h, hl, out);
         moni_free(h);
         if (a.csv) {          // -c: <sam>.csv (align_reads_dispatcher.hpp:302,334-339), header of aligner::to_csv (aligner_ksw2.hpp:3230-3234)
