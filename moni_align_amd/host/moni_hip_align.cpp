@@ -21,6 +21,11 @@
 // record-aligned text to the same workers, which parse it as if it were a range of a mapped plain file); --host-inflate, plain gzip, -m, -c,
 // --extend, the legacy and pattern-query modes and FASTA with wrapped lines stay on the older path.  -m writes the report-MEMs records (aligner_ksw2.hpp:346-373);
 // --ms / --mems write the legacy `moni ms` / `moni mems` text outputs (src/matching_statistics.cpp:520-610, src/mems.cpp:520-600).
+// Output: the three pipelines that write SAM - pairs (run_paired), single-end streaming, single-end queue - write through one Sink (below, behind parse): it
+// opens the file, writes the header in the flavour's form (text, --bgzf blocks, --bam, --bam --sort [--mark-dup]) and sets the BAM dictionary on the contexts,
+// turns a batch's text into the bytes that go into the file (or into a run of the sort), and ends the file (the sort's merge and index, the end-of-file
+// block, the close).  Its Placer puts blocks that come in any order at the in-order prefix sum of their lengths with pwrite in parallel slices; both streaming
+// pipelines use it, paired -c a second one for <sam>.csv, and the queue pipeline's writer thread appends.  The pattern modes write their own <out><suffix> files.
 // --ms / --mems --split [--seg-len N] [--overlap N] take patterns of genome length (a chromosome, an assembly) through moni_ms_long_batch: every pattern
 // is cut into segments of N bases that are walked side by side, and batches are sized by bases, not by reads.  .lengths and the (offset,length) pairs
 // of .mems are byte-identical to the run without --split; .pointers may differ where a pattern was cut - every pointer is a position of a maximal
@@ -83,52 +88,20 @@ static void die(const std::string& msg) { fprintf(stderr, "[ERROR] %s\n", msg.c_
 static void put(const void* p, size_t n, FILE* f) { if (n && fwrite(p, 1, n, f) != n) die("short write to the output file"); }
 static void close_out(FILE* f) { if (f && fclose(f) != 0) die("closing the output file failed (output incomplete)"); }
 static void info(const std::string& msg) { printf("[INFO] Message: %s\n", msg.c_str()); fflush(stdout); }
-// --bgzf: `len` bytes of text as BGZF blocks, in the context's pinned buffer until its next call; eof: the end-of-file block behind them
-static void bgzf_blocks(moni_ctx_t* c, const char* text, uint64_t len, bool eof, const char** z, uint64_t* zl) {
-    moni_bgzf_params_t bp; moni_bgzf_params_default(&bp);
-    bp.eof = eof ? 1 : 0;
-    const uint8_t* o = nullptr;
-    const int rc = moni_bgzf_compress(c, text, len, &bp, &o, zl, nullptr);
-    if (rc) die("moni_bgzf_compress failed (" + std::to_string(rc) + ")");
-    *z = (const char*)o;
+// every byte of [p, p + n) at `at` in fd
+static void pwrite_all(int fd, const char* p, size_t n, uint64_t at) {
+    while (n) {
+        const ssize_t w = pwrite(fd, p, n, (off_t)at);
+        if (w < 0) { if (errno == EINTR) continue; die("write to the output file failed"); }
+        p += w; n -= (size_t)w; at += (uint64_t)w;
+    }
 }
-// --bam: `len` bytes of SAM lines as BAM records in BGZF blocks (moni_bam_records, against the header bam_header_blocks set on this context), in the
-// context's pinned buffer until its next call
-static void bam_blocks(moni_ctx_t* c, const char* text, uint64_t len, const char** z, uint64_t* zl) {
-    moni_bam_params_t bp; moni_bam_params_default(&bp);
-    const uint8_t* o = nullptr;
-    moni_bam_stats_t st;
-    const int rc = moni_bam_records(c, text, len, &bp, &o, zl, &st);
-    if (rc == MONI_EINVAL && st.bad_lines)
-        die("moni_bam_records: " + std::to_string(st.bad_lines) + " line(s) of a batch cannot be written as BAM records; the first is its line " + std::to_string(st.first_bad_line) +
-            " (reason " + std::to_string(st.bad_reason) + " of MONI_BAM_*)");
-    if (rc) die("moni_bam_records failed (" + std::to_string(rc) + ")");
-    *z = (const char*)o;
-}
-// --bam: the SAM header becomes the dictionary of every context that will encode records; bh: the BAM header, in cs[0]'s buffer
-static void bam_set_headers(const std::vector<moni_ctx_t*>& cs, const char* h, uint64_t hl, const uint8_t** bh, uint64_t* bhl) {
-    for (size_t k = cs.size(); k-- > 0;)
-        if (moni_bam_set_header(cs[k], h, hl, bh, bhl)) die("moni_bam_set_header failed: the SAM header's @SQ lines do not make a BAM dictionary");
-}
-// ... and the BAM header as BGZF blocks of its own, in cs[0]'s pinned buffer until its next call
-static void bam_header_blocks(const std::vector<moni_ctx_t*>& cs, const char* h, uint64_t hl, const char** z, uint64_t* zl) {
-    const uint8_t* bh = nullptr; uint64_t bhl = 0;
-    bam_set_headers(cs, h, hl, &bh, &bhl);
-    bgzf_blocks(cs[0], (const char*)bh, bhl, false, z, zl);
-}
-
 
 // ---- --bam --sort: coordinate-sorted, indexed BAM -----------------------------------------------------------------------
 // Phase 1: every batch's SAM text becomes a sorted run (moni_bam_sorted_run on the context that aligned it); the run's records go to a temporary
 // file beside the output - unlinked as soon as it is open -, its keys and offsets stay in memory, 16 bytes a read.  Phase 2, behind the last
 // batch: moni_bam_merge_plan cuts the merged order into chunks, one contiguous slice of every run each; the contexts take the chunks in turn -
 // pread the slices, moni_bam_sort, the blocks at their place in the file - and moni_bai_add sees them in chunk order.
-static std::string sorted_header(const char* h, uint64_t hl, bool sort) {
-    std::string t(h, hl);
-    const size_t at = sort ? t.find("SO:unknown") : std::string::npos;
-    if (at != std::string::npos && t.compare(0, 3, "@HD") == 0 && at < t.find('\n')) t.replace(at, 10, "SO:coordinate");
-    return t;
-}
 struct SortedBam {
     struct Run { uint64_t at = 0; std::vector<uint64_t> keys, offs{0}; std::vector<moni_bam_dup_t> dups; std::vector<uint8_t> marks; };
     bool mark = false;              // --mark-dup: the runs keep their entries, 32 bytes a pair or fragment; the marks, a byte a record, come between the phases
@@ -432,7 +405,6 @@ struct Args {
     bool sort = false;                 // --sort (with --bam): the records in coordinate order, with <out>.bam.bai beside them
     uint64_t sort_chunk = 256ull << 20; bool sort_chunk_set = false;      // --sort-chunk: uncompressed bytes of a chunk of the merge
     bool mark_dup = false;             // --mark-dup (with --sort): duplicates flagged 0x400 on the GPU between the two phases of the sort
-    bool blocks() const { return bgzf || bam; }          // the output is a sequence of BGZF blocks
     bool bgzf = false;                 // --bgzf: the SAM text as BGZF blocks in <out>.gz, deflated on the GPU by the context that aligned it (moni_bgzf_compress)
 };
 
@@ -540,6 +512,122 @@ static void parse(int argc, char** argv, Args& a) {
     if (a.th > 1) a.P.host_threads = (uint32_t)a.th;
 }
 
+// what --dry-run says of the output's kind
+static const char* output_word(const Args& a) { return a.bgzf ? " bgzf=1" : !a.bam ? "" : !a.sort ? " bam=1" : a.mark_dup ? " bam=1 sort=1 markdup=1" : " bam=1 sort=1"; }
+
+// ---- the output of a run that writes SAM ------------------------------------------------------------------------------------------------
+// Placer: blocks that come in any order land in one file in the order of their ids, each at the prefix sum of the lengths before it.
+struct Placer {
+    int fd = -1;
+    uint64_t end = 0;               // behind everything appended or placed so far
+    std::mutex mu; std::condition_variable cv;
+    std::vector<uint64_t> slot;     // of an id: ~0, then the length it reported, then - once all ids before it have reported - its place
+    size_t upto = 0;                // the ids below have their place
+    void open(const std::string& path) {
+        fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        if (fd < 0) die("open() file " + path + " failed");
+    }
+    // a block behind the rest: for the one thread that writes before the placing starts, after it has ended, or instead of it
+    void append(const void* p, uint64_t n) { pwrite_all(fd, (const char*)p, n, end); end += n; }
+    // block `id` has `len` bytes: waits until every earlier id has reported and returns where the block goes.  The ids count from 0; how many come need not be known.
+    uint64_t place(size_t id, uint64_t len) {
+        std::unique_lock<std::mutex> lk(mu);
+        if (slot.size() <= id) slot.resize(id + 1, ~0ull);
+        slot[id] = len;
+        for (; upto < slot.size() && slot[upto] != ~0ull; ++upto) { const uint64_t l = slot[upto]; slot[upto] = end; end += l; }
+        cv.notify_all();
+        cv.wait(lk, [&] { return upto > id; });
+        return slot[id];
+    }
+    // the block at its place, in P slices side by side
+    void write(const char* p, uint64_t len, uint64_t at, int P) const {
+        if (!len) return;
+        std::vector<std::thread> th;
+        const size_t sl = (len + P - 1) / P;
+        for (int i = 1; i < P; ++i) { const size_t lo = std::min<size_t>(len, sl * i), hi = std::min<size_t>(len, sl * (i + 1)); if (hi > lo) th.emplace_back(pwrite_all, fd, p + lo, hi - lo, at + lo); }
+        pwrite_all(fd, p, std::min<size_t>(len, sl), at);
+        for (auto& t : th) t.join();
+    }
+    void close(const char* msg) { if (::close(fd) != 0) die(msg); fd = -1; }
+};
+
+// Sink: the file of a SAM-writing run in the flavour the flags ask for - the text, the text as BGZF blocks (--bgzf), BAM (--bam), or coordinate-sorted BAM with
+// its index (--sort, with duplicates marked under --mark-dup).  All three pipelines (pairs, single-end streaming, single-end queue) write through it: begin,
+// encode per batch, the block placed (Placer) or appended, finish.  A new flavour is added here and nowhere else.
+struct Block { const char* p; uint64_t n; };
+struct Sink : Placer {
+    bool bgzf = false, bam = false, sort = false;
+    uint64_t sort_chunk = 0;
+    std::string path, header;       // header: the SAM header whose @SQ lines are the BAM dictionary (under --sort with SO:coordinate)
+    SortedBam sorted;               // --sort: a batch is a run; nothing but the header reaches the file before finish
+
+    // `len` bytes of text as BGZF blocks, in the context's pinned buffer until its next call; eof: the end-of-file block behind them
+    static Block bgzf_blocks(moni_ctx_t* c, const char* text, uint64_t len, bool eof) {
+        moni_bgzf_params_t bp; moni_bgzf_params_default(&bp);
+        bp.eof = eof ? 1 : 0;
+        const uint8_t* o = nullptr; uint64_t zl = 0;
+        const int rc = moni_bgzf_compress(c, text, len, &bp, &o, &zl, nullptr);
+        if (rc) die("moni_bgzf_compress failed (" + std::to_string(rc) + ")");
+        return {(const char*)o, zl};
+    }
+    // `len` bytes of SAM lines as BAM records in BGZF blocks (moni_bam_records, against the dictionary set on this context), in the context's pinned buffer until its next call
+    static Block bam_blocks(moni_ctx_t* c, const char* text, uint64_t len) {
+        moni_bam_params_t bp; moni_bam_params_default(&bp);
+        const uint8_t* o = nullptr; uint64_t zl = 0;
+        moni_bam_stats_t st;
+        const int rc = moni_bam_records(c, text, len, &bp, &o, &zl, &st);
+        if (rc == MONI_EINVAL && st.bad_lines)
+            die("moni_bam_records: " + std::to_string(st.bad_lines) + " line(s) of a batch cannot be written as BAM records; the first is its line " + std::to_string(st.first_bad_line) +
+                " (reason " + std::to_string(st.bad_reason) + " of MONI_BAM_*)");
+        if (rc) die("moni_bam_records failed (" + std::to_string(rc) + ")");
+        return {(const char*)o, zl};
+    }
+
+    void open(const std::string& file, const Args& a, bool paired) {
+        path = file; bgzf = a.bgzf; bam = a.bam; sort = a.sort; sort_chunk = a.sort_chunk;
+        sorted.mark = a.mark_dup; sorted.paired = paired ? 1 : 0;
+        Placer::open(file);
+    }
+    // --bam: the header becomes the dictionary of every context that will encode records; returns the BAM header, in cs[0]'s buffer.  begin calls it; a pipeline
+    // that makes further contexts behind begin calls it for those.
+    Block set_dictionary(const std::vector<moni_ctx_t*>& cs) const {
+        const uint8_t* bh = nullptr; uint64_t bhl = 0;
+        for (size_t k = cs.size(); bam && k-- > 0;)
+            if (moni_bam_set_header(cs[k], header.data(), header.size(), &bh, &bhl)) die("moni_bam_set_header failed: the SAM header's @SQ lines do not make a BAM dictionary");
+        return {(const char*)bh, bhl};
+    }
+    // the header at the start of the file, in the flavour's form (blocks of its own, made on cs[0] before the workers take the contexts); `end` is where the body starts
+    void begin(moni_index_t* idx0, const std::vector<moni_ctx_t*>& cs) {
+        char* h; uint64_t hl; if (moni_sam_header(idx0, &h, &hl)) die("header");
+        Block z{h, hl};
+        if (bgzf) z = bgzf_blocks(cs[0], h, hl, false);
+        if (bam) {
+            header.assign(h, hl);
+            const size_t at = sort ? header.find("SO:unknown") : std::string::npos;
+            if (at != std::string::npos && header.compare(0, 3, "@HD") == 0 && at < header.find('\n')) header.replace(at, 10, "SO:coordinate");
+            z = set_dictionary(cs);
+            z = bgzf_blocks(cs[0], z.p, z.n, false);
+        }
+        append(z.p, z.n);
+        moni_free(h);
+        if (sort) sorted.open(path, sort_chunk, header);
+    }
+    // what goes into the file for a batch's text: the text itself, its blocks in c's pinned buffer (valid until c's next library call), or nothing - the batch
+    // became run `run_id` of the sort
+    Block encode(moni_ctx_t* c, size_t run_id, const char* text, uint64_t len) {
+        if (sort) { sorted.add_run(c, run_id, text, len); return {nullptr, 0}; }
+        if (bam) return bam_blocks(c, text, len);
+        if (bgzf) return bgzf_blocks(c, text, len, false);
+        return {text, len};
+    }
+    // behind the last batch: the merged chunks and the index of the sort over all contexts, the end-of-file block of the block flavours, the close
+    void finish(const std::vector<moni_ctx_t*>& cs) {
+        if (sort) end = sorted.finish(cs, fd, end);
+        if (bgzf || bam) { const Block z = bgzf_blocks(cs[0], nullptr, 0, true); append(z.p, z.n); }
+        close("closing the output file failed (output incomplete)");
+    }
+};
+
 
 // ---- streaming path for plain files ---------------------------------------------------------------------------------------------------
 namespace fastpath {
@@ -634,14 +722,6 @@ static void parse_range(const char* a, const char* b, const char* base, const ch
     if (B.off.size() < B.n + 1) { B.off.resize(B.n + 1 + B.n / 8); B.name_off.resize(B.n + 1 + B.n / 8); }
     B.off[0] = 0; B.name_off[0] = 0;
     run([&](int i) { walk<true>(cut[i], cut[i + 1], fq, B.seq.p, B.qual.p, B.names.p, B.off.data() + n_at[i], B.name_off.data() + n_at[i], s_at[i], m_at[i]); });
-}
-
-static void pwrite_all(int fd, const char* p, size_t n, uint64_t at) {
-    while (n) {
-        const ssize_t w = pwrite(fd, p, n, (off_t)at);
-        if (w < 0) { if (errno == EINTR) continue; die("write to the output file failed"); }
-        p += w; n -= (size_t)w; at += (uint64_t)w;
-    }
 }
 
 // the end of the n_rec-th record from s in a mapped four-line FASTQ file (or the end of the file; got = the records before it): the newlines of a
@@ -965,6 +1045,47 @@ static size_t read_pairs_par(AnyReader& r1, AnyReader& r2, size_t n_pairs, Batch
     for (auto& t : th) t.join();
     return n;
 }
+// the index on GPU g: <prefix>.mfi, or the reference's own files when that one is absent
+static moni_index_t* load_index(const Args& a, int g) {
+    const std::string idx_path = a.filename + ".mfi";
+    const bool have_mfi = !a.no_lcp && access(idx_path.c_str(), R_OK) == 0;          // (the flat file always carries the LCP samples)
+    const std::string ms_path = a.filename + (a.no_lcp ? ".thrbv.full.ms" : ".thrbv.full.lcp.ms"), ldx_path = a.filename + ".ldx", txt_path = a.filename + ".txt";
+    const bool have_txt = access(txt_path.c_str(), R_OK) == 0;          // optional: without it the text is rebuilt from the BWT on the GPU
+    moni_index_t* idx = nullptr;
+    if (have_mfi) { if (moni_index_load(idx_path.c_str(), g, &idx)) die("cannot load " + idx_path + " on GPU " + std::to_string(g) + " (moni-hip has no CPU path)"); }
+    else if (moni_index_load_reference(ms_path.c_str(), ldx_path.c_str(), have_txt ? txt_path.c_str() : nullptr, g, &idx))
+        die("cannot load " + idx_path + " nor " + ms_path + " + " + ldx_path + " (reader of the reference's files: layout unverified against a real `moni build` output) on GPU " + std::to_string(g) + " (moni-hip has no CPU path)");
+    return idx;
+}
+// a batch of interleaved mates as the library takes it: the slow reader's Batch, or the fast reader's PairBatch (both mate files four-line FASTQ)
+struct PairView {
+    const uint8_t* seq; const uint64_t* off; const uint8_t* names; const uint64_t* name_off; const uint8_t* qual; size_t n;
+    PairView(const Batch& b) : seq(b.seq.data()), off(b.off.data()), names(b.names.data()), name_off(b.name_off.data()), qual(b.has_qual ? b.qual.data() : nullptr), n(b.n()) {}
+    PairView(const fastpath::PairBatch& f) : seq(f.seq.p), off(f.off.data()), names(f.names.p), name_off(f.name_off.data()), qual(f.qual.p), n(f.n_reads) {}
+};
+// The paired library call the flags choose: -m the MEM records instead of the pairs' (the fragment model plays no part in them), -c the records and <sam>.csv's
+// lines, else the records alone - with `pinned` in C's pinned buffer, to be written out before C's next call, not freed.  owned: sam is moni_free's; csv always is.
+struct PairOut { char* sam = nullptr; uint64_t len = 0; char* csv = nullptr; uint64_t csv_len = 0; size_t aligned = 0; bool owned = true; };
+static PairOut pe_call(moni_ctx_t* C, const PairView& v, const Args& a, const moni_pe_model_t& model, bool pinned) {
+    const moni_read_batch_t rb{v.seq, v.off, v.n};
+    PairOut o;
+    moni_align_stats_t st;
+    if (a.report_mems) {
+        const int rm = moni_pe_report_mems_batch(C, &rb, v.names, v.name_off, v.qual, &a.P, &a.PE, &o.sam, &o.len);
+        if (rm) die("moni_pe_report_mems_batch failed (" + std::to_string(rm) + ")");
+        return o;
+    }
+    if (a.csv) {
+        const int rc = moni_pe_align_csv_batch(C, &rb, v.names, v.name_off, v.qual, &a.P, &a.PE, &model, &o.sam, &o.len, &o.csv, &o.csv_len, &st);
+        if (rc) die("moni_pe_align_csv_batch failed (" + std::to_string(rc) + ")");
+    } else {
+        const int rc = (pinned ? moni_pe_align_stream : moni_pe_align_batch)(C, &rb, v.names, v.name_off, v.qual, &a.P, &a.PE, &model, &o.sam, &o.len, &st);
+        if (rc) die(std::string(pinned ? "moni_pe_align_stream" : "moni_pe_align_batch") + " failed (" + std::to_string(rc) + (rc == MONI_ERANGE ? ": a pair exceeds the paired path's capacities)" : ")"));
+        o.owned = !pinned;
+    }
+    o.aligned = st.aligned;
+    return o;
+}
 static int run_paired(Args& a, const std::string& sam_filename) {
     a.PE.find_orphan = a.find_orphan ? 1 : 0;            // -u switches orphan recovery off (align_full_ksw2.cpp:248-250)
     a.PE.secondary_chains = a.secondary ? 1 : 0;         // -Z: find_chains_secondary (the second track of the chaining, on the staged paired kernels)
@@ -978,73 +1099,31 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         const size_t n = read_pairs(r1, r2, (size_t)-1, b);
         printf("dry-run: pairs=%zu bases=%zu min_len=%u filter_dir=%u dir_thr=%.1f find_orphan=%u b=%zu threads=%zu gpus=%d out=%s first=%.*s second=%.*s%s%s\n", n, b.seq.size(),
                a.P.min_len, a.PE.filter_dir, a.PE.dir_thr, a.PE.find_orphan, a.b, a.th, a.gpus, sam_filename.c_str(), n ? (int)b.name_off[1] : 0,
-               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", a.bgzf ? " bgzf=1" : a.bam ? (a.sort ? (a.mark_dup ? " bam=1 sort=1 markdup=1" : " bam=1 sort=1") : " bam=1") : "", bz_in ? " input=bgzf" : "");
+               n ? (const char*)b.names.data() : "", n ? (int)(b.name_off[2] - b.name_off[1]) : 0, n ? (const char*)b.names.data() + b.name_off[1] : "", output_word(a), bz_in ? " input=bgzf" : "");
         return 0;
     }
-    const std::string idx_path = a.filename + ".mfi";
-    const bool have_mfi = !a.no_lcp && access(idx_path.c_str(), R_OK) == 0;          // (the flat file always carries the LCP samples)
-    const std::string ms_path = a.filename + (a.no_lcp ? ".thrbv.full.ms" : ".thrbv.full.lcp.ms"), ldx_path = a.filename + ".ldx", txt_path = a.filename + ".txt";
-    const bool have_txt = access(txt_path.c_str(), R_OK) == 0;          // optional: without it the text is rebuilt from the BWT on the GPU
     std::vector<moni_index_t*> idx(a.gpus, nullptr);
     std::vector<moni_ctx_t*> ctx(a.gpus, nullptr);
     for (int g = 0; g < a.gpus; ++g) {
-        if (have_mfi) { if (moni_index_load(idx_path.c_str(), g, &idx[g])) die("cannot load " + idx_path + " on GPU " + std::to_string(g) + " (moni-hip has no CPU path)"); }
-        else if (moni_index_load_reference(ms_path.c_str(), ldx_path.c_str(), have_txt ? txt_path.c_str() : nullptr, g, &idx[g]))
-            die("cannot load " + idx_path + " nor " + ms_path + " + " + ldx_path + " (reader of the reference's files: layout unverified against a real `moni build` output) on GPU " + std::to_string(g) + " (moni-hip has no CPU path)");
+        idx[g] = load_index(a, g);
         if (moni_ctx_create(idx[g], &ctx[g])) die("cannot create a context on GPU " + std::to_string(g));
     }
     if (r1.bz) r1.bz->start(idx[0], a.inflate_blocks);
     if (r2.bz) r2.bz->start(idx[0], a.inflate_blocks);
     const auto t0 = std::chrono::steady_clock::now();
-    FILE* out = fopen(sam_filename.c_str(), "w");
-    if (!out) die("open() file " + sam_filename + " failed");
-    // --bgzf: every piece of text goes through moni_bgzf_compress on the context that made it, and its blocks take the text's place; --bam: through moni_bam_records
-    auto put_text = [&](moni_ctx_t* C, const char* p, uint64_t n) {
-        if (a.blocks()) { const char* z; uint64_t zl; if (a.bam) bam_blocks(C, p, n, &z, &zl); else bgzf_blocks(C, p, n, false, &z, &zl); put(z, zl, out); } else put(p, n, out);
-    };
-    std::string header_text;          // --bam: for the workers' contexts, which are made below
-    {
-        char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
-        if (a.bam) { const char* z; uint64_t zl; header_text = sorted_header(h, hl, a.sort); bam_header_blocks(ctx, header_text.data(), header_text.size(), &z, &zl); put(z, zl, out); } else put_text(ctx[0], h, hl);
-        moni_free(h);
-    }
-    SortedBam sorted;          // --sort: the learning batches are run 0, the workers' batches follow
-    if (a.sort) { sorted.mark = a.mark_dup; sorted.paired = 1; sorted.open(sam_filename, a.sort_chunk, header_text); }
-    // -c: <sam>.csv, one line per pair (aligner_ksw2.hpp:911-914; header of aligner::to_csv, :3230-3234); the blocks of the batches are kept and written in input order at the end
-    FILE* out2 = nullptr;
-    std::map<size_t, std::string> csv_blocks;
-    std::mutex mu_csv;
-    std::string csv_first;
+    Sink sink;          // --sort: the learning batches are run 0, the workers' batches follow
+    sink.open(sam_filename, a, true);
+    sink.begin(idx[0], ctx);
+    // -c: <sam>.csv, one line per pair (aligner_ksw2.hpp:911-914; header of aligner::to_csv, :3230-3234); the lines of a batch are placed behind those of the batches before it, as its records are
+    Placer csv;
     if (a.csv) {
-        out2 = fopen((sam_filename + ".csv").c_str(), "w");
-        if (!out2) die("open() file " + sam_filename + ".csv failed");
+        csv.open(sam_filename + ".csv");
         static const char hdr[] = "Read,Unique,Total,Max_Freq,Min_Freq,Highest_Occ,Lowest_Occ,Filtered,Chains_Skipped\n";
-        put(hdr, sizeof hdr - 1, out2);
+        csv.append(hdr, sizeof hdr - 1);
     }
     moni_pe_model_t model;
     memset(&model, 0, sizeof model);
     size_t processed = 0, aligned = 0;
-    auto align_one = [&](int g, Batch& b, char** sam, uint64_t* len, uint64_t* n_al) {
-        moni_read_batch_t rb{b.seq.data(), b.off.data(), b.n()};
-        moni_align_stats_t st;
-        if (a.report_mems) {           // -m: the MEM records instead of the pair's (the fragment model plays no part in them)
-            const int rm = moni_pe_report_mems_batch(ctx[g], &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &a.PE, sam, len);
-            if (rm) die("moni_pe_report_mems_batch failed (" + std::to_string(rm) + ")");
-            *n_al = 0;
-            return;
-        }
-        if (a.csv) {
-            char* cs = nullptr; uint64_t cl = 0;
-            const int rc = moni_pe_align_csv_batch(ctx[g], &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &a.PE, &model, sam, len, &cs, &cl, &st);
-            if (rc) die("moni_pe_align_csv_batch failed (" + std::to_string(rc) + ")");
-            csv_first.assign(cs, cl); moni_free(cs);
-            *n_al = st.aligned;
-            return;
-        }
-        const int rc = moni_pe_align_batch(ctx[g], &rb, b.names.data(), b.name_off.data(), b.has_qual ? b.qual.data() : nullptr, &a.P, &a.PE, &model, sam, len, &st);
-        if (rc) die("moni_pe_align_batch failed (" + std::to_string(rc) + (rc == MONI_ERANGE ? ": a pair exceeds the paired path's capacities)" : ")"));
-        *n_al = st.aligned;
-    };
     std::vector<Batch*> learnt;
     while (!model.complete && !a.report_mems) {
         Batch* b = new Batch();
@@ -1067,12 +1146,13 @@ static int run_paired(Args& a, const std::string& sam_filename) {
             delete b;
         }
         if (all.n()) {
-            char* sam = nullptr; uint64_t len = 0, n_al = 0;
-            align_one(0, all, &sam, &len, &n_al);
-            if (a.sort) sorted.add_run(ctx[0], 0, sam, len); else put_text(ctx[0], sam, len);
-            moni_free(sam);
-            if (out2) put(csv_first.data(), csv_first.size(), out2);
-            processed += all.n() / 2; aligned += n_al;
+            const PairOut o = pe_call(ctx[0], all, a, model, false);
+            const Block z = sink.encode(ctx[0], 0, o.sam, o.len);
+            sink.append(z.p, z.n);
+            moni_free(o.sam);
+            if (a.csv) csv.append(o.csv, o.csv_len);
+            moni_free(o.csv);
+            processed += all.n() / 2; aligned += o.aligned;
         }
     }
     // ---- the rest: reader thread (the two files parsed side by side) -> bounded queue -> a few workers per GPU, each with its own context (one's upload and
@@ -1084,21 +1164,16 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         if (k == 0) wctx[(size_t)g * per_gpu] = ctx[g];
         else if (moni_ctx_create(idx[g], &wctx[(size_t)g * per_gpu + k])) die("cannot create a context on GPU " + std::to_string(g));
     }
-    if (a.bam) { const uint8_t* bh; uint64_t bhl; bam_set_headers(wctx, header_text.data(), header_text.size(), &bh, &bhl); }          // the dictionary alone: the header is in the file
-    if (fflush(out) != 0) die("short write to the output file");
-    const uint64_t off0 = (uint64_t)ftello(out);
-    const int fd = fileno(out);
+    sink.set_dictionary(wctx);          // the dictionary alone: the header is in the file
     // a batch for the workers: the slow reader's Batch, or the fast reader's PairBatch (both mate files mapped four-line FASTQ)
     struct Item { size_t id; Batch* b; fastpath::PairBatch* f; };
     const bool fast_reader = r1.fastq_view() && r2.fastq_view() && getenv("MONI_CLI_SLOW_READER") == nullptr;
     const bool chunked = r1.bz || r2.bz;          // a view is a chunk of inflated text, not the whole file: a batch ends where a chunk does
-    std::mutex mu_q, mu_o;
-    std::condition_variable cv_put, cv_get, cv_o;
+    std::mutex mu_q;
+    std::condition_variable cv_put, cv_get;
     std::deque<Item> queue;
     bool reader_done = false;
     const size_t q_cap = wctx.size() + 1;
-    std::map<size_t, uint64_t> lens, starts;
-    size_t upto = 0; uint64_t off_upto = off0;
     std::atomic<size_t> n_proc{0}, n_al_all{0};
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_read = 0; std::vector<double> t_lib(wctx.size(), 0), t_wait(wctx.size(), 0), t_write(wctx.size(), 0);
@@ -1146,57 +1221,22 @@ static int run_paired(Args& a, const std::string& sam_filename) {
                 it = queue.front(); queue.pop_front();
                 cv_put.notify_one();
             }
-            const uint8_t* v_seq = it.f ? it.f->seq.p : it.b->seq.data(); const uint64_t* v_off = it.f ? it.f->off.data() : it.b->off.data();
-            const uint8_t* v_names = it.f ? it.f->names.p : it.b->names.data(); const uint64_t* v_noff = it.f ? it.f->name_off.data() : it.b->name_off.data();
-            const uint8_t* v_qual = it.f ? it.f->qual.p : (it.b->has_qual ? it.b->qual.data() : nullptr);
-            const size_t v_n = it.f ? it.f->n_reads : it.b->n();
-            moni_read_batch_t rb{v_seq, v_off, v_n};
-            char* sam = nullptr; uint64_t len = 0; size_t n_al = 0;
+            const PairView v = it.f ? PairView(*it.f) : PairView(*it.b);
             const double x1 = now();
-            if (a.report_mems) {
-                const int rm = moni_pe_report_mems_batch(C, &rb, v_names, v_noff, v_qual, &a.P, &a.PE, &sam, &len);
-                if (rm) die("moni_pe_report_mems_batch failed (" + std::to_string(rm) + ")");
-            } else if (a.csv) {
-                moni_align_stats_t st;
-                char* cs = nullptr; uint64_t cl = 0;
-                const int rc = moni_pe_align_csv_batch(C, &rb, v_names, v_noff, v_qual, &a.P, &a.PE, &model, &sam, &len, &cs, &cl, &st);
-                if (rc) die("moni_pe_align_csv_batch failed (" + std::to_string(rc) + ")");
-                { std::lock_guard<std::mutex> lk(mu_csv); csv_blocks[it.id].assign(cs, cl); }
-                moni_free(cs);
-                n_al = st.aligned;
-            } else {          // the text in the context's pinned buffer: written out before the context's next call
-                moni_align_stats_t st;
-                const int rc = moni_pe_align_stream(C, &rb, v_names, v_noff, v_qual, &a.P, &a.PE, &model, &sam, &len, &st);
-                if (rc) die("moni_pe_align_stream failed (" + std::to_string(rc) + (rc == MONI_ERANGE ? ": a pair exceeds the paired path's capacities)" : ")"));
-                n_al = st.aligned;
-            }
-            char* const lib_sam = sam;          // (what moni_free takes back in the -m path)
-            if (a.sort) { sorted.add_run(C, it.id + 1, sam, len); len = 0; }          // nothing goes to the output before the merge
-            else if (a.blocks()) { const char* z; uint64_t zl; if (a.bam) bam_blocks(C, sam, len, &z, &zl); else bgzf_blocks(C, sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
-            uint64_t at = 0;
+            const PairOut o = pe_call(C, v, a, model, true);          // the text in the context's pinned buffer (-m, -c: malloc'ed): written out before the context's next call
+            const Block z = sink.encode(C, it.id + 1, o.sam, o.len);
             const double x2 = now();
-            {
-                std::unique_lock<std::mutex> lk(mu_o);
-                lens[it.id] = len;
-                while (lens.count(upto)) { starts[upto] = off_upto; off_upto += lens[upto]; lens.erase(upto); ++upto; }
-                cv_o.notify_all();
-                cv_o.wait(lk, [&] { return upto > it.id; });
-                at = starts[it.id]; starts.erase(it.id);
-            }
+            const uint64_t at = sink.place(it.id, z.n);
             const double x3 = now();
-            if (len) {
-                std::vector<std::thread> th;
-                const size_t sl = (len + P - 1) / P;
-                for (int i = 1; i < P; ++i) { const size_t lo = std::min<size_t>(len, sl * i), hi = std::min<size_t>(len, sl * (i + 1)); if (hi > lo) th.emplace_back(fastpath::pwrite_all, fd, sam + lo, hi - lo, at + lo); }
-                fastpath::pwrite_all(fd, sam, std::min<size_t>(len, sl), at);
-                for (auto& t : th) t.join();
-            }
+            sink.write(z.p, z.n, at, P);
             const double x4 = now();
             t_lib[w] += x2 - x1; t_wait[w] += x3 - x2; t_write[w] += x4 - x3;
-            if (verbose_batches) fprintf(stderr, "batch %zu (worker %d, %zu pairs): library %.0f ms, wait %.0f ms, write %.0f ms, done at %.3f s\n", it.id, w, v_n / 2, (x2 - x1) * 1e3, (x3 - x2) * 1e3, (x4 - x3) * 1e3,
+            if (verbose_batches) fprintf(stderr, "batch %zu (worker %d, %zu pairs): library %.0f ms, wait %.0f ms, write %.0f ms, done at %.3f s\n", it.id, w, v.n / 2, (x2 - x1) * 1e3, (x3 - x2) * 1e3, (x4 - x3) * 1e3,
                                         std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-            if (a.report_mems || a.csv) moni_free(lib_sam);
-            n_proc += v_n / 2; n_al_all += n_al;
+            if (a.csv) csv.write(o.csv, o.csv_len, csv.place(it.id, o.csv_len), 1);
+            if (o.owned) moni_free(o.sam);
+            moni_free(o.csv);
+            n_proc += v.n / 2; n_al_all += o.aligned;
             delete it.b; delete it.f;
         }
     };
@@ -1206,7 +1246,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         for (auto& t : th) t.join();
     }
     reader.join();
-    if (out2) { for (auto& kv : csv_blocks) put(kv.second.data(), kv.second.size(), out2); if (fclose(out2) != 0) die("short write to the csv file"); }
+    if (a.csv) csv.close("short write to the csv file");
     processed += n_proc.load(); aligned += n_al_all.load();
     {
         double sl = 0, sw = 0, sr = 0;
@@ -1216,11 +1256,8 @@ static int run_paired(Args& a, const std::string& sam_filename) {
     }
     if (r1.bz) r1.bz->finish();
     if (r2.bz) r2.bz->finish();
-    if (a.sort) off_upto = sorted.finish(wctx, fd, off_upto);
-    if (fseeko(out, (off_t)off_upto, SEEK_SET) != 0) die("seek in the output file failed");
-    if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
+    sink.finish(wctx);
     for (int g = 0; g < a.gpus; ++g) for (int k = 1; k < per_gpu; ++k) moni_ctx_destroy(wctx[(size_t)g * per_gpu + k]);
-    close_out(out);
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     info("Number of aligned pairs: " + std::to_string(aligned) + "/" + std::to_string(processed));
     info("Elapsed time (s): " + std::to_string(el));
@@ -1511,6 +1548,32 @@ static bool mode_alone(const Args& a, unsigned id, bool paired) {
     return true;
 }
 
+// The output flags in the order that decides which message a wrong combination gets.  A set flag wants `needs` beside it, then refuses its `extras` in their
+// order, then - where it is a form of the SAM output (`sam`) - every mode that writes files of its own, in the table's order; `after` has the last word.
+struct Beside { bool Args::*set; const char* flag; };
+struct OutputFlag { Beside self, needs; Beside extras[3]; bool sam; void (*after)(const Args&); };
+static const Beside B_BGZF = {&Args::bgzf, "--bgzf"}, B_C = {&Args::csv, "-c"}, B_DRY_WRITE = {&Args::dry_write, "--dry-run-write"};
+static const OutputFlag OUTPUT_FLAGS[] = {
+    {{&Args::bgzf, "--bgzf"}, {}, {B_C, B_DRY_WRITE}, true, nullptr},
+    {{&Args::sort, "--sort"}, {&Args::bam, "--bam"}, {B_BGZF, B_C, B_DRY_WRITE}, true, [](const Args& a) {
+        if (a.sort ? a.sort_chunk < 65536 : a.sort_chunk_set) die(a.sort ? "--sort-chunk takes at least 65536 bytes" : "--sort-chunk belongs to --sort");
+    }},
+    // duplicate marking: a decision over the whole input, so it lives between the two phases of the sort; one record per read
+    {{&Args::mark_dup, "--mark-dup"}, {&Args::sort, "--sort"}, {{&Args::extend, "--extend"}, {&Args::report_mems, "-m"}}, false, nullptr},
+    {{&Args::bam, "--bam"}, {}, {B_BGZF, B_C, B_DRY_WRITE}, true, nullptr},          // one container
+};
+static void check_output_flags(const Args& a) {
+    for (const OutputFlag& f : OUTPUT_FLAGS) {
+        if (a.*f.self.set) {
+            const std::string clash = std::string(f.self.flag) + " cannot be combined with ";
+            if (f.needs.set && !(a.*f.needs.set)) die(std::string(f.self.flag) + " belongs to " + f.needs.flag);
+            for (const Beside& e : f.extras) if (e.set && a.*e.set) die(clash + e.flag);
+            for (const Mode& m : MODES) if (f.sam && m.suffix && a.*m.set) die(clash + m.flag);
+        }
+        if (f.after) f.after(a);
+    }
+}
+
 int main(int argc, char** argv) {
     // HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues; every context runs its launches on several streams (the paired
     // path on ~11), and streams that share a queue run one after the other
@@ -1545,51 +1608,7 @@ int main(int argc, char** argv) {
         if (a.max_occ && !a.max_hits) die("--approx: --max-occ needs --max-hits above 0");
     } else if (a.max_hits_set || a.max_steps_set) die("--max-hits / --max-steps belong to --approx");
     mode_alone(a, O_EXTEND, paired);
-    if (a.bgzf) {            // BGZF output: the modes that write SAM
-        if (a.csv) die("--bgzf cannot be combined with -c");
-        if (a.dry_write) die("--bgzf cannot be combined with --dry-run-write");
-        if (a.legacy_ms) die("--bgzf cannot be combined with --ms");
-        if (a.legacy_mems) die("--bgzf cannot be combined with --mems");
-        if (a.pseudo_ms) die("--bgzf cannot be combined with --pseudo-ms");
-        if (a.screen) die("--bgzf cannot be combined with --screen");
-        if (a.locate) die("--bgzf cannot be combined with --locate");
-        if (a.seq_count) die("--bgzf cannot be combined with --seq-count");
-        if (a.loci) die("--bgzf cannot be combined with --loci");
-        if (a.approx) die("--bgzf cannot be combined with --approx");
-    }
-    if (a.sort) {            // sorted BAM: what --bam takes, and --bam itself
-        if (!a.bam) die("--sort belongs to --bam");
-        if (a.bgzf) die("--sort cannot be combined with --bgzf");
-        if (a.csv) die("--sort cannot be combined with -c");
-        if (a.dry_write) die("--sort cannot be combined with --dry-run-write");
-        if (a.legacy_ms) die("--sort cannot be combined with --ms");
-        if (a.legacy_mems) die("--sort cannot be combined with --mems");
-        if (a.pseudo_ms) die("--sort cannot be combined with --pseudo-ms");
-        if (a.screen) die("--sort cannot be combined with --screen");
-        if (a.locate) die("--sort cannot be combined with --locate");
-        if (a.seq_count) die("--sort cannot be combined with --seq-count");
-        if (a.loci) die("--sort cannot be combined with --loci");
-        if (a.approx) die("--sort cannot be combined with --approx");
-        if (a.sort_chunk < 65536) die("--sort-chunk takes at least 65536 bytes");
-    } else if (a.sort_chunk_set) die("--sort-chunk belongs to --sort");
-    if (a.mark_dup) {        // duplicate marking: a decision over the whole input, so it lives between the two phases of the sort; one record per read
-        if (!a.sort) die("--mark-dup belongs to --sort");
-        if (a.extend) die("--mark-dup cannot be combined with --extend");
-        if (a.report_mems) die("--mark-dup cannot be combined with -m");
-    }
-    if (a.bam) {             // BAM output: the modes that write SAM, and one container
-        if (a.bgzf) die("--bam cannot be combined with --bgzf");
-        if (a.csv) die("--bam cannot be combined with -c");
-        if (a.dry_write) die("--bam cannot be combined with --dry-run-write");
-        if (a.legacy_ms) die("--bam cannot be combined with --ms");
-        if (a.legacy_mems) die("--bam cannot be combined with --mems");
-        if (a.pseudo_ms) die("--bam cannot be combined with --pseudo-ms");
-        if (a.screen) die("--bam cannot be combined with --screen");
-        if (a.locate) die("--bam cannot be combined with --locate");
-        if (a.seq_count) die("--bam cannot be combined with --seq-count");
-        if (a.loci) die("--bam cannot be combined with --loci");
-        if (a.approx) die("--bam cannot be combined with --approx");
-    }
+    check_output_flags(a);
     if (!paired && a.patterns.empty()) die("no reads given (-p)");
     std::string fn = a.filename;
     std::vector<char> tmp(fn.begin(), fn.end()); tmp.push_back(0);
@@ -1625,23 +1644,18 @@ int main(int argc, char** argv) {
         }
         printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%.*s%s%s%s\n", n, bases, a.P.min_len,
                a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(),
-               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), a.bgzf ? " bgzf=1" : a.bam ? (a.sort ? (a.mark_dup ? " bam=1 sort=1 markdup=1" : " bam=1 sort=1") : " bam=1") : "", bz ? " input=bgzf" : "");
+               n ? (int)b.name_off[1] : 0, n ? (const char*)b.names.data() : "", mode.c_str(), output_word(a), bz ? " input=bgzf" : "");
         if (!a.dry_write || !mapped) return 0;
     }
-    const std::string idx_path = a.filename + ".mfi";
     const bool fast = (mapped || bz) && !M && getenv("MONI_CLI_QUEUE_PATH") == nullptr;
     const int per_gpu = legacy ? 1 : (fast ? a.ctx_per_gpu : 2);                      // contexts (batches in flight) per GPU
     std::vector<moni_index_t*> idx(a.gpus, nullptr);
     std::vector<moni_ctx_t*> ctx((size_t)a.gpus * per_gpu, nullptr);
-    const bool have_mfi = !a.no_lcp && access(idx_path.c_str(), R_OK) == 0;          // (the flat file always carries the LCP samples)
-    const std::string ms_path = a.filename + (a.no_lcp ? ".thrbv.full.ms" : ".thrbv.full.lcp.ms"), ldx_path = a.filename + ".ldx", txt_path = a.filename + ".txt";
-    const bool have_txt = access(txt_path.c_str(), R_OK) == 0;          // optional: without it the text is rebuilt from the BWT on the GPU
     for (int g = 0; g < a.gpus && !a.dry_write; ++g) {
-        if (have_mfi) { if (moni_index_load(idx_path.c_str(), g, &idx[g])) die("cannot load " + idx_path + " on GPU " + std::to_string(g) + " (moni-hip has no CPU path)"); }
-        else if (moni_index_load_reference(ms_path.c_str(), ldx_path.c_str(), have_txt ? txt_path.c_str() : nullptr, g, &idx[g]))
-            die("cannot load " + idx_path + " nor " + ms_path + " + " + ldx_path + " (reader of the reference's files: layout unverified against a real `moni build` output) on GPU " + std::to_string(g) + " (moni-hip has no CPU path)");
+        idx[g] = load_index(a, g);
         for (int k = 0; k < per_gpu; ++k) if (moni_ctx_create(idx[g], &ctx[(size_t)g * per_gpu + k])) die("cannot create a context on GPU " + std::to_string(g));
     }
+    Sink sink;          // the output of the modes that write SAM; --sort: a range or batch is a run
     if (fast) {
         using namespace fastpath;
         const auto t0 = std::chrono::steady_clock::now();
@@ -1655,22 +1669,8 @@ int main(int argc, char** argv) {
         if (bz) bzin.start(idx[0], a.inflate_blocks);
         while (!bz && cuts.back() < end) { const char* nx = (size_t)(end - cuts.back()) <= chunk_bytes + chunk_bytes / 4 ? end : align_record(cuts.back() + chunk_bytes, base, end, fq); if (nx <= cuts.back()) nx = end; cuts.push_back(nx); }
         const size_t n_chunks = bz ? bzin.n_chunks() : cuts.size() - 1;
-        const int fd = ::open(sam_filename.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (fd < 0) die("open() file " + sam_filename + " failed");
-        SortedBam sorted;          // --sort: a range is a run
-        uint64_t hdr_len = 0;
-        if (!a.dry_write) {
-            char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
-            const char* hz = h; uint64_t hzl = hl;
-            if (a.bgzf) bgzf_blocks(ctx[0], h, hl, false, &hz, &hzl);          // the header as blocks of its own, before the workers take the contexts
-            const std::string bh = sorted_header(h, hl, a.sort);
-            if (a.bam) bam_header_blocks(ctx, bh.data(), bh.size(), &hz, &hzl);               // ... as a BAM header, and every context learns its dictionary
-            if (a.sort) { sorted.mark = a.mark_dup; sorted.open(sam_filename, a.sort_chunk, bh); }
-            pwrite_all(fd, hz, hzl, 0); hdr_len = hzl; moni_free(h);
-        }
-        std::mutex mu; std::condition_variable cv;
-        std::vector<uint64_t> lens(n_chunks, ~0ull), starts(n_chunks, 0);
-        size_t upto = 0; uint64_t off_upto = hdr_len;
+        sink.open(sam_filename, a, false);
+        if (!a.dry_write) sink.begin(idx[0], ctx);
         std::atomic<size_t> next_chunk{0};
         std::atomic<size_t> processed{0}, aligned{0};
         const int P = (int)std::max<size_t>(1, std::min<size_t>(8, a.th / std::max<size_t>(1, ctx.size() / (size_t)a.gpus)));      // helper threads of one worker
@@ -1694,7 +1694,7 @@ int main(int argc, char** argv) {
                     parse_range(cuts[id], cuts[id + 1], base, end, fq, P, B);
                 }
                 double x1 = now(); t_parse[w] += x1 - x0;
-                char* sam = nullptr; uint64_t len = 0;
+                Block z{nullptr, 0};          // the range's bytes for the file
                 moni_align_stats_t st; memset(&st, 0, sizeof st);
                 std::string placeholder;
                 if (a.dry_write) {          // one unaligned record per read (what the library returns for a read without seeds), worker id in a tag
@@ -1706,33 +1706,18 @@ int main(int argc, char** argv) {
                         if (fq) placeholder.append((const char*)B.qual.p + B.off[r], (size_t)(B.off[r + 1] - B.off[r])); else placeholder += "*";
                         placeholder += "\tXW:i:" + std::to_string(w) + "\n";
                     }
-                    sam = placeholder.data(); len = placeholder.size();
+                    z = {placeholder.data(), placeholder.size()};
                     std::this_thread::sleep_for(std::chrono::milliseconds(3));          // (a library call takes longer than that: the other workers get their ranges)
                 } else if (B.n) {
                     moni_read_batch_t rb{B.seq.p, B.off.data(), (uint64_t)B.n};
+                    char* sam = nullptr; uint64_t len = 0;
                     if (moni_align_stream(ctx[w], &rb, B.names.p, B.name_off.data(), fq ? B.qual.p : nullptr, &a.P, &sam, &len, &st)) die("moni_align_stream failed");
-                    // --bgzf: the range's text from the context's pinned buffer through the same context; its blocks take the text's place below
-                    if (a.sort) { sorted.add_run(ctx[w], id, sam, len); len = 0; }          // nothing goes to the output before the merge
-                    else if (a.blocks()) { const char* z; uint64_t zl; if (a.bam) bam_blocks(ctx[w], sam, len, &z, &zl); else bgzf_blocks(ctx[w], sam, len, false, &z, &zl); sam = const_cast<char*>(z); len = zl; }
+                    z = sink.encode(ctx[w], id, sam, len);          // the text in the context's pinned buffer, and so are its blocks
                 }
                 double x2 = now(); t_lib[w] += x2 - x1;
-                uint64_t at;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    lens[id] = len;
-                    while (upto < n_chunks && lens[upto] != ~0ull) { starts[upto] = off_upto; off_upto += lens[upto]; ++upto; }
-                    cv.notify_all();
-                    cv.wait(lk, [&] { return upto > id; });
-                    at = starts[id];
-                }
+                const uint64_t at = sink.place(id, z.n);
                 double x3 = now(); t_wait[w] += x3 - x2;
-                if (len) {
-                    std::vector<std::thread> th;
-                    const size_t sl = (len + P - 1) / P;
-                    for (int i = 1; i < P; ++i) { const size_t lo = std::min<size_t>(len, sl * i), hi = std::min<size_t>(len, sl * (i + 1)); if (hi > lo) th.emplace_back(pwrite_all, fd, sam + lo, hi - lo, at + lo); }
-                    pwrite_all(fd, sam, std::min<size_t>(len, sl), at);
-                    for (auto& t : th) t.join();
-                }
+                sink.write(z.p, z.n, at, P);
                 const double x4 = now();
                 t_write[w] += x4 - x3;
                 if (verbose_ranges) fprintf(stderr, "range %zu (worker %d, %zu reads): parse %.0f ms, library %.0f ms (seed %.0f, align kernels %.0f), wait %.0f ms, write %.0f ms, done at %.3f s\n", id, w, B.n,
@@ -1745,9 +1730,7 @@ int main(int argc, char** argv) {
         for (size_t w = 0; w < ctx.size(); ++w) th.emplace_back(worker, (int)w);
         for (auto& t : th) t.join();
         if (bz) bzin.finish();
-        if (a.sort) off_upto = sorted.finish(ctx, fd, off_upto);
-        if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); pwrite_all(fd, z, zl, off_upto); }          // the end-of-file block
-        if (::close(fd) != 0) die("close() of the output file failed");
+        sink.finish(ctx);
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         info("Number of aligned reads: " + std::to_string(aligned.load()) + "/" + std::to_string(processed.load()));
         info("Elapsed time (s): " + std::to_string(el));
@@ -1761,19 +1744,15 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (a.dry_write) return 0;
-    FILE* out = nullptr; FILE* out2 = nullptr;
-    SortedBam sorted;          // --sort: a batch is a run
+    FILE* out = nullptr; FILE* out2 = nullptr;          // the files of a pattern mode; out2 also <sam>.csv
+    const bool sam_out = !(M && M->suffix);
     if (M && M->suffix) {
         out = fopen((sam_filename + M->suffix).c_str(), "w");
         if (M->suffix2) out2 = fopen((sam_filename + M->suffix2).c_str(), "w");
         if (!out || (M->suffix2 && !out2)) die("open() file " + sam_filename + M->suffix + (M->suffix2 ? std::string("/") + M->suffix2 : "") + " failed");
     } else {
-        out = fopen(sam_filename.c_str(), "w");
-        if (!out) die("open() file " + sam_filename + " failed");
-        char* h; uint64_t hl; if (moni_sam_header(idx[0], &h, &hl)) die("header");
-        if (a.bam) { const char* z; uint64_t zl; const std::string bh = sorted_header(h, hl, a.sort); bam_header_blocks(ctx, bh.data(), bh.size(), &z, &zl); put(z, zl, out); if (a.sort) { sorted.mark = a.mark_dup; sorted.open(sam_filename, a.sort_chunk, bh); } }
-        else if (a.bgzf) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], h, hl, false, &z, &zl); put(z, zl, out); } else put(h, hl, out);
-        moni_free(h);
+        sink.open(sam_filename, a, false);
+        sink.begin(idx[0], ctx);
         if (a.csv) {          // -c: <sam>.csv (align_reads_dispatcher.hpp:302,334-339), header of aligner::to_csv (aligner_ksw2.hpp:3230-3234)
             out2 = fopen((sam_filename + ".csv").c_str(), "w");
             if (!out2) die("open() file " + sam_filename + ".csv failed");
@@ -1845,7 +1824,7 @@ int main(int argc, char** argv) {
                 cv_window.notify_all();
             }
             const double w0 = now();
-            if (d.la) put(d.a, d.la, out);
+            if (sam_out) sink.append(d.a, d.la); else put(d.a, d.la, out);
             if (d.a) moni_free(d.a);
             if (out2 && !d.b.empty()) put(d.b.data(), d.b.size(), out2);
             t_writer += now() - w0;
@@ -1867,13 +1846,13 @@ int main(int argc, char** argv) {
             Done d;
             const double a0 = now();
             const size_t n_al = (M ? M->run : run_align)(C, b, rb, it.first, a, seq_names, d);
-            if (a.sort) { sorted.add_run(C, it.id, d.a, d.la); moni_free(d.a); d.a = nullptr; d.la = 0; }          // nothing goes to the output before the merge
-            else if (a.blocks()) {          // the batch's text through this worker's context; a copy of the blocks waits for the writer (the pinned buffer is the context's next call's)
-                const char* z; uint64_t zl;
-                if (a.bam) bam_blocks(C, d.a, d.la, &z, &zl); else bgzf_blocks(C, d.a, d.la, false, &z, &zl);
-                moni_free(d.a);
-                d.a = (char*)malloc(zl + 1); if (!d.a) die("out of memory");
-                memcpy(d.a, z, zl); d.la = zl;
+            if (sam_out) {
+                const Block z = sink.encode(C, it.id, d.a, d.la);
+                if (z.p != d.a) {          // blocks in this worker's context's pinned buffer, which is the context's next call's: a copy of them waits for the writer
+                    moni_free(d.a);
+                    d.a = nullptr; d.la = z.n;
+                    if (z.n) { d.a = (char*)malloc(z.n); if (!d.a) die("out of memory"); memcpy(d.a, z.p, z.n); }
+                }
             }
             const size_t n_reads = b.n();
             delete it.b;
@@ -1892,12 +1871,7 @@ int main(int argc, char** argv) {
     for (auto& t : th) t.join();
     { std::lock_guard<std::mutex> lk(mu_out); workers_done = true; cv_out.notify_all(); }
     writer.join();
-    if (a.sort) {
-        if (fflush(out) != 0) die("short write to the output file");
-        const uint64_t end = sorted.finish(ctx, fileno(out), (uint64_t)ftello(out));
-        if (fseeko(out, (off_t)end, SEEK_SET) != 0) die("seek in the output file failed");
-    }
-    if (a.blocks()) { const char* z; uint64_t zl; bgzf_blocks(ctx[0], nullptr, 0, true, &z, &zl); put(z, zl, out); }          // the end-of-file block
+    if (sam_out) sink.finish(ctx);
     close_out(out);
     close_out(out2);
     delete zrd;
