@@ -748,6 +748,49 @@ int  moni_bgzf_scan(const void *data, uint64_t len, uint64_t *n_blocks, uint64_t
 int  moni_bgzf_inflate(moni_ctx_t *ctx, const void *blocks, uint64_t len, const moni_inflate_params_t *prm,
                        const uint8_t **out, uint64_t *out_len, moni_inflate_stats_t *stats);
 
+/* ---- BAM input: the reads of unaligned or aligned BAM as FASTQ text, made on the GPU ---- */
+/* A BAM file is BGZF members whose text is the header (`BAM\1`, l_text, the text, n_ref, the references) and then records, each behind
+ * its own block_size, aligned to nothing.  A context holds one stream: the header's state and the bytes that no call has used yet (the
+ * carry: a header, a record or a pair that is not whole).  moni_bam_in_feed inflates the members it is given behind the carry, finds
+ * every record start on the device, and writes the primary records that have bases as four-line FASTQ: @name, the bases (= as N), +,
+ * the qualities + 33 (`"` for every base where they are absent: a first byte of 0xFF).  A record with 0x10 is given as sequenced: the
+ * bases reversed and complemented, the qualities reversed.  CIGAR and tags are dropped.  Records with 0x100 or 0x800 and records
+ * without bases are skipped and counted.  paired: the records kept come as a first mate (0x1 | 0x40) followed by its second
+ * (0x1 | 0x80) under the same name - what unaligned BAM and `samtools collate` give; the first mates go to text1, the second to text2. */
+typedef struct { uint32_t paired;             /* default 0 */
+                 uint32_t check_crc;          /* verify CRC-32 of every member; default 1 */
+                 uint32_t reserved[2]; } moni_bamin_params_t;
+typedef struct { moni_inflate_stats_t inflate;          /* of the members of this call, as moni_bgzf_inflate gives them (its bad_blocks, first_bad_block, bad_reason) */
+                 uint64_t records, reads;               /* records seen by this call (those carried on are not); reads written (paired: both mates) */
+                 uint64_t skipped_secondary, skipped_empty;
+                 uint64_t carried_bytes;                /* of the stream, left for the next call */
+                 uint64_t bad_records;                  /* 1 where a record (or the header) was refused: what lies behind it is not looked at */
+                 uint64_t first_bad_record;             /* its index among the records since the last reset, the lowest */
+                 uint32_t bad_record_reason, header_done;
+                 double t_kernel[4];                    /* HIP-event seconds: inflation; sweep, chain and list; selection and scans; text */
+                 double t_total; } moni_bamin_stats_t;
+enum { MONI_BAMIN_OK = 0,
+       MONI_BAMIN_MAGIC,       /* the stream does not start with BAM\1 */
+       MONI_BAMIN_HEADER,      /* a negative l_text or n_ref, a reference name of length 0 or less */
+       MONI_BAMIN_BLOCK_SIZE,  /* outside [32, 2^28] */
+       MONI_BAMIN_FIELDS,      /* l_read_name 0, a name that does not end in NUL, a negative l_seq, fields that do not fit block_size */
+       MONI_BAMIN_PAIRING,     /* paired: a kept record without 0x1, not the mate (0x40 / 0x80) its turn asks for, or a second mate under another name */
+       MONI_BAMIN_TRUNCATED }; /* last was set and bytes are left over: a header or a record that is not whole, a lone first mate */
+void moni_bamin_params_default(moni_bamin_params_t *p);
+/* Forgets the header's state, the carry and the record count: the next feed starts a file. */
+int  moni_bam_in_reset(moni_ctx_t *ctx);
+/* blocks: len bytes of host memory, whole BGZF members only (as for moni_bgzf_inflate); last: nothing follows.  *text1 / *len1 (and,
+ * paired, *text2 / *len2 - else NULL and 0) point into pinned buffers of the context that belong to this call alone: valid until the
+ * next moni_bam_in_feed, moni_bam_in_reset or moni_ctx_destroy on this context.  *n_reads: records in text1 (paired: pairs).  A header
+ * may span any number of calls.  len 0 with last 0 launches nothing.  What the other calls of the context hold - the resident batch,
+ * moni_last_kernel_ms, moni_last_counters, pending *_fetch results, the pointers moni_bgzf_compress, moni_bam_records, moni_bgzf_inflate
+ * and the sort calls returned - stays as it is.  stats may be NULL.
+ * MONI_EINVAL: a NULL argument but stats (blocks may be NULL with len 0); paired, check_crc or last above 1, a non-zero reserved; a bad
+ * member (stats->inflate says which); a bad record (stats->first_bad_record, bad_record_reason).  Then nothing is written, both lengths
+ * are 0, and the stream is left as it was before the call.  MONI_ERANGE: carry and text together reach 2^32 bytes. */
+int  moni_bam_in_feed(moni_ctx_t *ctx, const void *blocks, uint64_t len, const moni_bamin_params_t *prm, int last,
+                      const uint8_t **text1, uint64_t *len1, const uint8_t **text2, uint64_t *len2, uint64_t *n_reads, moni_bamin_stats_t *stats);
+
 /* ---- the reference's on-disk liftidx (<prefix>.ldx: include/aligner/liftidx.hpp:117-143 over include/common/seqidx.hpp:197-238) ---- */
 /* Both layouts load: the current one (u64 w after u) and the older one the reference's fixture data/Chr21.10.ldx has. */
 int moni_ldx_info(const char *path, uint64_t *n_seq, uint64_t *u, uint64_t *w, int *has_w);

@@ -43,6 +43,7 @@ EXPORTS = [
     "moni_bam_sorted_run_dup", "moni_bam_dup_resolve", "moni_bam_sort_marked",
     "moni_bai_create", "moni_bai_add", "moni_bai_finish", "moni_bai_destroy",
     "moni_inflate_params_default", "moni_bgzf_scan", "moni_bgzf_inflate",
+    "moni_bamin_params_default", "moni_bam_in_reset", "moni_bam_in_feed",
 ]
 
 
@@ -164,6 +165,18 @@ class InflateStatsC(C.Structure):
                 ("t_kernel", C.c_double), ("t_total", C.c_double)]
 
 
+class BamInParamsC(C.Structure):
+    _fields_ = [("paired", C.c_uint32), ("check_crc", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class BamInStatsC(C.Structure):
+    _fields_ = [("inflate", InflateStatsC), ("records", C.c_uint64), ("reads", C.c_uint64), ("skipped_secondary", C.c_uint64), ("skipped_empty", C.c_uint64),
+                ("carried_bytes", C.c_uint64), ("bad_records", C.c_uint64), ("first_bad_record", C.c_uint64), ("bad_record_reason", C.c_uint32),
+                ("header_done", C.c_uint32), ("t_kernel", C.c_double * 4), ("t_total", C.c_double)]
+
+
+BAMIN_REASONS = ("OK", "MAGIC", "HEADER", "BLOCK_SIZE", "FIELDS", "PAIRING", "TRUNCATED")
+BAMIN_PHASES = ("inflate", "find", "select", "text")          # moni_bamin_stats_t::t_kernel
 INF_REASONS = ("OK", "HEADER", "BTYPE", "STORED_LEN", "CODE_LENGTHS", "BAD_SYMBOL", "DISTANCE", "OVERRUN", "TRUNCATED", "TRAILING", "ISIZE", "CRC")
 
 
@@ -475,6 +488,11 @@ def lib():
         L.moni_bgzf_scan.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.moni_bgzf_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(InflateParamsC), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                         C.POINTER(InflateStatsC)]
+        L.moni_bamin_params_default.argtypes = [C.POINTER(BamInParamsC)]
+        L.moni_bamin_params_default.restype = None
+        L.moni_bam_in_reset.argtypes = [C.c_void_p]
+        L.moni_bam_in_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BamInParamsC), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(BamInStatsC)]
         _lib = L
     return _lib
 
@@ -914,6 +932,30 @@ class Ctx:
             return rc, n.value, stats
         _chk(rc, "moni_bgzf_inflate")
         return C.string_at(out.value, n.value) if n.value else b"", stats
+
+    def bam_in_reset(self):
+        """moni_bam_in_reset: the next bam_in_feed starts a file"""
+        _chk(self._L.moni_bam_in_reset(self._h), "moni_bam_in_reset")
+
+    def bam_in_feed(self, data, paired: bool = False, last: bool = False, check_crc: bool = True, rc_only: bool = False):
+        """moni_bam_in_feed: whole BGZF members of a BAM file (bytes, or a uint8 array) behind what the calls before left over.  Returns
+        (text1, text2, reads or pairs, stats: the fields of moni_bamin_stats_t with the inflater's under 'inflate' and t_kernel as a dict by
+        BAMIN_PHASES); with rc_only the return code comes first and nothing is raised."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        p = BamInParamsC()
+        self._L.moni_bamin_params_default(C.byref(p))
+        p.paired, p.check_crc = 1 if paired else 0, 1 if check_crc else 0
+        t1, t2, n1, n2, nr, st = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64(), BamInStatsC()
+        rc = self._L.moni_bam_in_feed(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(p), 1 if last else 0, C.byref(t1), C.byref(n1), C.byref(t2),
+                                      C.byref(n2), C.byref(nr), C.byref(st))
+        stats = {k: getattr(st, k) for k, _ in BamInStatsC._fields_ if k not in ("inflate", "t_kernel")}
+        stats["inflate"] = {k: getattr(st.inflate, k) for k, _ in InflateStatsC._fields_}
+        stats["t_kernel"] = dict(zip(BAMIN_PHASES, st.t_kernel))
+        out = (C.string_at(t1.value, n1.value) if n1.value else b"", C.string_at(t2.value, n2.value) if n2.value else b"", nr.value, stats)
+        if rc_only:
+            return (rc,) + out
+        _chk(rc, "moni_bam_in_feed")
+        return out
 
     def bam_set_header(self, text) -> bytes:
         """moni_bam_set_header: the dictionary of the @SQ lines of `text` (bytes or str) for this context's bam_records; returns the uncompressed

@@ -53,6 +53,7 @@
 #include "bam_dup_kernels.hip"
 #include "bam_index.hpp"
 #include "inflate_kernels.hip"
+#include "bamin_kernels.hip"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "moni_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return MONI_ENODEV; } } while (0)
 
@@ -276,6 +277,14 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
         DBuf<uint8_t> in, out; DBuf<infl_member_t> mem; DBuf<uint32_t> status; DBuf<unsigned long long> counters;
         HBuf<infl_member_t> h_mem; HBuf<uint32_t> h_status; HBuf<unsigned long long> h_ctr; HBuf<uint8_t> h_out; Event e0, e1;
     } inf;
+    struct BamInBufs {      // BAM input (bamin_api.inc).  The stream's state between feeds: the carry and its length, the records seen, whether the header is passed.
+                            // A feed: the members' tables (inf; its out / h_out stay empty, the text goes into the stream), the stream, a group's tables,
+                            // per segment its entry, slots, count and bad record, the scan; per record its start, class, text lengths and their scans;
+                            // the kept records' starts, the texts and their pinned copies, what the kernels hand each other
+        InflateBufs inf; DBuf<uint8_t> stream, carry, text1, text2; DBuf<uint16_t> table; DBuf<uint32_t> entry, slots, seg_bad, rec_off, kept_off;
+        DBuf<uint64_t> cnt, pos, cls, cls_x, len1, len2, len1_x, len2_x; DBuf<bamin_state_t> st; HBuf<bamin_state_t> h_st; HBuf<uint64_t> h_sum; HBuf<uint8_t> h_text1, h_text2;
+        uint64_t carry_len = 0, rec_base = 0; bool header_done = false; Event e[6];
+    } bamin;
     int n_cu_cached = 0, pe_occ_cached = 0;         // hipGetDeviceProperties / the occupancy query take a millisecond each: asked once per context
 };
 
@@ -2129,5 +2138,6 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "bam_sort_api.inc"
 #include "bam_dup_api.inc"
 #include "inflate_api.inc"
+#include "bamin_api.inc"
 
 }  // extern "C"

@@ -397,6 +397,7 @@ struct Args {
     int ctx_per_gpu = 3;               // streaming path: contexts (ranges in flight) per GPU
     bool host_inflate = false;         // --host-inflate: BGZF input through zlib on the host (the record-by-record Reader), as plain gzip goes
     size_t inflate_blocks = 4096;      // --inflate-blocks: BGZF members per moni_bgzf_inflate call (4096: about 256 MB of text)
+    std::string interleaved;           // --interleaved FILE.bam: pairs from one name-grouped BAM (unaligned BAM, samtools collate): first mate, second mate
     bool dry_run = false;
     bool dry_write = false;     // --dry-run-write: no GPU, but the single-end front end's batching runs - ranges, workers of all (absent) GPUs, blocks placed in input order - with placeholder records
     moni_pe_params_t PE;               // -d, -D (paired-end)
@@ -422,6 +423,7 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--ctx-per-gpu") && i + 1 < argc) { a.ctx_per_gpu = std::max(1, atoi(argv[++i])); continue; }
         if (!strcmp(argv[i], "--bgzf")) { a.bgzf = true; continue; }
         if (!strcmp(argv[i], "--host-inflate")) { a.host_inflate = true; continue; }
+        if (!strcmp(argv[i], "--interleaved") && i + 1 < argc) { a.interleaved = argv[++i]; continue; }
         if (!strcmp(argv[i], "--inflate-blocks") && i + 1 < argc) { a.inflate_blocks = std::max<size_t>(1, strtoull(argv[++i], nullptr, 10)); continue; }
         if (!strcmp(argv[i], "--bam")) { a.bam = true; continue; }
         if (!strcmp(argv[i], "--sort")) { a.sort = true; continue; }
@@ -458,11 +460,13 @@ static void parse(int argc, char** argv, Args& a) {
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--sort [--sort-chunk BYTES]] [--mark-dup] [--host-inflate] [--inflate-blocks N] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--sort [--sort-chunk BYTES]] [--mark-dup] [--host-inflate] [--inflate-blocks N] [--interleaved FILE.bam] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
                               "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n"
                               "  --bgzf: the SAM output (single end, -1 / -2, -m, --extend) as blocked gzip in <output>.gz, compressed on the GPU; samtools, htslib and bgzip -d read it as SAM\n"
                               "  --host-inflate: BGZF (blocked gzip) input of single-end and -1 / -2 alignment is inflated on the GPU; this option sends it through zlib on the host, as plain gzip, -m, -c, --extend, the legacy and pattern-query modes and FASTA with wrapped lines always go\n"
                               "  --inflate-blocks N: BGZF members inflated per call (4096, about 256 MB of text)\n"
+                              "  -p / -1 / -2 FILE.bam: BAM input, unaligned or aligned: the records are found and turned into reads on the GPU; every primary record with bases is a read (as sequenced: reverse-strand records are turned back), secondary and supplementary records are skipped, tags are dropped\n"
+                              "  --interleaved FILE.bam: pairs from one BAM grouped by name (unaligned BAM, samtools collate): first mate, then second mate; in place of -1 / -2\n"
                               "  --bam: the SAM output (the same four modes) as BAM in <output>.bam (a trailing .sam becomes .bam): header and records encoded and compressed on the GPU, unsorted, no index\n"
                               "  --sort: with --bam, the records in coordinate order (samtools sort's: reference, position, forward strand first; ties keep input order) under @HD SO:coordinate, and the index in <output>.bam.bai; sorted on the GPU, merged through a temporary file beside the output\n"
                               "  --sort-chunk BYTES: uncompressed bytes of the records sorted and compressed per call in the merge (268435456; at least 65536)\n"
@@ -796,14 +800,17 @@ static size_t read_pairs_fast(const char* base[2], const char* end[2], size_t at
 // MappedReader::open applies, on the leading members inflated with zlib.  A thread with a context of its own (it never aligns, so it never makes the
 // large first-call allocations) inflates `blocks` members per call in file order, puts the unfinished record of the chunk before in front, cuts
 // behind the last whole record - it counts newlines; it knows the line phase because it works in order - and queues the record-aligned text.
+// A file whose text starts with BAM\1 is BAM (unaligned or aligned): the same thread feeds the members to moni_bam_in_feed, which finds the records
+// and writes the primary ones as FASTQ on the GPU; its text is record-aligned already, so nothing is counted or cut.  `pairs`: a name-grouped
+// BAM (--interleaved) - every call gives the first mates' text and the second mates', with equal numbers of reads, in the two queues.
 struct TextChunk { size_t id = 0; char* p = nullptr; size_t n = 0, cap = 0; };          // p: malloc'ed; the taker gives it back with recycle()
 struct BgzfInput {
     std::string path;
     const uint8_t* z = nullptr; size_t zn = 0; int fd = -1;
-    bool fq = false;
+    bool fq = false, bam = false, pairs = false;
     std::vector<uint64_t> cut;          // where the chunks start in the file, and its end
     moni_ctx_t* ctx = nullptr;
-    std::thread th; std::mutex mu; std::condition_variable cv_put, cv_get; std::deque<TextChunk> q; bool done = false;
+    std::thread th; std::mutex mu; std::condition_variable cv_put, cv_get; std::deque<TextChunk> q, q2; bool done = false;          // q2: the second mates' chunks of a BAM with pairs
     std::vector<TextChunk> pool;          // buffers that came back: a fresh 256 MB block costs its page faults, about twice the copy into it
     double t_inflate = 0, t_cut = 0, t_full = 0;          // seconds in moni_bgzf_inflate, in copying + cutting, waiting for room in the queue
 
@@ -835,6 +842,7 @@ struct BgzfInput {
         auto first_record = [&]() -> int {          // 1: a one-line record, 0: not one, -1: not yet whole
             const char* p = head.data();
             if (!hn) return -1;
+            if (p[0] == 'B') { if (hn < 4 && at < zn) return -1; bam = hn >= 4 && !memcmp(p, "BAM\1", 4); return bam ? 1 : 0; }
             if (p[0] != '@' && p[0] != '>') return 0;
             const char* l1 = (const char*)memchr(p, '\n', hn);
             if (!l1) return -1;
@@ -859,7 +867,7 @@ struct BgzfInput {
         }
         if (ok < 0 && at >= zn) ok = first_record();          // the text ends here
         if (ok != 1) { close(); return false; }
-        fq = head[0] == '@';
+        fq = bam || head[0] == '@';
         return true;
     }
     size_t n_chunks() const { return cut.size() - 1; }
@@ -901,7 +909,53 @@ struct BgzfInput {
         if (pool.size() < 4) pool.push_back(c); else free(c.p);
         c = TextChunk();
     }
+    // out[0, n) into dst by a few threads side by side; with `lines`, the newlines of each part are counted
+    static size_t copy_out(char* dst, const uint8_t* out, size_t n, bool lines) {
+        const int T = 8;
+        size_t cnt[T];
+        auto part = [&](int i) {
+            const size_t lo = n / T * i, hi = i + 1 == T ? n : n / T * (i + 1);
+            if (hi > lo) memcpy(dst + lo, out + lo, hi - lo);
+            cnt[i] = lines ? (size_t)std::count(dst + lo, dst + hi, '\n') : 0;
+        };
+        { std::vector<std::thread> t; for (int i = 1; i < T; ++i) t.emplace_back(part, i); part(0); for (auto& x : t) x.join(); }
+        size_t sum = 0;
+        for (int i = 0; i < T; ++i) sum += cnt[i];
+        return sum;
+    }
+    void run_bam() {
+        auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        static const char* const why[] = {"", "it does not start with BAM\\1", "a bad header", "a block_size outside [32, 2^28]", "fields that do not fit their record",
+                                          "the primary records do not come as first mate, second mate under one name (a coordinate-sorted file? samtools collate groups it by name)", "the file ends inside a header, a record or a pair"};
+        moni_bamin_params_t bp; moni_bamin_params_default(&bp);
+        bp.paired = pairs ? 1 : 0;
+        for (size_t id = 0; id + 1 < cut.size(); ++id) {
+            const uint8_t *o1 = nullptr, *o2 = nullptr; uint64_t n1 = 0, n2 = 0, nr = 0;
+            moni_bamin_stats_t st;
+            const double x0 = now();
+            const int rc = moni_bam_in_feed(ctx, z + cut[id], cut[id + 1] - cut[id], &bp, id + 2 == cut.size(), &o1, &n1, &o2, &n2, &nr, &st);
+            if (rc == MONI_EINVAL && st.inflate.bad_blocks) die(path + ": BGZF member " + std::to_string(st.inflate.first_bad_block) + " of chunk " + std::to_string(id) + " is damaged (reason " + std::to_string(st.inflate.bad_reason) + ")");
+            if (rc == MONI_EINVAL && st.bad_records) die(path + ": BAM record " + std::to_string(st.first_bad_record) + " is refused (reason " + std::to_string(st.bad_record_reason) + ": " + why[st.bad_record_reason < 7 ? st.bad_record_reason : 0] + ")");
+            if (rc) die("moni_bam_in_feed failed (" + std::to_string(rc) + ")");
+            const double x1 = now();
+            TextChunk c = buffer((size_t)n1 + 1), c2;
+            c.id = id; c.n = (size_t)n1;
+            copy_out(c.p, o1, (size_t)n1, false);
+            if (pairs) { c2 = buffer((size_t)n2 + 1); c2.id = id; c2.n = (size_t)n2; copy_out(c2.p, o2, (size_t)n2, false); }
+            const double x2 = now();
+            std::unique_lock<std::mutex> lk(mu);
+            cv_put.wait(lk, [&] { return q.size() < 2 && q2.size() < 2; });
+            q.push_back(c);
+            if (pairs) q2.push_back(c2);
+            cv_get.notify_all();
+            t_inflate += x1 - x0; t_cut += x2 - x1; t_full += now() - x2;
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        done = true;
+        cv_get.notify_all();
+    }
     void run() {
+        if (bam) return run_bam();
         auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         moni_inflate_params_t ip; moni_inflate_params_default(&ip);
         std::vector<char> carry;
@@ -917,18 +971,8 @@ struct BgzfInput {
             TextChunk c = buffer(total + 1);
             c.id = id;
             if (!carry.empty()) memcpy(c.p, carry.data(), carry.size());
-            // the text out of the pinned buffer and its newlines, by a few threads side by side
-            const int T = 8;
-            size_t cnt[T];
-            char* dst = c.p + carry.size();
-            auto part = [&](int i) {
-                const size_t lo = (size_t)ol / T * i, hi = i + 1 == T ? (size_t)ol : (size_t)ol / T * (i + 1);
-                if (hi > lo) memcpy(dst + lo, out + lo, hi - lo);
-                cnt[i] = (size_t)std::count(dst + lo, dst + hi, '\n');
-            };
-            { std::vector<std::thread> t; for (int i = 1; i < T; ++i) t.emplace_back(part, i); part(0); for (auto& x : t) x.join(); }
-            size_t lines = (size_t)std::count(carry.begin(), carry.end(), '\n');
-            for (int i = 0; i < T; ++i) lines += cnt[i];
+            // the text out of the pinned buffer and its newlines
+            const size_t lines = (size_t)std::count(carry.begin(), carry.end(), '\n') + copy_out(c.p + carry.size(), out, (size_t)ol, true);
             c.n = id + 2 == cut.size() ? total : record_end(c.p, total, lines, fq ? 4 : 2);
             carry.assign(c.p + c.n, c.p + total);
             const double x2 = now();
@@ -942,12 +986,13 @@ struct BgzfInput {
         done = true;
         cv_get.notify_all();
     }
-    // the next chunk, in file order; false behind the last
-    bool next(TextChunk& c) {
+    // the next chunk, in file order (side 1: of the second mates); false behind the last
+    bool next(TextChunk& c, int side = 0) {
+        std::deque<TextChunk>& Q = side ? q2 : q;
         std::unique_lock<std::mutex> lk(mu);
-        cv_get.wait(lk, [&] { return !q.empty() || done; });
-        if (q.empty()) return false;
-        c = q.front(); q.pop_front();
+        cv_get.wait(lk, [&] { return !Q.empty() || done; });
+        if (Q.empty()) return false;
+        c = Q.front(); Q.pop_front();
         cv_put.notify_one();
         return true;
     }
@@ -956,16 +1001,62 @@ struct BgzfInput {
         if (th.joinable()) th.join();
         if (ctx) moni_ctx_destroy(ctx);
         ctx = nullptr;
-        fprintf(stderr, "[INFO] BGZF input %s: %zu chunks; inflater thread seconds: moni_bgzf_inflate %.3f, copy + cut %.3f, waiting for room in the queue %.3f\n", path.c_str(), n_chunks(), t_inflate, t_cut, t_full);
+        fprintf(stderr, "[INFO] %s input %s: %zu chunks; inflater thread seconds: %s %.3f, copy%s %.3f, waiting for room in the queue %.3f\n", bam ? "BAM" : "BGZF", path.c_str(), n_chunks(),
+                bam ? "moni_bam_in_feed" : "moni_bgzf_inflate", t_inflate, bam ? "" : " + cut", t_cut, t_full);
     }
     ~BgzfInput() {
         if (th.joinable()) th.join();
         for (TextChunk& c : q) free(c.p);
+        for (TextChunk& c : q2) free(c.p);
         for (TextChunk& c : pool) free(c.p);
         if (ctx) moni_ctx_destroy(ctx);
         close();
     }
 };
+
+// The text of `path` starts with BAM\1 (through zlib, which reads BGZF as the gzip it is): what the modes without a BAM reader refuse by name.
+static bool looks_like_bam(const std::string& path) {
+    gzFile f = gzopen(path.c_str(), "rb");
+    if (!f) return false;
+    char h[4];
+    const bool bam = gzdirect(f) == 0 && gzread(f, h, 4) == 4 && !memcmp(h, "BAM\1", 4);
+    gzclose(f);
+    return bam;
+}
+// looks_like_bam goes through zlib, which also reads what the GPU reader does not take: BAM in plain gzip, a file cut inside a member, trailing bytes.
+// Such a file is refused by name here, before anything parses it as text.
+static void require_bgzf_bam(const std::string& path) {
+    BgzfInput probe;
+    if (!probe.open(path) || !probe.bam) die(path + ": BAM input must be whole BGZF members from the first byte to the last; plain-gzip BAM is not read, and this file may be cut off inside a member");
+}
+// --dry-run of BAM input, on the host: the records that would become reads are counted by hopping over block_size, nothing else of them is looked at
+struct BamCount { size_t reads = 0, bases = 0; std::string first, second; };
+static BamCount bam_dry_count(const std::string& path) {
+    BamCount c;
+    gzFile f = gzopen(path.c_str(), "rb");
+    if (!f) die("cannot read " + path);
+    auto get = [&](void* p, unsigned n) { return gzread(f, p, n) == (int)n; };
+    auto skip = [&](int64_t n) { return n >= 0 && gzseek(f, (z_off_t)n, SEEK_CUR) >= 0; };
+    char magic[4]; int32_t l_text = 0, n_ref = 0;
+    bool ok = get(magic, 4) && !memcmp(magic, "BAM\1", 4) && get(&l_text, 4) && skip(l_text) && get(&n_ref, 4);
+    for (int32_t r = 0; ok && r < n_ref; ++r) { int32_t l = 0; ok = get(&l, 4) && skip((int64_t)l + 4); }
+    if (!ok) die(path + ": not a whole BAM header");
+    uint8_t h[36];
+    while (get(h, 36)) {
+        uint32_t bs, l_seq; uint16_t flag;
+        memcpy(&bs, h, 4); memcpy(&flag, h + 18, 2); memcpy(&l_seq, h + 20, 4);
+        const uint32_t l_name = h[12];
+        if (bs < 32u + l_name) die(path + ": a record's fields do not fit its block_size");
+        std::string name(l_name, 0);
+        if (l_name && !get(&name[0], l_name)) break;
+        if (!skip((int64_t)bs - 32 - l_name)) break;
+        if ((flag & 0x900) || !l_seq) continue;
+        if (c.reads < 2) (c.reads ? c.second : c.first) = name.c_str();
+        c.reads += 1; c.bases += l_seq;
+    }
+    gzclose(f);
+    return c;
+}
 
 // ---- paired-end (-1 / -2): st_align's paired loop (align_reads_dispatcher.hpp:356-389) over the C ABI ----------------------------------
 // Learn the insert-size model on batches of -b pairs until it is complete (or the input ends), align those batches, then the rest (in
@@ -973,16 +1064,18 @@ struct BgzfInput {
 struct AnyReader {
     MappedReader m; Reader* z = nullptr; bool mapped = false;
     BgzfInput* bz = nullptr; TextChunk cur;          // BGZF input inflated on the GPU: m is a view of the current chunk
+    int side = 0;                                    // 1: the second mates of `first`'s BAM with pairs (bz is first's)
     explicit AnyReader(const std::string& path, bool gpu_inflate = false) {
         if (gpu_inflate) { bz = new BgzfInput(); if (!bz->open(path)) { delete bz; bz = nullptr; } }
         if (!bz) { mapped = m.open(path); if (!mapped) z = new Reader(path); }
     }
-    ~AnyReader() { if (bz) { m.p = nullptr; free(cur.p); delete bz; } delete z; }          // (free: the pool may be gone with bz's thread)
+    explicit AnyReader(AnyReader& first) : bz(first.bz), side(1) {}
+    ~AnyReader() { if (bz) { m.p = nullptr; free(cur.p); if (!side) delete bz; } delete z; }          // (free: the pool may be gone with bz's thread)
     bool fastq_view() const { return bz ? bz->fq : mapped && m.p[m.at < m.n ? m.at : 0] == '@'; }
     // the next chunk becomes the view; false behind the last
     bool refill() {
         bz->recycle(cur); m.p = nullptr; m.n = m.at = 0;
-        if (!bz->next(cur)) return false;
+        if (!bz->next(cur, side)) return false;
         m.p = cur.p; m.n = cur.n;
         return true;
     }
@@ -1090,8 +1183,27 @@ static int run_paired(Args& a, const std::string& sam_filename) {
     a.PE.find_orphan = a.find_orphan ? 1 : 0;            // -u switches orphan recovery off (align_full_ksw2.cpp:248-250)
     a.PE.secondary_chains = a.secondary ? 1 : 0;         // -Z: find_chains_secondary (the second track of the chaining, on the staged paired kernels)
     info("Output file: " + sam_filename);
+    const bool one_file = !a.interleaved.empty();
+    if (one_file) a.mate1 = a.mate2 = a.interleaved;
+    const bool bam_in = looks_like_bam(a.mate1) || looks_like_bam(a.mate2);
+    if (one_file && !bam_in) die("--interleaved takes a BAM file");
+    if (bam_in && !(looks_like_bam(a.mate1) && looks_like_bam(a.mate2))) die("-1 and -2: one mate file is BAM, the other is not");
+    if (bam_in && a.host_inflate) die("--host-inflate cannot be combined with BAM input: there is no host BAM parser, the records are read on the GPU");
+    if (bam_in && (a.report_mems || a.csv)) die(std::string(a.report_mems ? "-m" : "-c") + " does not take BAM input");
+    if (bam_in) { require_bgzf_bam(a.mate1); if (!one_file) require_bgzf_bam(a.mate2); }
+    if (bam_in && a.dry_run) {
+        const BamCount c1 = bam_dry_count(a.mate1), c2 = one_file ? c1 : bam_dry_count(a.mate2);
+        if (one_file ? (c1.reads & 1) != 0 : c1.reads != c2.reads) die(one_file ? "--interleaved: an odd number of primary records" : "the mate files have different numbers of records");
+        const std::string& second = one_file ? c1.second : c2.first;
+        printf("dry-run: pairs=%zu bases=%zu min_len=%u filter_dir=%u dir_thr=%.1f find_orphan=%u b=%zu threads=%zu gpus=%d out=%s first=%s second=%s%s input=bam\n", one_file ? c1.reads / 2 : c1.reads,
+               one_file ? c1.bases : c1.bases + c2.bases, a.P.min_len, a.PE.filter_dir, a.PE.dir_thr, a.PE.find_orphan, a.b, a.th, a.gpus, sam_filename.c_str(), c1.first.c_str(), second.c_str(), output_word(a));
+        return 0;
+    }
     const bool gpu_inflate = !a.host_inflate && !a.report_mems && !a.csv && !a.dry_run;
-    AnyReader r1(a.mate1, gpu_inflate), r2(a.mate2, gpu_inflate);
+    AnyReader r1(a.mate1, gpu_inflate);
+    if (one_file) r1.bz->pairs = true;
+    const std::unique_ptr<AnyReader> second(one_file ? new AnyReader(r1) : new AnyReader(a.mate2, gpu_inflate));          // (it goes before r1 does)
+    AnyReader& r2 = *second;
     if (a.dry_run) {
         bool bz_in = false;          // counting stays on the host; the word says what the run would do
         if (!a.host_inflate && !a.report_mems && !a.csv) { BgzfInput p1, p2; bz_in = p1.open(a.mate1) || p2.open(a.mate2); }
@@ -1109,7 +1221,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
         if (moni_ctx_create(idx[g], &ctx[g])) die("cannot create a context on GPU " + std::to_string(g));
     }
     if (r1.bz) r1.bz->start(idx[0], a.inflate_blocks);
-    if (r2.bz) r2.bz->start(idx[0], a.inflate_blocks);
+    if (r2.bz && !one_file) r2.bz->start(idx[0], a.inflate_blocks);
     const auto t0 = std::chrono::steady_clock::now();
     Sink sink;          // --sort: the learning batches are run 0, the workers' batches follow
     sink.open(sam_filename, a, true);
@@ -1255,7 +1367,7 @@ static int run_paired(Args& a, const std::string& sam_filename) {
              std::to_string(sl) + ", waiting for the block's place " + std::to_string(sw) + ", file writes " + std::to_string(sr));
     }
     if (r1.bz) r1.bz->finish();
-    if (r2.bz) r2.bz->finish();
+    if (r2.bz && !one_file) r2.bz->finish();
     sink.finish(wctx);
     for (int g = 0; g < a.gpus; ++g) for (int k = 1; k < per_gpu; ++k) moni_ctx_destroy(wctx[(size_t)g * per_gpu + k]);
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1586,8 +1698,9 @@ int main(int argc, char** argv) {
     // -n: <prefix>.thrbv.full.ms (ms_pointers<>: no LCP samples; the occurrence walks measure the LCP on the text, seed_finder.hpp:346-370).
     // -q: the reference would take the text from <prefix>.slp (SelfShapedSlp) instead of <prefix>.plain.slp; both grammars spell the same
     //     text and neither is read here - the text is rebuilt from the BWT - so the flag changes nothing (align_full_ksw2.cpp:414-426)
-    const bool paired = !a.mate1.empty() || !a.mate2.empty();
-    if (paired && (a.mate1.empty() || a.mate2.empty())) die("paired-end alignment needs both -1 and -2");
+    if (!a.interleaved.empty() && (!a.patterns.empty() || !a.mate1.empty() || !a.mate2.empty())) die("--interleaved cannot be combined with -p, -1 or -2: it names the one file of both mates");
+    const bool paired = !a.mate1.empty() || !a.mate2.empty() || !a.interleaved.empty();
+    if (paired && a.interleaved.empty() && (a.mate1.empty() || a.mate2.empty())) die("paired-end alignment needs both -1 and -2");
     if (paired && (a.legacy_ms || a.legacy_mems)) die("--ms / --mems take single-end input (-p)");
     if (a.split && !(a.legacy_ms || a.legacy_mems)) die("--split belongs to --ms / --mems");
     if ((a.seg_len_set || a.overlap_set) && !a.split) die("--seg-len / --overlap belong to --split");
@@ -1613,7 +1726,7 @@ int main(int argc, char** argv) {
     std::string fn = a.filename;
     std::vector<char> tmp(fn.begin(), fn.end()); tmp.push_back(0);
     const std::string base_name = basename(tmp.data());
-    std::string sam_filename = (paired ? a.mate1 : a.patterns) + "_" + base_name + "_" + std::to_string(a.P.min_len) + ".sam";   // align_full_ksw2.cpp:347-353
+    std::string sam_filename = (!a.interleaved.empty() ? a.interleaved : paired ? a.mate1 : a.patterns) + "_" + base_name + "_" + std::to_string(a.P.min_len) + ".sam";   // align_full_ksw2.cpp:347-353
     if (!a.output.empty()) sam_filename = a.output;
     if (a.bgzf) sam_filename += ".gz";
     if (a.bam) {             // a trailing .sam becomes .bam
@@ -1626,6 +1739,18 @@ int main(int argc, char** argv) {
     for (const Mode& m : MODES) if (a.*m.set) { M = &m; break; }
     if (M && M->suffix && a.output.empty()) sam_filename = a.patterns + "_" + base_name;       // mems.cpp / matching_statistics.cpp / run_spumoni.cpp: <patterns>_<index> + .mems / .pointers / .lengths / .pseudo_lengths (and .locate / .seqcount)
     info("Output file: " + sam_filename);
+    if (looks_like_bam(a.patterns)) {          // BAM is read on the GPU, by the streaming path of plain alignment alone
+        if (M) die(std::string(M->flag) + " does not take BAM input");
+        if (a.host_inflate) die("--host-inflate cannot be combined with BAM input: there is no host BAM parser, the records are read on the GPU");
+        if (getenv("MONI_CLI_QUEUE_PATH")) die("the queue path does not take BAM input");
+        require_bgzf_bam(a.patterns);
+        if (a.dry_run) {
+            const BamCount c = bam_dry_count(a.patterns);
+            printf("dry-run: reads=%zu bases=%zu min_len=%u ext_len=%u S=%u F=%.2f O=%d,%d E=%d,%d threads=%zu gpus=%d out=%s first=%s%s input=bam\n", c.reads, c.bases, a.P.min_len,
+                   a.P.ext_len, a.P.n_seeds_thr, a.P.freq_thr, a.P.gapo, a.P.gapo2, a.P.gape, a.P.gape2, a.th, a.gpus, sam_filename.c_str(), c.first.c_str(), output_word(a));
+            return 0;
+        }
+    }
     BgzfInput bzin;          // BGZF input of plain alignment: inflated on the GPU; counting (--dry-run) stays with the Reader
     const bool bz = !a.host_inflate && !M && getenv("MONI_CLI_QUEUE_PATH") == nullptr && bzin.open(a.patterns);
     MappedReader mrd;
