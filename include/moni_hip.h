@@ -708,6 +708,53 @@ int  moni_bai_add(moni_bai_t *b, const moni_bam_ent_t *ents, uint64_t n, uint64_
 int  moni_bai_finish(moni_bai_t *b, uint64_t eof_off, const uint8_t **bytes, uint64_t *len);
 void moni_bai_destroy(moni_bai_t *b);
 
+/* ---- depth of coverage of the sorted output ---------------------------------------------- */
+/* The references r = 0 .. n_ref - 1 of the header set on the context, of lengths LN_r.  Reference r owns LN_r + 1 slots of one int32 array,
+ * from base_r = sum over q < r of (LN_q + 1); the last slot of a reference takes the -1 of a block that ends at LN_r and is never a base.
+ * A record counts iff refID >= 0, pos >= 0, n_cigar_op > 0, flag & exclude_flags == 0 and mapq >= min_mapq; one that fails several of
+ * these is counted once, as unplaced (the first three) before skipped_flag before skipped_mapq.  The CIGAR is walked from p = pos: M = X D
+ * cover [p, p + len) and advance p, N advances p, I S H P do nothing; adjacent covering operations are one block.  A block [b, e) is
+ * clipped to e = min(e, LN_r) and dropped if b >= LN_r (the record then counts in `clipped`, once); it adds +1 at slot base_r + b and -1 at
+ * base_r + e, and counts in `blocks`.  The depth at base x of r is the sum of the slots base_r .. base_r + x.  No mate-overlap correction:
+ * mosdepth's --fast-mode with deletions counted.  The depth is an int32 because an object counts fewer than 2^31 records in all. */
+typedef struct moni_cov moni_cov_t;
+typedef struct { uint32_t exclude_flags, min_mapq, reserved[2]; } moni_cov_params_t;      /* defaults: 0x704 (mosdepth's 1796), 0 */
+typedef struct { uint64_t records, counted, skipped_flag, skipped_mapq, unplaced, clipped, blocks,
+                 bad_records, first_bad_record; uint32_t bad_reason, pad;      /* as moni_bam_sort_stats_t has them (MONI_BAMSORT_OFFSET .. LENGTH) */
+                 double t_add, t_total; } moni_cov_stats_t;      /* the call's kernels (HIP-event seconds); host seconds of the call */
+typedef struct { uint64_t length, bases; uint32_t min, max; } moni_cov_ref_t;      /* bases: the sum of the depth over [0, length) */
+void moni_cov_params_default(moni_cov_params_t *p);
+/* An object for the dictionary of the header set on ctx, its slots zeroed on ctx's device and owned by the object (4 bytes a slot).  It may be
+ * added to from any context of that device whose header has the same dictionary, from several host threads at once: the adds are
+ * device-scope integer atomics, so the result is exact and independent of their order.  Seal, next, windows and destroy are for one thread,
+ * after the adds have returned.  MONI_EINVAL: a NULL argument, no header set, a non-zero reserved word. */
+int  moni_cov_create(moni_ctx_t *ctx, const moni_cov_params_t *prm, moni_cov_t **cov);
+void moni_cov_destroy(moni_cov_t *cov);
+/* records, len, offs, n: raw BAM records in host memory as moni_bam_sort takes them, with its checks and reasons; a bad record adds nothing
+ * of the call (MONI_EINVAL, stats carry bad_records, first_bad_record, bad_reason).  MONI_ERANGE, with nothing added, once the object's
+ * counted records would reach 2^31.  MONI_EINVAL too: a sealed object, a context of another device or of another number of references.
+ * Both adds leave undisturbed what moni_bam_records leaves undisturbed, and the results of the sort calls.  stats may be NULL. */
+int  moni_cov_add(moni_ctx_t *ctx, moni_cov_t *cov, const void *records, uint64_t len, const uint64_t *offs, uint64_t n, moni_cov_stats_t *stats);
+/* The records that the context's last successful moni_bam_sort, moni_bam_sort_marked, moni_bam_sorted_run or moni_bam_sorted_run_dup left on
+ * the device, in coordinate order and with the 0x400 bits of moni_bam_sort_marked set: no second upload.  The result is that of moni_cov_add on
+ * the raw bytes those calls return.  MONI_EINVAL if no such call has succeeded on ctx. */
+int  moni_cov_add_sorted(moni_ctx_t *ctx, moni_cov_t *cov, moni_cov_stats_t *stats);
+/* The slots become depths (one scan in place; every reference's slots sum to zero, so the scan needs no restart), and *refs (*n_ref entries,
+ * valid until moni_cov_destroy) the figures of every reference.  After a seal the adds return MONI_EINVAL; a second seal gives the same refs. */
+int  moni_cov_seal(moni_ctx_t *ctx, moni_cov_t *cov, const moni_cov_ref_t **refs, uint32_t *n_ref);
+/* An iterator over the per-base text in genome order: for every reference the maximal runs of equal depth over [0, LN_r), zero included, one
+ * line `name\tstart\tend\tdepth\n` a run (0-based, half-open; mosdepth's per-base.bed).  A call looks at no more than max_bases slots and
+ * writes no more than max_lines lines (both at least 1); lines are whole, and a run that reaches past what a call looked at is written by the
+ * call that sees its end.  *text (*len bytes, possibly 0) is a pinned buffer of ctx, valid until ctx's next moni_cov_next or its destroy;
+ * *done = 1 with the last piece.  The pieces of all calls, one behind the other, are the same bytes for every max_bases and max_lines.
+ * MONI_EINVAL: a NULL argument, an object that is not sealed, max_bases or max_lines 0. */
+int  moni_cov_next(moni_ctx_t *ctx, moni_cov_t *cov, uint64_t max_bases, uint64_t max_lines, const char **text, uint64_t *len, int *done);
+/* *sums (*n = ceil(LN_r / window) entries, a pinned buffer of ctx valid until ctx's next moni_cov_windows or its destroy): the sum of the
+ * depth over [k * window, min((k + 1) * window, LN_r)).  MONI_EINVAL: not sealed, ref_id >= n_ref, window outside [1, 2^31). */
+int  moni_cov_windows(moni_ctx_t *ctx, moni_cov_t *cov, uint32_t ref_id, uint32_t window, const uint64_t **sums, uint64_t *n);
+/* For the tests alone: the object's count of counted records becomes `counted`, so that the 2^31 bound is reached without 2^31 records. */
+void moni_cov_test_set_counted(moni_cov_t *cov, uint64_t counted);
+
 /* ---- BGZF input: blocked gzip inflated on the GPU --------------------------------------- */
 /* Input is a concatenation of BGZF members (SAM specification 4.1: what bgzip, unaligned BAM and moni_bgzf_compress write): gzip members
  * with the `BC` extra subfield - anywhere in the extra field -, each at most 64 KB and inflating to at most 64 KB, with any number of

@@ -44,6 +44,8 @@ EXPORTS = [
     "moni_bai_create", "moni_bai_add", "moni_bai_finish", "moni_bai_destroy",
     "moni_inflate_params_default", "moni_bgzf_scan", "moni_bgzf_inflate",
     "moni_bamin_params_default", "moni_bam_in_reset", "moni_bam_in_feed",
+    "moni_cov_params_default", "moni_cov_create", "moni_cov_destroy", "moni_cov_add", "moni_cov_add_sorted", "moni_cov_seal", "moni_cov_next", "moni_cov_windows",
+    "moni_cov_test_set_counted",
 ]
 
 
@@ -250,6 +252,22 @@ class BamBadRecord(ValueError):
         r = stats["bad_reason"]
         super().__init__("moni_bam_sort: %d bad record(s), the first is record %d (%s)" %
                          (stats["bad_records"], stats["first_bad_record"], BAMSORT_REASONS[r] if r < len(BAMSORT_REASONS) else r))
+
+
+class CovParamsC(C.Structure):
+    _fields_ = [("exclude_flags", C.c_uint32), ("min_mapq", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class CovStatsC(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("counted", C.c_uint64), ("skipped_flag", C.c_uint64), ("skipped_mapq", C.c_uint64), ("unplaced", C.c_uint64),
+                ("clipped", C.c_uint64), ("blocks", C.c_uint64), ("bad_records", C.c_uint64), ("first_bad_record", C.c_uint64),
+                ("bad_reason", C.c_uint32), ("pad", C.c_uint32), ("t_add", C.c_double), ("t_total", C.c_double)]
+
+
+# moni_cov_ref_t: the figures of one reference of a sealed coverage object
+COV_REF_DTYPE = np.dtype([("length", np.uint64), ("bases", np.uint64), ("min", np.uint32), ("max", np.uint32)])
+COV_EXCLUDE_DEFAULT = 0x704
+assert COV_REF_DTYPE.itemsize == 24 and C.sizeof(CovStatsC) == 96
 
 
 def bam_merge_plan(keys, offs, chunk_bytes: int) -> np.ndarray:
@@ -493,6 +511,18 @@ def lib():
         L.moni_bam_in_reset.argtypes = [C.c_void_p]
         L.moni_bam_in_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BamInParamsC), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(BamInStatsC)]
+        L.moni_cov_params_default.argtypes = [C.POINTER(CovParamsC)]
+        L.moni_cov_params_default.restype = None
+        L.moni_cov_create.argtypes = [C.c_void_p, C.POINTER(CovParamsC), C.POINTER(C.c_void_p)]
+        L.moni_cov_destroy.argtypes = [C.c_void_p]
+        L.moni_cov_destroy.restype = None
+        L.moni_cov_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(CovStatsC)]
+        L.moni_cov_add_sorted.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CovStatsC)]
+        L.moni_cov_seal.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        L.moni_cov_next.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        L.moni_cov_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.moni_cov_test_set_counted.argtypes = [C.c_void_p, C.c_uint64]
+        L.moni_cov_test_set_counted.restype = None
         _lib = L
     return _lib
 
@@ -529,6 +559,82 @@ def flat_struct(fi, without_text: bool = False, without_lcp: bool = False) -> Fl
         s.lift_ins_off, s.lift_ins = lf.ins_off.ctypes.data, lf.ins.ctypes.data
         s.lift_del_off, s.lift_del = lf.del_off.ctypes.data, lf.dele.ctypes.data
     return s
+
+
+class Coverage:
+    """moni_cov_*: the depth of coverage of the records added, over the dictionary of the header set on `ctx`.  Every method
+    takes the context it runs on; an add may run on any context of the same device, from several threads at once.  The calls return the
+    library's code first, so that a test sees a refusal as it is; rc_only=False raises on any code but 0."""
+
+    def __init__(self, ctx, exclude_flags: int = COV_EXCLUDE_DEFAULT, min_mapq: int = 0, reserved=(0, 0)):
+        self._L = lib()
+        self._h = C.c_void_p()
+        p = CovParamsC()
+        self._L.moni_cov_params_default(C.byref(p))
+        assert p.exclude_flags == COV_EXCLUDE_DEFAULT and p.min_mapq == 0
+        p.exclude_flags, p.min_mapq = exclude_flags, min_mapq
+        p.reserved[0], p.reserved[1] = reserved
+        self.rc = self._L.moni_cov_create(ctx._h, C.byref(p), C.byref(self._h))
+        if self.rc:
+            self._h = C.c_void_p()
+            raise ValueError("moni_cov_create failed with code %d" % self.rc)
+
+    @staticmethod
+    def _stats(st):
+        return {k: getattr(st, k) for k, _ in CovStatsC._fields_ if k != "pad"}
+
+    def add(self, ctx, records, offs):
+        """moni_cov_add: (rc, stats)"""
+        buf = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray, memoryview)) else np.ascontiguousarray(records, dtype=np.uint8)
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        st = CovStatsC()
+        rc = self._L.moni_cov_add(ctx._h, self._h, buf.ctypes.data if buf.size else None, buf.size, o.ctypes.data if o.size else None, max(len(o) - 1, 0), C.byref(st))
+        return rc, self._stats(st)
+
+    def add_sorted(self, ctx):
+        """moni_cov_add_sorted: (rc, stats)"""
+        st = CovStatsC()
+        rc = self._L.moni_cov_add_sorted(ctx._h, self._h, C.byref(st))
+        return rc, self._stats(st)
+
+    def seal(self, ctx):
+        """moni_cov_seal: (rc, [(length, bases, min, max)] per reference)"""
+        refs, n = C.c_void_p(), C.c_uint32()
+        rc = self._L.moni_cov_seal(ctx._h, self._h, C.byref(refs), C.byref(n))
+        if rc or not n.value:
+            return rc, []
+        a = np.frombuffer(C.string_at(refs.value, COV_REF_DTYPE.itemsize * n.value), dtype=COV_REF_DTYPE)
+        return rc, [tuple(int(x) for x in r) for r in a]
+
+    def next(self, ctx, max_bases: int, max_lines: int):
+        """moni_cov_next: (rc, the piece of text, done)"""
+        t, n, done = C.c_void_p(), C.c_uint64(), C.c_int()
+        rc = self._L.moni_cov_next(ctx._h, self._h, max_bases, max_lines, C.byref(t), C.byref(n), C.byref(done))
+        return rc, (C.string_at(t.value, n.value) if rc == 0 and n.value else b""), done.value
+
+    def text(self, ctx, max_bases: int = 1 << 26, max_lines: int = 1 << 22) -> bytes:
+        """the whole per-base text: the pieces of moni_cov_next until done"""
+        out = []
+        while True:
+            rc, piece, done = self.next(ctx, max_bases, max_lines)
+            _chk(rc, "moni_cov_next")
+            out.append(piece)
+            if done:
+                return b"".join(out)
+
+    def windows(self, ctx, ref_id: int, window: int):
+        """moni_cov_windows: (rc, [sum of the depth per window])"""
+        p, n = C.c_void_p(), C.c_uint64()
+        rc = self._L.moni_cov_windows(ctx._h, self._h, ref_id, window, C.byref(p), C.byref(n))
+        return rc, (np.frombuffer(C.string_at(p.value, 8 * n.value), dtype=np.uint64).tolist() if rc == 0 and n.value else [])
+
+    def test_set_counted(self, counted: int):
+        self._L.moni_cov_test_set_counted(self._h, counted)
+
+    def close(self):
+        if self._h:
+            self._L.moni_cov_destroy(self._h)
+            self._h = C.c_void_p()
 
 
 class Index:

@@ -78,6 +78,7 @@ static int bam_sorted_run_core(moni_ctx_t* c, const void* sam_lines, uint64_t le
     moni_bam_sort_stats_t st;
     memset(&st, 0, sizeof st);
     *records_len = 0; *n = 0;
+    B.have_sorted = false;
     // the encoder's passes, as moni_bam_records runs them: the records stay in moni_ctx::bam.out, their offsets in moni_ctx::bam.off
     moni_bam_stats_t es;
     uint64_t n_rec = 0, enc_bytes = 0;
@@ -112,6 +113,7 @@ static int bam_sorted_run_core(moni_ctx_t* c, const void* sam_lines, uint64_t le
         } else B.h_off.p[0] = 0;
         *records = B.h_rec.p; *records_len = total; *keys = B.h_key.p; *offs = B.h_off.p; *n = n_rec;
         st.bam_bytes = total; st.out_bytes = total;
+        B.have_sorted = true; B.sorted_n = n_rec; B.sorted_len = total;
     }
     st.t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;
@@ -136,6 +138,7 @@ static int bam_sort_core(moni_ctx_t* c, const void* records, uint64_t len, const
     memset(&st, 0, sizeof st);
     st.in_bytes = len; st.records = n;
     *out_len = 0;
+    B.have_sorted = false;
     int rc = MONI_OK;
     uint64_t total = 0;
     if ((n ? offs[n] : 0) != len || n >= (1ull << 32)) { st.bad_records = 1; st.first_bad_record = n; st.bad_reason = MONI_BAMSORT_LENGTH; rc = MONI_EINVAL; }
@@ -160,6 +163,7 @@ static int bam_sort_core(moni_ctx_t* c, const void* records, uint64_t len, const
         }
         *ents = B.h_ents.p;
         st.bam_bytes = total;
+        B.have_sorted = true; B.sorted_n = n; B.sorted_len = total;
     }
     st.t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;

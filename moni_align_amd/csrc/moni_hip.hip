@@ -12,6 +12,7 @@
 #include <chrono>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include <sched.h>
 #include <cstdio>
@@ -54,6 +55,7 @@
 #include "bam_index.hpp"
 #include "inflate_kernels.hip"
 #include "bamin_kernels.hip"
+#include "cov_kernels.hip"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "moni_hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return MONI_ENODEV; } } while (0)
 
@@ -264,6 +266,7 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
         DBuf<uint8_t> in, out, sort_tmp; DBuf<uint64_t> in_off, key[2], size, out_off; DBuf<uint32_t> idx[2]; DBuf<bam_pre_t> pre; DBuf<moni_bam_ent_t> ents;
         DBuf<unsigned long long> ctr; HBuf<unsigned long long> h_sum; HBuf<uint8_t> h_rec; HBuf<uint64_t> h_key, h_off; HBuf<moni_bam_ent_t> h_ents;
         Event e0, e1, e2, e3, e4;
+        bool have_sorted = false; uint64_t sorted_n = 0, sorted_len = 0;      // the last sort call succeeded: out / out_off hold its sorted_n records (moni_cov_add_sorted)
     } bsort;
     struct BamDupBufs {     // duplicate marking (bam_dup_api.inc).  A run: the records' signatures, their places in the sorted run, the units' entry counts and their scan,
                             // the entries and their pinned copy.  The resolve: all entries, where the runs' entries and marks begin, the records' places among all
@@ -285,6 +288,11 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
         DBuf<uint64_t> cnt, pos, cls, cls_x, len1, len2, len1_x, len2_x; DBuf<bamin_state_t> st; HBuf<bamin_state_t> h_st; HBuf<uint64_t> h_sum; HBuf<uint8_t> h_text1, h_text2;
         uint64_t carry_len = 0, rec_base = 0; bool header_done = false; Event e[6];
     } bamin;
+    struct CovBufs {        // depth of coverage (cov_api.inc).  An add: moni_cov_add's records and offsets as given, the counters.  A piece of text: the run-end flags of
+                            // the call's slots and their scan, the ends kept, the lines' lengths and offsets, the text and its pinned copy.  The windows' sums; grow-only
+        DBuf<uint8_t> in, flag, text, scan_tmp; DBuf<uint64_t> in_off, pos, len, off, sums; DBuf<uint32_t> scan; DBuf<unsigned long long> ctr;
+        HBuf<unsigned long long> h_ctr; HBuf<char> h_text; HBuf<uint64_t> h_sums; Event e0, e1, e2, e3;
+    } cov;
     int n_cu_cached = 0, pe_occ_cached = 0;         // hipGetDeviceProperties / the occupancy query take a millisecond each: asked once per context
 };
 
@@ -2139,5 +2147,6 @@ int moni_sam_header(const moni_index_t* I, char** sam, uint64_t* sam_len) {
 #include "bam_dup_api.inc"
 #include "inflate_api.inc"
 #include "bamin_api.inc"
+#include "cov_api.inc"
 
 }  // extern "C"

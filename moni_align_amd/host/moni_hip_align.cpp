@@ -102,6 +102,10 @@ static void pwrite_all(int fd, const char* p, size_t n, uint64_t at) {
 // file beside the output - unlinked as soon as it is open -, its keys and offsets stay in memory, 16 bytes a read.  Phase 2, behind the last
 // batch: moni_bam_merge_plan cuts the merged order into chunks, one contiguous slice of every run each; the contexts take the chunks in turn -
 // pread the slices, moni_bam_sort, the blocks at their place in the file - and moni_bai_add sees them in chunk order.
+// --coverage: the files beside <out>.bam from a sealed object - the summary, the per-base text in BGZF blocks and, with a window, the regions
+struct CoverageOut { bool on = false; uint32_t window = 0, min_mapq = 0; uint64_t max_bases = 64ull << 20, max_lines = 4ull << 20; };      // the two limits of a moni_cov_next call stand as proposed: neither has been measured
+static void write_coverage(moni_ctx_t* c, moni_cov_t* cov, const CoverageOut& co, const std::string& bam_path, const std::string& header, uint64_t counted, uint64_t records);
+
 struct SortedBam {
     struct Run { uint64_t at = 0; std::vector<uint64_t> keys, offs{0}; std::vector<moni_bam_dup_t> dups; std::vector<uint8_t> marks; };
     bool mark = false;              // --mark-dup: the runs keep their entries, 32 bytes a pair or fragment; the marks, a byte a record, come between the phases
@@ -110,13 +114,15 @@ struct SortedBam {
     int tmp_fd = -1;
     uint64_t chunk_bytes = 0;
     uint32_t n_ref = 0;
+    CoverageOut cover;              // --coverage: every chunk's records are added to one object while they are still on the device
+    std::string out_path, sam_header;
     std::string bai_path;
     std::atomic<uint64_t> tmp_len{0};
     std::mutex mu;
     std::map<size_t, Run> runs;
 
     void open(const std::string& out_path, uint64_t chunk, const std::string& header) {
-        chunk_bytes = chunk; bai_path = out_path + ".bai";
+        chunk_bytes = chunk; bai_path = out_path + ".bai"; this->out_path = out_path; sam_header = header;
         for (size_t at = 0; at < header.size(); at = header.find('\n', at) == std::string::npos ? header.size() : header.find('\n', at) + 1)
             if (!header.compare(at, 4, "@SQ\t")) ++n_ref;
         std::string t = out_path + ".sort.XXXXXX";
@@ -190,6 +196,14 @@ struct SortedBam {
         moni_bai_t* bai = moni_bai_create(n_ref);
         if (!bai) die("out of memory");
         moni_bam_params_t bp; moni_bam_params_default(&bp);
+        moni_cov_t* cov = nullptr;
+        std::atomic<uint64_t> cov_counted{0}, cov_records{0};
+        if (cover.on) {
+            moni_cov_params_t cp; moni_cov_params_default(&cp);
+            cp.min_mapq = cover.min_mapq;
+            const int rc = moni_cov_create(cs[0], &cp, &cov);
+            if (rc) die("moni_cov_create failed (" + std::to_string(rc) + (rc == MONI_ENOMEM ? "): --coverage takes 4 bytes of the device's memory per reference base" : ")"));
+        }
         std::atomic<uint64_t> next{0};
         std::mutex mo; std::condition_variable cv;
         uint64_t upto = 0, off_upto = at;
@@ -213,6 +227,12 @@ struct SortedBam {
                 const uint8_t* z; uint64_t zl; const moni_bam_ent_t* ents; moni_bam_sort_stats_t st;
                 const int rc = moni_bam_sort_marked(c, buf.data(), bytes, offs.data(), n, mark ? mk.data() : nullptr, &bp, &z, &zl, &ents, &st);
                 if (rc) die("moni_bam_sort failed (" + std::to_string(rc) + ")");
+                if (cov) {          // z and ents stay valid: the adds have buffers of their own
+                    moni_cov_stats_t vs;
+                    const int vrc = moni_cov_add_sorted(c, cov, &vs);
+                    if (vrc) die("moni_cov_add_sorted failed (" + std::to_string(vrc) + (vrc == MONI_ERANGE ? "): --coverage counts fewer than 2^31 records" : ")"));
+                    cov_counted += vs.counted; cov_records += vs.records;
+                }
                 cs_.clear();
                 for (uint64_t p = 0; p < zl;) { const uint32_t b = (uint32_t)z[p + 16] + ((uint32_t)z[p + 17] << 8) + 1u; cs_.push_back(b); p += b; }
                 uint64_t mine;
@@ -235,6 +255,10 @@ struct SortedBam {
         for (size_t w = 1; w < cs.size(); ++w) th.emplace_back(worker, cs[w]);
         worker(cs[0]);
         for (auto& t : th) t.join();
+        if (cov) {
+            write_coverage(cs[0], cov, cover, out_path, sam_header, cov_counted.load(), cov_records.load());
+            moni_cov_destroy(cov);
+        }
         const uint8_t* ib; uint64_t il;
         if (moni_bai_finish(bai, off_upto, &ib, &il)) die("moni_bai_finish failed");
         FILE* f = fopen(bai_path.c_str(), "w");
@@ -406,6 +430,8 @@ struct Args {
     bool sort = false;                 // --sort (with --bam): the records in coordinate order, with <out>.bam.bai beside them
     uint64_t sort_chunk = 256ull << 20; bool sort_chunk_set = false;      // --sort-chunk: uncompressed bytes of a chunk of the merge
     bool mark_dup = false;             // --mark-dup (with --sort): duplicates flagged 0x400 on the GPU between the two phases of the sort
+    bool coverage = false;             // --coverage (with --sort): depth of coverage of the sorted records, added on the GPU as the chunks are merged
+    uint32_t cov_window = 0, cov_mapq = 0; bool cov_window_set = false, cov_mapq_set = false; bool cov_window_bad = false, cov_mapq_bad = false;      // --cov-window N, --cov-mapq Q
     bool bgzf = false;                 // --bgzf: the SAM text as BGZF blocks in <out>.gz, deflated on the GPU by the context that aligned it (moni_bgzf_compress)
 };
 
@@ -428,6 +454,9 @@ static void parse(int argc, char** argv, Args& a) {
         if (!strcmp(argv[i], "--bam")) { a.bam = true; continue; }
         if (!strcmp(argv[i], "--sort")) { a.sort = true; continue; }
         if (!strcmp(argv[i], "--mark-dup")) { a.mark_dup = true; continue; }
+        if (!strcmp(argv[i], "--coverage")) { a.coverage = true; continue; }
+        if (!strcmp(argv[i], "--cov-window") && i + 1 < argc) { const unsigned long long v = strtoull(argv[++i], nullptr, 10); a.cov_window = (uint32_t)v; a.cov_window_set = true; a.cov_window_bad = v < 1 || v >= (1ull << 31); continue; }
+        if (!strcmp(argv[i], "--cov-mapq") && i + 1 < argc) { const unsigned long long v = strtoull(argv[++i], nullptr, 10); a.cov_mapq = (uint32_t)v; a.cov_mapq_set = true; a.cov_mapq_bad = v > 255; continue; }
         if (!strcmp(argv[i], "--sort-chunk") && i + 1 < argc) { a.sort_chunk = strtoull(argv[++i], nullptr, 10); a.sort_chunk_set = true; continue; }
         if (!strcmp(argv[i], "--ms")) { a.legacy_ms = true; continue; }
         if (!strcmp(argv[i], "--mems")) { a.legacy_mems = true; continue; }
@@ -460,7 +489,7 @@ static void parse(int argc, char** argv, Args& a) {
     }
     const std::string usage = "usage: " + std::string(argv[0]) + " infile [-p patterns] [-o output] [-t threads] [-b batch] [-l len] [-L ext_l] [-A smatch] "
                               "[-B smismatch] [-O gapo] [-E gape] [-s seeds_dis] [-f freq_dis] [-S seeds_thr] [-F freq_thr] [-w max_iter] [-v max_pred] "
-                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--sort [--sort-chunk BYTES]] [--mark-dup] [--host-inflate] [--inflate-blocks N] [--interleaved FILE.bam] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
+                              "[-x max_dist_x] [-y max_dist_y] [-k min_chain_mem] [-j min_chain_score] [-a chain_dis] [--gpus N] [--gpu-batch reads] [--bgzf] [--bam] [--sort [--sort-chunk BYTES]] [--mark-dup] [--coverage [--cov-window N] [--cov-mapq Q]] [--host-inflate] [--inflate-blocks N] [--interleaved FILE.bam] [--ms | --mems [--split [--seg-len N] [--overlap N]] | --extend | --pseudo-ms | --screen [--window N] [--min-win N] [--ks NUM/DEN] [--one-strand] | --locate [--max-occ N] [--both-strands] | --seq-count [--max-walk N] [--both-strands] | --loci [--max-walk N] [--both-strands] [--no-lift] | --approx K [--max-hits N] [--max-occ N] [--both-strands] [--max-steps N]]\n"
                               "  --split: patterns of genome length, cut into segments of --seg-len bases walked side by side; .lengths / .mems are identical to the run without it, .pointers may name other positions of the same matches\n"
                               "  --bgzf: the SAM output (single end, -1 / -2, -m, --extend) as blocked gzip in <output>.gz, compressed on the GPU; samtools, htslib and bgzip -d read it as SAM\n"
                               "  --host-inflate: BGZF (blocked gzip) input of single-end and -1 / -2 alignment is inflated on the GPU; this option sends it through zlib on the host, as plain gzip, -m, -c, --extend, the legacy and pattern-query modes and FASTA with wrapped lines always go\n"
@@ -470,7 +499,10 @@ static void parse(int argc, char** argv, Args& a) {
                               "  --bam: the SAM output (the same four modes) as BAM in <output>.bam (a trailing .sam becomes .bam): header and records encoded and compressed on the GPU, unsorted, no index\n"
                               "  --sort: with --bam, the records in coordinate order (samtools sort's: reference, position, forward strand first; ties keep input order) under @HD SO:coordinate, and the index in <output>.bam.bai; sorted on the GPU, merged through a temporary file beside the output\n"
                               "  --sort-chunk BYTES: uncompressed bytes of the records sorted and compressed per call in the merge (268435456; at least 65536)\n"
-                              "  --mark-dup: with --sort (single end and -1 / -2), duplicates get flag 0x400 (Picard's rule on unclipped 5' ends, strands and the sum of base qualities of 15 and more; no optical duplicates, no UMIs): signatures on the GPU while a batch's records are still there, one resolve over all batches between the two phases of the sort, the flags set as the chunks are merged\n";
+                              "  --mark-dup: with --sort (single end and -1 / -2), duplicates get flag 0x400 (Picard's rule on unclipped 5' ends, strands and the sum of base qualities of 15 and more; no optical duplicates, no UMIs): signatures on the GPU while a batch's records are still there, one resolve over all batches between the two phases of the sort, the flags set as the chunks are merged\n"
+                              "  --coverage: with --sort, the depth of coverage of the sorted records (mosdepth --fast-mode with deletions counted: no mate-overlap correction; records with flag & 1796 are skipped, so --mark-dup's duplicates do not count): added on the GPU while a chunk of the merge is still there; <output>.bam.mosdepth.summary.txt and <output>.bam.per-base.bed.gz, and with --cov-window N the windows' mean depth in <output>.bam.regions.bed.gz; 4 bytes of the GPU's memory per reference base, one GPU\n"
+                              "  --cov-window N: with --coverage, windows of N bases (1 to 2147483647)\n"
+                              "  --cov-mapq Q: with --coverage, records with a mapping quality below Q are skipped (0 to 255; 0)\n";
     int c;
     char* s;
     optind = 1;
@@ -517,7 +549,9 @@ static void parse(int argc, char** argv, Args& a) {
 }
 
 // what --dry-run says of the output's kind
-static const char* output_word(const Args& a) { return a.bgzf ? " bgzf=1" : !a.bam ? "" : !a.sort ? " bam=1" : a.mark_dup ? " bam=1 sort=1 markdup=1" : " bam=1 sort=1"; }
+static const char* output_word(const Args& a) {
+    return a.bgzf ? " bgzf=1" : !a.bam ? "" : !a.sort ? " bam=1" : a.mark_dup ? (a.coverage ? " bam=1 sort=1 markdup=1 coverage=1" : " bam=1 sort=1 markdup=1") : a.coverage ? " bam=1 sort=1 coverage=1" : " bam=1 sort=1";
+}
 
 // ---- the output of a run that writes SAM ------------------------------------------------------------------------------------------------
 // Placer: blocks that come in any order land in one file in the order of their ids, each at the prefix sum of the lengths before it.
@@ -590,6 +624,7 @@ struct Sink : Placer {
     void open(const std::string& file, const Args& a, bool paired) {
         path = file; bgzf = a.bgzf; bam = a.bam; sort = a.sort; sort_chunk = a.sort_chunk;
         sorted.mark = a.mark_dup; sorted.paired = paired ? 1 : 0;
+        sorted.cover.on = a.coverage; sorted.cover.window = a.cov_window; sorted.cover.min_mapq = a.cov_mapq;
         Placer::open(file);
     }
     // --bam: the header becomes the dictionary of every context that will encode records; returns the BAM header, in cs[0]'s buffer.  begin calls it; a pipeline
@@ -632,6 +667,81 @@ struct Sink : Placer {
     }
 };
 
+
+// The files of --coverage.  The per-base text comes in pieces from moni_cov_next and goes through the blocks of --bgzf; the regions are formatted
+// here from the windows' sums, a reference at a time.
+static void write_coverage(moni_ctx_t* c, moni_cov_t* cov, const CoverageOut& co, const std::string& bam_path, const std::string& header, uint64_t counted, uint64_t records) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<std::string> names;          // the first SN: of every @SQ line, as the dictionary takes it
+    for (size_t at = 0; at < header.size();) {
+        const size_t e = std::min(header.find('\n', at), header.size());
+        for (size_t f = at + 4; !header.compare(at, 4, "@SQ\t") && f < e;) {
+            const size_t g = std::min(header.find('\t', f), e);
+            if (!header.compare(f, 3, "SN:")) { names.push_back(header.substr(f + 3, g - f - 3)); break; }
+            f = g + 1;
+        }
+        at = e + 1;
+    }
+    const moni_cov_ref_t* refs = nullptr; uint32_t n_ref = 0;
+    int rc = moni_cov_seal(c, cov, &refs, &n_ref);
+    if (rc) die("moni_cov_seal failed (" + std::to_string(rc) + ")");
+    if (names.size() != n_ref) die("--coverage: the header's @SQ lines and the dictionary disagree");
+    auto open_out = [](const std::string& p) { FILE* f = fopen(p.c_str(), "w"); if (!f) die("open() file " + p + " failed"); return f; };
+    char line[512];
+    // the summary
+    uint64_t t_len = 0, t_bases = 0; uint32_t t_min = n_ref ? 0xFFFFFFFFu : 0u, t_max = 0;
+    {
+        FILE* f = open_out(bam_path + ".mosdepth.summary.txt");
+        std::string out = "chrom\tlength\tbases\tmean\tmin\tmax\n";
+        for (uint32_t r = 0; r < n_ref; ++r) {
+            snprintf(line, sizeof line, "\t%llu\t%llu\t%.2f\t%u\t%u\n", (unsigned long long)refs[r].length, (unsigned long long)refs[r].bases, (double)refs[r].bases / (double)refs[r].length, refs[r].min, refs[r].max);
+            out += names[r] + line;
+            t_len += refs[r].length; t_bases += refs[r].bases; t_min = std::min(t_min, refs[r].min); t_max = std::max(t_max, refs[r].max);
+        }
+        snprintf(line, sizeof line, "total\t%llu\t%llu\t%.2f\t%u\t%u\n", (unsigned long long)t_len, (unsigned long long)t_bases, t_len ? (double)t_bases / (double)t_len : 0.0, t_min, t_max);
+        out += line;
+        put(out.data(), out.size(), f);
+        close_out(f);
+    }
+    // the per-base text
+    uint64_t n_lines = 0;
+    {
+        FILE* f = open_out(bam_path + ".per-base.bed.gz");
+        for (int done = 0; !done;) {
+            const char* t = nullptr; uint64_t tl = 0;
+            rc = moni_cov_next(c, cov, co.max_bases, co.max_lines, &t, &tl, &done);
+            if (rc) die("moni_cov_next failed (" + std::to_string(rc) + ")");
+            n_lines += (uint64_t)std::count(t, t + tl, '\n');
+            const Block z = Sink::bgzf_blocks(c, t, tl, false);
+            put(z.p, z.n, f);
+        }
+        const Block z = Sink::bgzf_blocks(c, nullptr, 0, true);
+        put(z.p, z.n, f);
+        close_out(f);
+    }
+    // the regions
+    if (co.window) {
+        FILE* f = open_out(bam_path + ".regions.bed.gz");
+        std::string out;
+        auto flush = [&](bool eof) { const Block z = Sink::bgzf_blocks(c, out.data(), out.size(), eof); put(z.p, z.n, f); out.clear(); };
+        for (uint32_t r = 0; r < n_ref; ++r) {
+            const uint64_t* sums = nullptr; uint64_t nw = 0;
+            rc = moni_cov_windows(c, cov, r, co.window, &sums, &nw);
+            if (rc) die("moni_cov_windows failed (" + std::to_string(rc) + ")");
+            for (uint64_t k = 0; k < nw; ++k) {
+                const uint64_t a = k * co.window, b = std::min<uint64_t>(a + co.window, refs[r].length);
+                snprintf(line, sizeof line, "\t%llu\t%llu\t%.2f\n", (unsigned long long)a, (unsigned long long)b, (double)sums[k] / (double)(b - a));
+                out += names[r]; out += line;
+                if (out.size() >= (32u << 20)) flush(false);
+            }
+        }
+        flush(true);
+        close_out(f);
+    }
+    snprintf(line, sizeof line, "%.2f", t_len ? (double)t_bases / (double)t_len : 0.0);
+    info("Coverage: " + std::to_string(counted) + " counted of " + std::to_string(records) + " records, mean depth " + line + " over " + std::to_string(t_len) + " bases of " +
+         std::to_string(n_ref) + " references; " + std::to_string(n_lines) + " per-base lines in " + std::to_string(std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()) + " s: " + bam_path + ".per-base.bed.gz");
+}
 
 // ---- streaming path for plain files ---------------------------------------------------------------------------------------------------
 namespace fastpath {
@@ -1672,6 +1782,12 @@ static const OutputFlag OUTPUT_FLAGS[] = {
     }},
     // duplicate marking: a decision over the whole input, so it lives between the two phases of the sort; one record per read
     {{&Args::mark_dup, "--mark-dup"}, {&Args::sort, "--sort"}, {{&Args::extend, "--extend"}, {&Args::report_mems, "-m"}}, false, nullptr},
+    // depth of coverage: added where the sorted records lie, so it lives in the second phase of the sort
+    {{&Args::coverage, "--coverage"}, {&Args::sort, "--sort"}, {{&Args::extend, "--extend"}, {&Args::report_mems, "-m"}}, false, [](const Args& a) {
+        if (a.cov_window_set && (!a.coverage || a.cov_window_bad)) die(a.coverage ? "--cov-window takes 1 to 2147483647 bases" : "--cov-window belongs to --coverage");
+        if (a.cov_mapq_set && (!a.coverage || a.cov_mapq_bad)) die(a.coverage ? "--cov-mapq takes 0 to 255" : "--cov-mapq belongs to --coverage");
+        if (a.coverage && a.gpus > 1) die("--coverage takes one GPU (--gpus 1)");
+    }},
     {{&Args::bam, "--bam"}, {}, {B_BGZF, B_C, B_DRY_WRITE}, true, nullptr},          // one container
 };
 static void check_output_flags(const Args& a) {
