@@ -885,6 +885,17 @@ int moni_seed_occ_stats(moni_ctx_t *ctx, uint64_t out[6]);
 int moni_seed_prefilter(moni_ctx_t *ctx, int mode);
 /* The filter in the last seeding run: out[0] tasks, [1] tasks skipped, [2] table lookups, [3] the table's density x 1e6. */
 int moni_seed_prefilter_stats(moni_ctx_t *ctx, uint64_t out[4]);
+/* The leaping walk of the seeding stage (csrc/seed_core.h: ms_task_events_leap): behind 8 matched steps in a row the walk compares the read with
+ * the text and crosses the rest of the matched stretch in one move, re-entering through a sampled inverse suffix array that every index
+ * carries (one entry per `stride` text positions, built on the device when the index is created; MONI_MS_LEAP_STRIDE=8|16|32).  The seeds and
+ * moni_last_counters are the same with and without it: [0] there counts the reference walk's steps, not the rows fetched.  MONI_MS_LEAP=0 at
+ * index creation leaves the tables out, in a new context it leaves them unused.  Of the last seeding run: out[0] leaps, [1] steps leapt,
+ * [2] comparisons started, [3] the table's stride (0: the index has no table). */
+int moni_ms_leap_stats(moni_ctx_t *ctx, uint64_t out[4]);
+/* The table itself (tests): *n_entries entries, isa[i] = run | off << 32 of ISA[i * stride] and clean[i] = the number of text bytes from
+ * i * stride on that are A / C / G / T, at most 255; *build_ms the time its build took on the device.  Any pointer may be NULL; cap: the
+ * entries isa and clean have room for (MONI_EINVAL if fewer than *n_entries). */
+int moni_index_leap_table(const moni_index_t *index, uint64_t *isa, uint8_t *clean, uint64_t cap, uint64_t *n_entries, uint32_t *stride, float *build_ms);
 const char *moni_version(void);
 
 #ifdef __cplusplus

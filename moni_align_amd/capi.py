@@ -24,7 +24,7 @@ EXPORTS = [
     "moni_index_device_bytes", "moni_index_text", "moni_ctx_create", "moni_ctx_destroy", "moni_reads_upload", "moni_reads_swap", "moni_ms_run",
     "moni_ms_query_batch", "moni_seed_run", "moni_seed_counts", "moni_seed_fetch", "moni_seed_batch", "moni_free",
     "moni_phi_lcp_batch", "moni_extz_batch", "moni_last_kernel_ms", "moni_last_counters", "moni_seed_occ_stats",
-    "moni_seed_prefilter", "moni_seed_prefilter_stats",
+    "moni_seed_prefilter", "moni_seed_prefilter_stats", "moni_ms_leap_stats", "moni_index_leap_table",
     "moni_align_params_default", "moni_align_batch", "moni_align_csv_batch", "moni_align_run", "moni_align_stream", "moni_sam_header",
     "moni_ldx_info", "moni_ldx_rewrite", "moni_ldx_lift_batch", "moni_ldx_write",
     "moni_ms_file_info", "moni_ms_file_read", "moni_ms_file_write", "moni_index_load_reference", "moni_ms_lengths_batch", "moni_report_mems_batch",
@@ -460,6 +460,8 @@ def lib():
         L.moni_seed_occ_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.moni_seed_prefilter.argtypes = [C.c_void_p, C.c_int]
         L.moni_seed_prefilter_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.moni_ms_leap_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.moni_index_leap_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
         L.moni_ms_lengths_batch.argtypes = [C.c_void_p, C.POINTER(ReadBatchC), C.c_void_p, C.c_void_p]
         L.moni_mslong_params_default.argtypes = [C.POINTER(MslongParamsC)]
         L.moni_mslong_params_default.restype = None
@@ -654,6 +656,17 @@ class Index:
         self.n = self._L.moni_index_n(self._h)
         self.r = self._L.moni_index_r(self._h)
         self.device_bytes = self._L.moni_index_device_bytes(self._h)
+
+    def leap_table(self, fetch: bool = True):
+        """the sampled inverse suffix array of the leaping walk (moni_index_leap_table): stride, build time in ms, and with fetch the entries
+        (run | off << 32) and their clean bytes; stride 0 and empty arrays for an index made under MONI_MS_LEAP=0"""
+        n_ent, stride, ms = C.c_uint64(), C.c_uint32(), C.c_float()
+        _chk(self._L.moni_index_leap_table(self._h, None, None, 0, C.byref(n_ent), C.byref(stride), C.byref(ms)), "moni_index_leap_table")
+        isa = np.zeros(n_ent.value if fetch else 0, dtype=np.uint64)
+        clean = np.zeros(n_ent.value if fetch else 0, dtype=np.uint8)
+        if fetch and n_ent.value:
+            _chk(self._L.moni_index_leap_table(self._h, isa.ctypes.data, clean.ctypes.data, n_ent.value, None, None, None), "moni_index_leap_table")
+        return {"stride": int(stride.value), "build_ms": float(ms.value), "isa": isa, "clean": clean}
 
     def text(self) -> np.ndarray:
         """the text of the index (n - 1 bytes), as handed over or as rebuilt from the BWT"""
@@ -1452,6 +1465,13 @@ class Ctx:
         out = np.zeros(4, dtype=np.uint64)
         _chk(self._L.moni_seed_prefilter_stats(self._h, out.ctypes.data), "moni_seed_prefilter_stats")
         return {"tasks": int(out[0]), "skipped": int(out[1]), "lookups": int(out[2]), "density": float(out[3]) / 1e6}
+
+
+    def ms_leap_stats(self) -> Dict[str, int]:
+        """the leaps of the walk in the last seeding run (moni_ms_leap_stats); stride 0: the index has no table"""
+        out = np.zeros(4, dtype=np.uint64)
+        _chk(self._L.moni_ms_leap_stats(self._h, out.ctypes.data), "moni_ms_leap_stats")
+        return dict(zip(("leaps", "steps_leapt", "comparisons", "stride"), (int(v) for v in out)))
 
 
 def ldx_info(path: str):

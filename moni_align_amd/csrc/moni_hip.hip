@@ -105,6 +105,7 @@ struct moni_index {
     DBuf<uint32_t> d_phi_dir, d_phi_inv_dir;
     DBuf<uint8_t> d_text;
     DBuf<uint64_t> d_text2; DBuf<uint32_t> d_exc; uint32_t exc_sh = 10, exc_words = 0;      // 2-bit text and its exception bitmap (seed_core.h: mem_fast_t)
+    DBuf<uint64_t> d_isa, d_clean; uint32_t leap_sh = 0; float leap_build_ms = 0;      // the sampled inverse suffix array of the leaping walk and its clean bytes (seed_core.h: ms_leap_t); d_isa.p null: no leaping
     DBuf<uint32_t> d_kmers; uint32_t pf_k = 0; double pf_density = 0; bool pf_on = false; float pf_build_ms = 0; bool compl_acgt = false;      // the text's k-mers, one bit each (prefilter_core.h); pf_on: sparse enough to filter with
     DBuf<uint64_t> d_seq_starts;
     DBuf<uint32_t> d_name_id;
@@ -148,6 +149,8 @@ struct moni_ctx : ResidentBatch {            // (the base: the resident batch)
     int seed_prefilter = 1;                    // moni_seed_prefilter: 0 off, 1 in the align and paired paths, 2 in moni_seed_run too
     bool seed_fuse = true;                     // the filtered stage runs pack_filter_kernel (MONI_SEED_FUSE=0: pack_kernel + strand_filter_kernel)
     DBuf<uint64_t> evl; DBuf<uint32_t> evl_cnt;  // the seeding stage's walk as event lists (seed_core.h: ms_task_events) and their lengths per task, in place of ptr
+    bool ms_leap = true;                       // the staged walk leaps over matched stretches where the index has the tables (MONI_MS_LEAP=0: stepwise)
+    DBuf<unsigned long long> leap_stats;       // leaps, steps leapt, comparisons of the last seeding run (moni_ms_leap_stats)
     bool ms_events = true;                     // seed_all takes the event lists (MONI_MS_EVENTS=0: the dense pointers, as every other caller of ms_launch does)
     bool pf_active = false;                    // the last ms_launch filtered: pf_live / pf_pos[n_tasks] are the live list and its length
     uint64_t pf_tasks = 0;                     // tasks of the last seeding run
@@ -517,6 +520,23 @@ int moni_index_create(const moni_flat_index_t* f, int device, moni_index_t** out
         hipLaunchKernelGGL(text2_build_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, 0, I->d_text.p, n_text, n_words, I->d_text2.p, I->d_exc.p, I->exc_sh);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { moni_index_destroy(I); return MONI_ENODEV; }
     }
+    if (const char* v = getenv("MONI_MS_LEAP"); !v || atoi(v) != 0) {   // the tables of the leaping walk (seed_core.h), from the rows and the byte text on the device
+        const uint64_t n = f->n, r = f->r;
+        uint32_t sh = MONI_LEAP_SH;
+        if (const char* w = getenv("MONI_MS_LEAP_STRIDE")) { const int x = atoi(w); if (x == 8) sh = 3; else if (x == 16) sh = 4; else if (x == 32) sh = 5; }
+        const uint64_t n_ent = ((n - 1) >> sh) + 1, clean_words = n_ent / 8 + 2, chunk = 4096;
+        DBuf<uint64_t> d_ssa;
+        Event e0, e1;
+        if (I->d_isa.alloc_exact(n_ent + 2) || I->d_clean.alloc_exact(clean_words) || d_ssa.alloc_exact(r + 1)) { moni_index_destroy(I); return MONI_ENOMEM; }
+        I->bytes += (n_ent + 2) * 8 + clean_words * 8;
+        if (hipMemcpy(d_ssa.p, f->ssa, r * 8, hipMemcpyHostToDevice) != hipSuccess || hipEventCreate(&e0.h) != hipSuccess || hipEventCreate(&e1.h) != hipSuccess ||
+            hipEventRecord(e0, 0) != hipSuccess || hipMemsetAsync(I->d_isa.p, 0, (n_ent + 2) * 8, 0) != hipSuccess || hipMemsetAsync(I->d_clean.p, 0, clean_words * 8, 0) != hipSuccess) { moni_index_destroy(I); return MONI_ENODEV; }
+        hipLaunchKernelGGL(leap_clean_kernel, dim3((unsigned)(((n + chunk - 1) / chunk + 255) / 256)), dim3(256), 0, 0, I->d_text.p, n - 1, n, chunk, sh, reinterpret_cast<uint8_t*>(I->d_clean.p));
+        hipLaunchKernelGGL(isa_build_kernel, dim3((unsigned)((r + 255) / 256)), dim3(256), 0, 0, I->d_rows.p, r, n, d_ssa.p, sh, I->d_isa.p, reinterpret_cast<uint8_t*>(I->d_clean.p));
+        if (hipEventRecord(e1, 0) != hipSuccess || hipGetLastError() != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&I->leap_build_ms, e0, e1) != hipSuccess) { moni_index_destroy(I); return MONI_ENODEV; }
+        I->leap_sh = sh;
+        if (getenv("MONI_AK_PROFILE")) fprintf(stderr, "moni_hip: leap tables: stride %u, %.1f MB, built in %.2f ms\n", 1u << sh, ((n_ent + 2) * 8 + clean_words * 8) / 1e6, I->leap_build_ms);
+    }
     {   // the k-mer table of the strand prefilter, from the byte text on the device (the 2-bit text codes a byte outside A / C / G / T as A)
         const uint64_t n_text = f->n - 1, n_words = n_text / 32 + 1;
         I->pf_k = pf_choose_k(n_text);
@@ -652,11 +672,12 @@ int moni_ctx_create(moni_index_t* I, moni_ctx_t** out) {
     if (const char* v = getenv("MONI_EXTZ_LDS")) c->extz_lds = atoi(v);
     if (const char* v = getenv("MONI_SEED_FUSE")) c->seed_fuse = atoi(v) != 0;
     if (const char* v = getenv("MONI_MS_EVENTS")) c->ms_events = atoi(v) != 0;
+    if (const char* v = getenv("MONI_MS_LEAP")) c->ms_leap = atoi(v) != 0;
     if (const char* v = getenv("MONI_SEED_PREFILTER")) { const int x = atoi(v); if (x >= 0 && x <= 2) c->seed_prefilter = x; }
     bool ok = hipStreamCreate(&c->stream.h) == hipSuccess;
     for (int i = 0; ok && i < EV_N; ++i) ok = hipEventCreate(&c->ev[i].h) == hipSuccess;
-    ok = ok && c->d_small.alloc_exact(1) == MONI_OK && c->d_counters.alloc_exact(4) == MONI_OK && c->pf_stats.alloc_exact(2) == MONI_OK &&
-         hipMemset(c->pf_stats.p, 0, 2 * sizeof(unsigned long long)) == hipSuccess && hipMemset(c->d_small.p, 0, sizeof(occ_small_t)) == hipSuccess && hipMemset(c->d_counters.p, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
+    ok = ok && c->d_small.alloc_exact(1) == MONI_OK && c->d_counters.alloc_exact(4) == MONI_OK && c->pf_stats.alloc_exact(2) == MONI_OK && c->leap_stats.alloc_exact(4) == MONI_OK &&
+         hipMemset(c->pf_stats.p, 0, 2 * sizeof(unsigned long long)) == hipSuccess && hipMemset(c->leap_stats.p, 0, 4 * sizeof(unsigned long long)) == hipSuccess && hipMemset(c->d_small.p, 0, sizeof(occ_small_t)) == hipSuccess && hipMemset(c->d_counters.p, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) { fprintf(stderr, "moni_hip: context creation failed on device %d\n", I->device); moni_ctx_destroy(c); return MONI_ENODEV; }
     *out = c;
     return MONI_OK;
@@ -666,6 +687,13 @@ void moni_ctx_destroy(moni_ctx_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->idx->device);          // the members free their memory, streams and events: on this context's GPU,
     if (c->stream) (void)hipStreamSynchronize(c->stream);      // ... with its stream idle
+    if (getenv("MONI_AK_PROFILE") && c->leap_stats.p && c->pf_stats.p && c->d_counters.p) {          // the walk of the context's last seeding run
+        unsigned long long lp[4] = {0, 0, 0, 0}, pf[2] = {0, 0}, cn[4] = {0, 0, 0, 0};
+        if (hipMemcpy(lp, c->leap_stats.p, sizeof lp, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(pf, c->pf_stats.p, sizeof pf, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(cn, c->d_counters.p, sizeof cn, hipMemcpyDeviceToHost) == hipSuccess)
+            fprintf(stderr, "moni_hip: last seeding run: %llu tasks, %llu skipped by the prefilter, S %llu, J %llu; %llu leaps, %llu steps leapt, %llu comparisons\n",
+                    (unsigned long long)c->pf_tasks, pf[0], cn[0], cn[1], lp[0], lp[1], lp[2]);
+    }
     delete c;
 }
 
@@ -776,6 +804,14 @@ static int ms_launch(moni_ctx* c, const moni_tables_t* tabs = nullptr, uint32_t 
 #define MS_LAUNCH(NCH, MINW, STAGED) do { const uint64_t nl = (n_tasks + (NCH) - 1) / (NCH); \
         hipLaunchKernelGGL((ms_lf_events_kernel<NCH, MINW, STAGED>), dim3((unsigned)((nl + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream, \
                            I->K, tabs, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p, n_tasks, c->evl.p, c->evl_cnt.p, c->d_counters.p, live, n_live); } while (0)
+        // the product's instance (one task per lane, staged) leaps where the index has the tables and the 2-bit text; every other variant walks step by step
+        const bool leap = c->ms_leap && I->d_isa.p && I->d_text2.p && MONI_MS_EV_STAGE != 0 && (c->ms_variant == 0 || c->ms_variant == 4 || c->ms_variant > 5 || c->ms_variant < 0);
+        if (leap) {
+            ms_leap_t Z; Z.isa = I->d_isa.p; Z.clean = I->d_clean.p; Z.text2 = I->d_text2.p; Z.n_text = I->K.n_text; Z.sh = I->leap_sh;
+            hipLaunchKernelGGL((ms_lf_leap_kernel<6>), dim3((unsigned)((n_tasks + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, c->stream,
+                               I->K, tabs, I->d_rows.p, I->d_frows.p, I->d_cr.p, I->d_recs.p, c->pat.p, c->offs.p, c->blk.p, n_tasks, c->evl.p, c->evl_cnt.p, c->d_counters.p, live, n_live,
+                               Z, c->pflag.p, c->leap_stats.p);
+        } else
         switch (c->ms_variant) {
             case 1: MS_LAUNCH(1, 8, MONI_MS_EV_STAGE != 0); break;
             case 2: MS_LAUNCH(2, 8, false); break;
@@ -883,6 +919,7 @@ static int seed_all(moni_ctx* c, const moni_seed_params_t* prm, bool align_path)
     HIPCHK(hipMemsetAsync(c->d_counters.p, 0, 4 * sizeof(unsigned long long), c->stream));
     HIPCHK(hipMemsetAsync(c->d_small.p, 0, sizeof(occ_small_t), c->stream));
     HIPCHK(hipMemsetAsync(c->pf_stats.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->leap_stats.p, 0, 4 * sizeof(unsigned long long), c->stream));
     c->pf_tasks = n_tasks;
     // the strand prefilter: where the mode asks for it, the index's table is sparse enough and min_len leaves a window of k-mers (prefilter_core.h)
     const bool filter = (c->seed_prefilter == 2 || (c->seed_prefilter == 1 && align_path)) && I->pf_on && prm->min_len >= I->pf_k;
@@ -1026,6 +1063,29 @@ int moni_seed_prefilter_stats(moni_ctx_t* c, uint64_t out[4]) {
     unsigned long long h[2];
     HIPCHK(hipMemcpy(h, c->pf_stats.p, sizeof(h), hipMemcpyDeviceToHost));
     out[0] = c->pf_tasks; out[1] = h[0]; out[2] = h[1]; out[3] = (uint64_t)(c->idx->pf_density * 1e6 + 0.5);
+    return MONI_OK;
+}
+
+int moni_ms_leap_stats(moni_ctx_t* c, uint64_t out[4]) {
+    if (!c || !out) return MONI_EINVAL;
+    HIPCHK(hipSetDevice(c->idx->device));
+    unsigned long long h[4];
+    HIPCHK(hipMemcpy(h, c->leap_stats.p, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = c->idx->d_isa.p ? 1ull << c->idx->leap_sh : 0;
+    return MONI_OK;
+}
+
+int moni_index_leap_table(const moni_index_t* I, uint64_t* isa, uint8_t* clean, uint64_t cap, uint64_t* n_entries, uint32_t* stride, float* build_ms) {
+    if (!I) return MONI_EINVAL;
+    const uint64_t n_ent = I->d_isa.p ? ((I->K.n - 1) >> I->leap_sh) + 1 : 0;
+    if (n_entries) *n_entries = n_ent;
+    if (stride) *stride = I->d_isa.p ? 1u << I->leap_sh : 0;
+    if (build_ms) *build_ms = I->leap_build_ms;
+    if (!isa && !clean) return MONI_OK;
+    if (cap < n_ent) return MONI_EINVAL;
+    HIPCHK(hipSetDevice(I->device));
+    if (isa && n_ent) HIPCHK(hipMemcpy(isa, I->d_isa.p, n_ent * 8, hipMemcpyDeviceToHost));
+    if (clean && n_ent) HIPCHK(hipMemcpy(clean, I->d_clean.p, n_ent, hipMemcpyDeviceToHost));
     return MONI_OK;
 }
 

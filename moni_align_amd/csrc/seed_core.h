@@ -283,11 +283,14 @@ MONI_HD void ms_step_general(const moni_consts_t& K, const lds_tables_t& L, cons
 #define MS_ATTR_WALK(nj)
 #define MS_ATTR_GEN(nj)
 #endif
-// One LF step of one task for symbol code c (moni.hpp:579-621).
+// One LF step of one task for symbol code c (moni.hpp:579-621).  have_pre: pre holds words 0 and 1 of frows[S.run], fetched by the caller in front of
+// the call (ms_task_events_leap asks for them together with its other loads); otherwise they are fetched here.  A state that is re-anchored first
+// does not use them.
 MONI_HD void ms_step(const moni_consts_t& K, const lds_tables_t& L, const moni_row_t* __restrict__ rows,
                      const moni_frow_t* __restrict__ frows, const uint32_t* __restrict__ cr, const moni_rec_t* __restrict__ recs,
-                     uint32_t c, ms_state_t& S, unsigned long long& n_jumps) {
-    if (S.abs) {                                             // re-anchor an absolute position: (run, off)
+                     uint32_t c, ms_state_t& S, unsigned long long& n_jumps, bool have_pre = false, moni_u64x2 pre = moni_u64x2()) {
+    if (S.abs) {
+        have_pre = false;                                             // re-anchor an absolute position: (run, off)
         moni_row_t A;
         settle_run(rows, K.r, S.pos, S.run, A);
         S.off = (uint32_t)(S.pos - row_start(A));            // < 2^32 unless the run is longer, in which case the row is not "ok" anyway
@@ -297,7 +300,8 @@ MONI_HD void ms_step(const moni_consts_t& K, const lds_tables_t& L, const moni_r
     const uint32_t hc = L.hot_slot[c];
     while (true) {
         const moni_frow_t* __restrict__ fr = frows + S.run;
-        const moni_u64x2 q0 = *reinterpret_cast<const moni_u64x2*>(&fr->w[0]);   // w0, w1
+        const moni_u64x2 q0 = have_pre ? pre : *reinterpret_cast<const moni_u64x2*>(&fr->w[0]);   // w0, w1
+        have_pre = false;
         const uint64_t w0 = q0.x;
         const uint32_t len = (uint32_t)w0 & 0xFFFu;
         if (!((w0 >> 58) & 1u) || hc >= 4) {                 // general path: absolute position from the 32-byte row
@@ -507,6 +511,174 @@ MONI_HD void ms_task_events(const moni_consts_t& K, const lds_tables_t& L, const
                 ev_cnt[tk[k]] = ne[k];
             }
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Leaping over matched stretches (the staged walk of the seeding stage).
+// After every step that went through ms_step, and in the start state, the walk's BWT position is ISA[sample]: `sample` is the text position of the
+// pattern byte just consumed, so the next step matches exactly when the next pattern byte is text[sample - 1].  A matched step makes no event, so a
+// stretch of them can be crossed on the text: compare pattern and text backwards from sample - 1 (32 bases per XOR of 2-bit words), and take the
+// BWT position at the far end from a sampled inverse suffix array.  An absent byte breaks the relation (it assigns sample 0 and the position F[b]);
+// it holds again from the next jump on.
+//   isa[t >> sh]    the (run, off << 32) state of ISA[t] for every text position t that is a multiple of the stride 2^sh, t = 0 .. n - 1
+//   clean[t >> sh]  how many bytes of the text from t on are A / C / G / T, at most 255 (one byte per entry).  The 2-bit text codes every other byte
+//                   as A, so a leap to t over L steps is taken only if clean >= L; no leap is longer than 255 steps (a longer stretch leaps again).
+// Both are built from the index image alone (isa_walk_run, leap_clean_chunk), once per index.
+// ------------------------------------------------------------------------------------------------
+#define MONI_LEAP_SH 4u                    // stride 16 (MONI_MS_LEAP_STRIDE=8|16|32 at index creation)
+#ifndef MONI_LEAP_T
+#define MONI_LEAP_T 8u                     // matched steps in a row behind a jump before the text is asked (profiles/ms_leap: -DMONI_LEAP_T=4u .. 16u)
+#endif
+#ifndef MONI_LEAP_KMIN
+#define MONI_LEAP_KMIN 8u                  // a stretch of fewer than stride + KMIN further matches is walked
+#endif
+#define MONI_LEAP_MAX 255u
+struct ms_leap_t {
+    const uint64_t* isa; const uint64_t* clean;      // clean: the bytes as 64-bit words
+    const uint64_t* text2;                           // seed_core.h: text2_word
+    uint64_t n_text; uint32_t sh;
+};
+struct moni_u64pair { uint64_t x, y; };              // 16 bytes at an 8-byte aligned address
+
+// The lane of run k in the table's build: from the LF image of the run's first position, whose text position is ssa_k = SA[start] - 1, down the text
+// with the BWT's own symbol (always a match) until the position reached is a run's first one - the lane of that run goes on from its LF image - or
+// the text's start.  Every text position is visited by exactly one lane.  off > 0xFFFFFFFE (a run of 2^32 positions): the entry's clean byte is
+// cleared, so that no leap takes it.  Needs clean to be built first.
+MONI_HD void isa_walk_run(const moni_row_t* __restrict__ rows, uint64_t r, uint64_t n, uint64_t k, uint64_t ssa_k, uint32_t sh,
+                          uint64_t* __restrict__ isa, uint8_t* __restrict__ clean) {
+    moni_row_t A = ld_row(rows, (uint32_t)k);
+    uint64_t pos = row_lfbase(A), sample = ssa_k % n;
+    uint32_t run = row_dest(A);
+    const uint64_t mask = (1ull << sh) - 1;
+    while (true) {
+        settle_run(rows, r, pos, run, A);
+        const uint64_t off = pos - row_start(A);
+        if (!(sample & mask)) {
+            if (off > 0xFFFFFFFEull) { isa[sample >> sh] = 0; clean[sample >> sh] = 0; }
+            else isa[sample >> sh] = (uint64_t)run | (off << 32);
+        }
+        if (off == 0 || sample == 0) break;
+        pos = row_lfbase(A) + off; run = row_dest(A); --sample;
+    }
+}
+// clean bytes of the entries in text positions [c0, c1), from the back: the count at c1 first, then one byte of text per position
+MONI_HD void leap_clean_chunk(const uint8_t* __restrict__ text, uint64_t n_text, uint64_t c0, uint64_t c1, uint32_t sh, uint8_t* __restrict__ clean) {
+    uint32_t cnt = 0;
+    { uint64_t e = c1; while (e < n_text && cnt < MONI_LEAP_MAX && base_acgt(text[e])) { ++e; ++cnt; } }
+    const uint64_t mask = (1ull << sh) - 1;
+    for (uint64_t t = c1; t-- > c0;) {
+        cnt = (t < n_text && base_acgt(text[t])) ? (cnt < MONI_LEAP_MAX ? cnt + 1u : MONI_LEAP_MAX) : 0u;
+        if (!(t & mask)) clean[t >> sh] = (uint8_t)cnt;
+    }
+}
+
+// ms_task_events<1, true> with leaps: the same event lists, counts, steps and jumps.  A lane advances its own step index, and every turn of its loop
+// is one round trip to memory whatever the lane is doing - a walk step (the fast row), a window of the comparison (two words of the 2-bit text) or the
+// table entry - with the address chosen first and the loads issued for all lanes together, so that lanes of a wavefront in different states do not
+// wait for one another's memory.  stats: [0] leaps, [1] steps leapt, [2] comparisons started.
+MONI_HD void ms_task_events_leap(const moni_consts_t& K, const lds_tables_t& L, const moni_row_t* __restrict__ rows,
+                                 const moni_frow_t* __restrict__ frows, const uint32_t* __restrict__ cr, const moni_rec_t* __restrict__ recs,
+                                 const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t n_tasks, uint64_t slot,
+                                 uint64_t* __restrict__ ev, uint32_t* __restrict__ ev_cnt, unsigned long long& n_steps, unsigned long long& n_jumps,
+                                 const uint64_t* __restrict__ live, uint64_t* stage, uint32_t stage_stride,
+                                 const ms_leap_t& Z, const uint8_t* __restrict__ pflag, unsigned long long* stats) {
+    if (slot >= n_tasks) return;
+    const uint64_t task = live ? live[slot] : slot; const uint64_t read = task >> 1;
+    const uint32_t m = (uint32_t)(offs[read + 1] - offs[read]);
+    if (!m) return;
+    const uint64_t pb = ws_pat_base(blk, task), eb = ws_ev_base(blk, task);
+    const uint64_t lb = ws_block_len(blk, task);
+    const uint64_t cb = pb + 64u * ((lb + 7) / 8);                  // the task's code words (pack_task); its mask words lie 64 * ((lb + 31) / 32) behind
+    const bool has_inv = pflag[task] != 0;
+    const uint32_t stride = 1u << Z.sh;
+    ms_state_t S;
+    S.m = m; S.run = (uint32_t)K.r - 1; S.pos = K.n - 1; S.abs = true; S.off = 0; S.sample = K.last_run_sample; S.word = 0;
+    n_steps += m;
+    enum { STEP = 0, PROBE = 1, ENTRY = 2 };
+    uint32_t mode = STEP, s = 0, ne = 0;
+    uint32_t cnt = 0;                  // matched steps in a row behind a jump or the start; above T: no comparison before the next jump
+    uint32_t k = 0;                    // PROBE: bases found equal so far
+    uint64_t t0 = 0;                   // ENTRY: the text position to leap to
+    bool capped = false;
+    while (s < m) {
+        const void* pa; const uint64_t* pw;
+        if (mode == STEP) { pa = frows + S.run; pw = pat + pb + (uint64_t)(s >> 3) * 64u; }
+        else if (mode == PROBE) {
+            // the window: pattern bases qi - sh .. qi of one code word (read order; step s + j consumes base m - 1 - s - j) against text a - sh .. a
+            const uint64_t a = S.sample - 1 - k; const uint32_t qi = m - 1u - s - k, sh = qi & 31u;
+            pa = Z.text2 + ((a >= sh ? a - sh : 0) >> 5); pw = pat + cb + (uint64_t)(qi >> 5) * 64u;
+        } else { pa = Z.isa + (t0 >> Z.sh); pw = Z.clean + (t0 >> (Z.sh + 3u)); }
+        const moni_u64pair qa = *reinterpret_cast<const moni_u64pair*>(pa);
+        const uint64_t qw = *pw;
+        if (mode == STEP) {
+            const uint32_t raw = (uint32_t)(qw >> (8u * (s & 7u))) & 0xFFu;
+            const uint32_t c = L.code[raw];
+            bool assigned = true;
+            if (c == MONI_CODE_ABSENT) {                      // n_c == 0   (moni.hpp:583-588)
+                S.sample = 0; S.pos = L.abs_pos[raw]; S.run = L.abs_run[raw]; S.abs = true;
+                cnt = MONI_LEAP_T + 1u;                        // the position is no longer ISA[sample]
+            } else {
+                const uint32_t j0 = (uint32_t)n_jumps;
+                moni_u64x2 q0; q0.x = qa.x; q0.y = qa.y;
+                ms_step(K, L, rows, frows, cr, recs, c, S, n_jumps, true, q0);
+                assigned = ((((uint32_t)n_jumps) ^ j0) & 0x0FFFFFFFu) != 0;
+                if (assigned) cnt = 0; else if (cnt <= MONI_LEAP_T) ++cnt;
+            }
+            if (assigned || s == 0) {
+                const uint64_t w = assigned ? (S.sample | ((uint64_t)(s + 1u) << MONI_EV_SHIFT)) : K.last_run_sample;
+                const uint32_t j = ne & (MONI_EV_STAGE_N - 1u);
+                stage[(uint64_t)j * stage_stride] = w;
+                if (j == MONI_EV_STAGE_N - 1u) {
+#pragma unroll
+                    for (uint32_t i = 0; i < MONI_EV_STAGE_N; i += 2) {          // (a list starts on a 64-byte boundary: the eight words are one line)
+                        moni_u64x2 two; two.x = stage[(uint64_t)i * stage_stride]; two.y = stage[(uint64_t)(i + 1u) * stage_stride];
+                        *reinterpret_cast<moni_u64x2*>(ev + eb + (ne - j) + i) = two;
+                    }
+                }
+                ++ne;
+            }
+            ++s;
+            // T matches in a row: ask the text, if the read has room for a leap and sample - 1 is a text position
+            if (cnt == MONI_LEAP_T && m - s >= stride + MONI_LEAP_KMIN && S.sample - 1 < Z.n_text) { mode = PROBE; k = 0; ++stats[2]; }
+        } else if (mode == PROBE) {
+            const uint64_t a = S.sample - 1 - k; const uint32_t qi = m - 1u - s - k, sh = qi & 31u, ta = (uint32_t)a & 31u;
+            uint32_t lim = sh + 1u;
+            if (a < sh) lim = (uint32_t)a + 1u;                // the text's start
+            // base a in the top two bits, the bases in front of it below
+            uint64_t tw;
+            if ((a >> 5) == ((a >= sh ? a - sh : 0) >> 5)) tw = qa.x << (2u * (31u - ta));
+            else tw = (qa.y << (2u * (31u - ta))) | (qa.x >> (2u * (ta + 1u)));          // (ta < sh <= 31 here)
+            uint64_t x = tw ^ (qw << (2u * (31u - sh)));
+            if (has_inv) x |= pat[cb + 64u * ((lb + 31) / 32) + (uint64_t)(qi >> 5) * 64u] << (2u * (31u - sh));
+            uint32_t eq = x ? (uint32_t)__builtin_clzll(x) >> 1 : 32u;
+            if (eq > lim) eq = lim;
+            k += eq;
+            if (eq < lim || k >= m - s || (uint64_t)k >= S.sample) {          // a difference, the read's end or the text's start
+                mode = STEP; cnt = MONI_LEAP_T + 1u;
+                if (k >= stride + MONI_LEAP_KMIN) {
+                    const uint64_t far = S.sample - k;
+                    t0 = (far + stride - 1u) & ~(uint64_t)(stride - 1u);
+                    capped = S.sample - t0 > MONI_LEAP_MAX;
+                    if (capped) t0 = (S.sample - MONI_LEAP_MAX + stride - 1u) & ~(uint64_t)(stride - 1u);
+                    mode = ENTRY;
+                }
+            }
+        } else {
+            const uint32_t len = (uint32_t)(S.sample - t0);
+            const uint32_t cl = (uint32_t)(qw >> (8u * ((uint32_t)(t0 >> Z.sh) & 7u))) & 0xFFu;
+            mode = STEP;
+            if (cl >= len) {
+                s += len; S.sample = t0; S.run = (uint32_t)qa.x; S.off = (uint32_t)(qa.x >> 32); S.abs = false;
+                ++stats[0]; stats[1] += len;
+                if (capped) cnt = 0;                           // the stretch may go on: count matches again
+            }
+        }
+    }
+    {   // the walk has ended: the staged events behind the last full line, and the count
+        const uint32_t rem = ne & (MONI_EV_STAGE_N - 1u);
+        for (uint32_t i = 0; i < rem; ++i) ev[eb + (ne - rem) + i] = stage[(uint64_t)i * stage_stride];
+        ev_cnt[task] = ne;
     }
 }
 

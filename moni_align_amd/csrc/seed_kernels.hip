@@ -97,6 +97,42 @@ ms_lf_events_kernel(const moni_consts_t K, const moni_tables_t* __restrict__ T, 
     wave_add(n_jumps, &counters[1]);
 }
 
+// ... with leaps over matched stretches (seed_core.h: ms_task_events_leap): the same lists and counters; leap[0..2] += leaps, steps leapt, comparisons
+template <int MINW>
+__global__ void __launch_bounds__(MS_BLOCK, MINW)
+ms_lf_leap_kernel(const moni_consts_t K, const moni_tables_t* __restrict__ T, const moni_row_t* __restrict__ rows,
+                  const moni_frow_t* __restrict__ frows, const uint32_t* __restrict__ cr, const moni_rec_t* __restrict__ recs,
+                  const uint64_t* __restrict__ pat, const uint64_t* __restrict__ offs, const moni_u64x2* __restrict__ blk, uint64_t n_tasks,
+                  uint64_t* __restrict__ ev, uint32_t* __restrict__ ev_cnt, unsigned long long* __restrict__ counters,
+                  const uint64_t* __restrict__ live, const uint64_t* __restrict__ n_live, const ms_leap_t Z, const uint8_t* __restrict__ pflag,
+                  unsigned long long* __restrict__ leap) {
+    if (live) {
+        n_tasks = *n_live;
+        if ((uint64_t)blockIdx.x * MS_BLOCK >= n_tasks) return;
+    }
+    __shared__ lds_tables_t L;
+    __shared__ uint64_t ST[MONI_EV_STAGE_N][MS_BLOCK];      // [event of the group][lane]
+    load_tables(L, T, K);
+    const uint64_t slot = (uint64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
+    unsigned long long n_steps = 0, n_jumps = 0, st[3] = {0, 0, 0};
+    ms_task_events_leap(K, L, rows, frows, cr, recs, pat, offs, blk, n_tasks, slot, ev, ev_cnt, n_steps, n_jumps, live, &ST[0][threadIdx.x], MS_BLOCK, Z, pflag, st);
+    wave_add(n_steps, &counters[0]);
+    wave_add(n_jumps, &counters[1]);
+    wave_add(st[0], &leap[0]);
+    wave_add(st[1], &leap[1]);
+    wave_add(st[2], &leap[2]);
+}
+// the leap tables, once per index (seed_core.h): the clean bytes, one thread per chunk of text positions; then the sampled ISA, one thread per run
+__global__ void __launch_bounds__(256) leap_clean_kernel(const uint8_t* __restrict__ text, uint64_t n_text, uint64_t n, uint64_t chunk, uint32_t sh, uint8_t* __restrict__ clean) {
+    const uint64_t c0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * chunk;
+    if (c0 < n) leap_clean_chunk(text, n_text, c0, c0 + chunk < n ? c0 + chunk : n, sh, clean);
+}
+__global__ void __launch_bounds__(256) isa_build_kernel(const moni_row_t* __restrict__ rows, uint64_t r, uint64_t n, const uint64_t* __restrict__ ssa, uint32_t sh,
+                                                        uint64_t* __restrict__ isa, uint8_t* __restrict__ clean) {
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < r) isa_walk_run(rows, r, n, k, ssa[k], sh, isa, clean);
+}
+
 // W: 64-bit pattern code words per lane in LDS (reads of up to 32 W bases take the 2-bit comparison; longer ones in the same launch compare bytes)
 template <bool EMIT, int W, class SRC>
 __device__ __forceinline__ void
